@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: VideoCoF 4-step denoising on the HIP-backed Wan2.1 DiT.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 14b-cof]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload 14b-cof] [--dump-outputs DIR] [--full]
 
 A *step* is one denoise step of the reference loop (pipeline_wan.py:694-740): one DiT forward
 over the whole CoF token slab + `noise_pred[:, :, :cc] = 0` + one UniPC update.  Inputs are
@@ -18,7 +18,10 @@ scaling; what the reference CLI does, fast_infer.py:272).  The N > 1 line adds `
 (HIP events around the exchanges the projections do not cover: the waits before attention and the inverse exchange)
 and the roofline of the local head shard.
 
-Rank 0 prints ONE JSON line; it also carries
+Rank 0 prints ONE JSON line.  A plain run does only what its headline needs: set up, warm up, time the K steps, write the
+outputs if `--dump-outputs DIR` is given, print the line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step` =
+wall milliseconds of one timed step).  Everything else is measured only with `--full` (the `--no-*` options below switch
+single parts of it off again); under `--full` the line also carries
   roofline      -- the dominant kernel (self-attention flash kernel): algorithmic FLOP per launch
                    / mean launch duration measured with HIP events on the launch stream inside
                    the timed region, vs the bf16 dense MFMA peak (2.5 PFLOP/s);
@@ -33,7 +36,11 @@ Rank 0 prints ONE JSON line; it also carries
                    before and after the timed region, and the chip's clock / power / temperature sampled
                    during it; `value_normalised` = value x (reference probe rate / this box's): the figure to
                    compare across boxes and rounds (the chips are power-limited here and differ by ~4 %);
-  rank_wall_s   -- (N > 1) every rank's own wall clock of the timed region and max / min.
+  e2e           -- one whole edit end to end (umT5 + WanVAE encode + WanPipeline + WanVAE decode), timed on its own;
+  rank_wall_s   -- (N > 1) every rank's own wall clock of the timed region and max / min (in every run: the line's time is the max).
+`--dump-outputs DIR` writes what the timed path computed in its LAST timed step -- the denoised latents the loop returns (rank 0) --
+as DIR/latents.npy in float32; an output above 64 MB is written as a fixed seeded sample of 16 M elements (DIR/latents_sample.npy,
+see dump_outputs).  The inputs (weights, latents, prompts) are seeded: the same arguments give the same inputs in every run.
 `--force-sp` runs the whole sequence-parallel line over a 1-rank RCCL group (code path, not scaling).
 `--cfg S` runs every step with classifier-free guidance as WanPipeline does (one forward over [uncond, cond], B = 2; BASELINE configs[3]).
 `--emulate-sp P` (one GPU) runs what ONE rank of a P-way Ulysses group computes -- the shard shapes of every kernel, device-local
@@ -510,10 +517,35 @@ def e2e_edit(model, wl, dev):
             "data": "synthetic clip, random-init weights; toy whitespace tokenizer"}
 
 
+DUMP_MAX_ELEMENTS = 16 * 1024 * 1024        # 64 MB of float32 in all
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_outputs(out_dir, arrays):
+    """Write {name: tensor} as out_dir/<name>.npy in float32.  If the whole set would exceed DUMP_MAX_ELEMENTS, each array is
+    replaced by a fixed sample of its flattened elements (ascending indices drawn without replacement by a generator seeded with
+    DUMP_SAMPLE_SEED, in proportion to its size) written as out_dir/<name>_sample.npy: the same elements in every run of the same shape.
+    Returns {file name: shape}."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(int(a.numel()) for a in arrays.values())
+    written = {}
+    for name, a in arrays.items():
+        flat = a.detach().float().cpu()
+        if total > DUMP_MAX_ELEMENTS:
+            n = int(flat.numel()) * DUMP_MAX_ELEMENTS // total
+            g = torch.Generator().manual_seed(DUMP_SAMPLE_SEED)
+            idx = torch.randperm(flat.numel(), generator=g)[:n].sort().values
+            flat, name = flat.reshape(-1)[idx], name + "_sample"
+        arr = flat.numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+        written[name + ".npy"] = list(arr.shape)
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=4)
+    ap.add_argument("--steps", type=int, default=4, help="timed denoise steps (>= 1); ms_per_step = wall of the timed region / steps")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="14b-cof", choices=sorted(WORKLOADS))
     ap.add_argument("--mode", default="sp", choices=["sp", "dp"], help="N>1: Ulysses sequence parallel or replicas")
@@ -565,7 +597,16 @@ def main():
     ap.add_argument("--graph-loop", action="store_true",
                     help="replay the WHOLE K-step loop (forwards, CoF mask, UniPC updates) from ONE hipGraph "
                          "(videocof_amd.GraphedLoop = WanPipeline(capture_graph='loop')).  For launch-bound small shapes.")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed (rank 0's denoised latents) to DIR/latents.npy "
+                         "(float32; a fixed seeded sample when above 64 MB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what the headline does not need: kernel events + roofline, exposed communication, "
+                         "box probe + telemetry (value_normalised*), the parity check of the last block, the end-to-end edit and the "
+                         "CPU baseline.  A plain run (the default) sets up, warms up, times the steps, dumps, and prints the line.")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps K: K >= 1 timed steps")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -668,7 +709,7 @@ def main():
     gfi = [(Fs, Fs + G)] * nb if cof else None
     sched = FlowUniPCMultistepScheduler(num_train_timesteps=1000, shift=1, solver_order=2)
 
-    prof = [] if not args.no_kernel_events else None
+    prof = [] if (args.full and not args.no_kernel_events) else None
     model._attn_events = prof
     comm = [] if (sp and prof is not None) else None
     model._comm_events = comm
@@ -735,7 +776,7 @@ def main():
     if model._ws_self.buf is not None:
         model._ws_self.buf[8:12].zero_()          # scratch header word [2]: repair events of the lazy softmax reference
     box = None
-    if not args.no_box_probe:
+    if args.full and not args.no_box_probe:
         from videocof_amd import ops as vops
         box = {"before": vops.box_probe(dev, target_ms=900)}     # (0.6 s measured after 0.3 s of the same) the warm-up steps above have brought the chip to temperature
     sampler = BoxSampler(local_rank).start() if box is not None else None
@@ -755,6 +796,9 @@ def main():
         rank_walls = [float(v.item()) for v in tws]
         wall = max(rank_walls)
     assert torch.isfinite(out.float()).all(), "non-finite latents"
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, {"latents": out})
 
     # ---------------- parity of this run's own forward (untimed): probe the last block, compare with the oracle.
     # Under sequence parallelism EVERY rank runs the probed forward (it contains collectives); each rank's probe is its token shard
@@ -764,7 +808,7 @@ def main():
     parity = None
     if emu:
         parity = {"skipped": "--emulate-sp: the arrived operands are this rank's own slabs, the output is not a denoised latent"}
-    elif not args.no_verify and (rank == 0 or sp) and not args.graph_loop:
+    elif args.full and not args.no_verify and (rank == 0 or sp) and not args.graph_loop:
         model._attn_events = None
         model._comm_events = None
         model.mask_source_frames = 0
@@ -879,6 +923,8 @@ def main():
         "graph": "loop" if args.graph_loop else bool(args.graph),
         "attn_stress": bool(args.attn_stress),
         "fp8_attn_smooth_k": (not args.fp8_no_smooth_k) if (args.fp8 and "attn" in args.fp8_layers.split(",")) else None,
+        "full": bool(args.full),
+        "dumped_outputs": dumped,
     }
     if emu:
         res["metric"] = "PROJECTION (one rank of a %d-way Ulysses group emulated on one GPU): " % emu + res["metric"]
@@ -891,7 +937,7 @@ def main():
                     "the RCCL exchanges would be.  `value` = L * steps / wall: the whole-job rate a %d-GPU run reaches if every rank takes "
                     "this long, i.e. its compute-side bound; exposed xGMI time comes on top.  No byte crossed a link; the output is not a "
                     "latent (parity skipped)." % (emu, emu, emu, emu)}
-    if rank == 0 and world == 1 and not force_sp and not emu and not cfg_scale and not args.no_e2e and args.workload in ("14b-cof", "14b-cof-33f") and not (args.fp8 or args.attn_stress or args.graph or args.graph_loop):
+    if args.full and rank == 0 and world == 1 and not force_sp and not emu and not cfg_scale and not args.no_e2e and args.workload in ("14b-cof", "14b-cof-33f") and not (args.fp8 or args.attn_stress or args.graph or args.graph_loop):
         try:        # the metric's second half (sec / video of a whole edit); separate from the timed region above, never takes it down
             res["e2e"] = e2e_edit(model, wl, dev)
         except Exception as e:
@@ -899,7 +945,7 @@ def main():
     if rank == 0 and isinstance(res.get("e2e"), dict) and "error" not in res["e2e"]:
         res["e2e"]["ingest"] = committed_ingest()
     if rank == 0:
-        if world == 1 and not emu and not args.no_cpu_baseline:
+        if args.full and world == 1 and not emu and not args.no_cpu_baseline:
             try:
                 res["cpu_baseline"] = cpu_baseline(wl, L)
                 res["gpu_over_cpu"] = round(value / res["cpu_baseline"]["value"], 1)

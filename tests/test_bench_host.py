@@ -202,3 +202,33 @@ def test_split_normalisation_tightens_the_committed_lines():
     roof, box = {"avg_ms": 60.0}, {"before": {"mfma_mix_tflops": 1500.0}, "after": {"mfma_mix_tflops": 1500.0}}
     assert bench.normalised_split(67080 * 4, 15.2, 4, 40, roof, box) == round(67080 * 4 / 15.2, 1)
     assert bench.normalised_split(1, 1.0, 4, 40, None, box) is None and bench.normalised_split(1, 1.0, 4, 40, roof, None) is None
+
+
+def test_dump_outputs_writes_float32_and_samples_above_the_cap(tmp_path, monkeypatch):
+    """`--dump-outputs DIR`: each output as DIR/<name>.npy in float32; above the cap, a fixed seeded sample of the flattened
+    elements (the same elements in every run) that keeps the whole dump under it."""
+    import numpy as np
+    import torch
+    x = torch.randn(2, 3, 4, 5, generator=torch.Generator().manual_seed(1)).bfloat16()
+    assert bench.dump_outputs(str(tmp_path / "a"), {"latents": x}) == {"latents.npy": [2, 3, 4, 5]}
+    got = np.load(tmp_path / "a" / "latents.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, x.float().numpy())
+    assert bench.DUMP_MAX_ELEMENTS * 4 <= 64 * 1024 * 1024
+    monkeypatch.setattr(bench, "DUMP_MAX_ELEMENTS", 30)
+    y = torch.arange(120, dtype=torch.float64).view(2, 60)
+    assert bench.dump_outputs(str(tmp_path / "b"), {"latents": y}) == {"latents_sample.npy": [30]}
+    assert bench.dump_outputs(str(tmp_path / "c"), {"latents": y}) == {"latents_sample.npy": [30]}
+    s1, s2 = np.load(tmp_path / "b" / "latents_sample.npy"), np.load(tmp_path / "c" / "latents_sample.npy")
+    assert s1.dtype == np.float32 and np.array_equal(s1, s2)
+    assert len(set(s1.tolist())) == 30 and np.all(np.diff(s1) > 0)          # distinct elements, in index order (value = index here)
+
+
+def test_plain_and_full_arguments():
+    """A plain run measures the headline only; --full is off by default and --steps sets the timed steps."""
+    import inspect
+    src = inspect.getsource(bench.main)
+    assert '"--full", action="store_true"' in src and '"--dump-outputs"' in src
+    for gate in ("prof = [] if (args.full and", "if args.full and not args.no_box_probe", "elif args.full and not args.no_verify",
+                 "if args.full and rank == 0 and world == 1", "if args.full and world == 1 and not emu and not args.no_cpu_baseline"):
+        assert gate in src, gate
+    assert '"ms_per_step": round(wall / args.steps * 1e3, 2)' in src and "out = run(args.steps)" in src

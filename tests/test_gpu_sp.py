@@ -598,7 +598,7 @@ def test_bench_line_under_sequence_parallelism_is_self_validating():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("RANK", None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--share-gpu",
-                        "--workload", "1.3b-small", "--layers", "3", "--steps", "1", "--warmup", "1"],
+                        "--workload", "1.3b-small", "--layers", "3", "--steps", "1", "--warmup", "1", "--full"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -628,7 +628,7 @@ def test_bench_sequence_parallel_line_over_rccl_with_one_rank():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--force-sp", "--workload", "1.3b-small", "--layers", "3",
-                        "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, timeout=900, env=env, cwd=root)
+                        "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 1 and line["ranks_seen"] == 1 and "RCCL" in line["backend"] and "force_ulysses" in line["backend"]
@@ -650,7 +650,7 @@ def test_bench_cfg_and_emulated_rank_lines():
 
     def line(*args):
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "1.3b-small", "--layers", "3", "--steps", "2", "--warmup", "1",
-                            "--no-cpu-baseline", *args], capture_output=True, text=True, timeout=900, env=env, cwd=root)
+                            "--no-cpu-baseline", "--full", *args], capture_output=True, text=True, timeout=900, env=env, cwd=root)
         assert r.returncode == 0, r.stderr[-2000:]
         return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     one, two = line(), line("--cfg", "5.0")
@@ -661,6 +661,33 @@ def test_bench_cfg_and_emulated_rank_lines():
     assert emu["metric"].startswith("PROJECTION") and emu["projection"]["of_n_gpus"] == 4 and "skipped" in emu["parity"]
     assert emu["config"]["parallelism"].startswith("EMULATED rank 0 of ulysses-sp4") and emu["roofline"]["heads_local"] == 3 and emu["n_gpus"] == 1
     assert emu["tokens_per_s_per_gpu"] == round(emu["value"] / 4, 1) and emu["cpu_baseline"] is None
+
+
+def test_bench_plain_line_times_the_steps_and_dumps_the_last_output(tmp_path):
+    """A plain `bench.py` run (no --full): the headline fields, nothing of what --full measures, and --dump-outputs writes the latents
+    its last timed step returned -- the same values in a second run with the same arguments (seeded inputs)."""
+    import json
+    import subprocess
+    import sys
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+
+    def line(steps, d):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--workload", "1.3b-small", "--layers", "3", "--steps", str(steps),
+                            "--warmup", "1", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=900, env=env, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    a, b, c = line(2, tmp_path / "a"), line(2, tmp_path / "b"), line(3, tmp_path / "c")
+    for x, steps in ((a, 2), (b, 2), (c, 3)):
+        assert x["steps"] == steps and x["ms_per_step"] > 0 and x["unit"] == "tokens/s" and x["higher_is_better"] is True
+        assert x["dtype"] == "bf16" and x["full"] is False and x["dumped_outputs"] == {"latents.npy": [1, 16, 9, 32, 32]}
+        assert abs(x["value"] - 2304 * steps / (x["ms_per_step"] * steps * 1e-3)) / x["value"] < 1e-2
+        assert x["parity"] is None and x["roofline"] is None and x["box"] is None and x["cpu_baseline"] is None and "e2e" not in x
+    la, lb, lc = (np.load(tmp_path / d / "latents.npy") for d in "abc")
+    assert la.dtype == np.float32 and la.shape == (1, 16, 9, 32, 32) and np.isfinite(la).all()
+    assert float(np.linalg.norm(la - lb) / np.linalg.norm(la)) < 1e-2          # same inputs, same outputs (to bf16 rounding)
+    assert float(np.linalg.norm(la - lc) / np.linalg.norm(la)) > 1e-2          # a third step is another latent
 
 
 def test_emulated_rank_runs_the_shard_shapes_and_degree_one_is_the_single_device():

@@ -5,7 +5,7 @@ set -u
 stage=${1:?stage}
 out=gpurun_out/r06_${stage}${3:-}
 mkdir -p "$out"
-B="python bench.py"
+B="python bench.py --full"
 json() { grep '^{' | tail -1; }
 case $stage in
   a)  # the new bench plumbing: box probe, SP parity over gloo on a shared GPU (N = 2, 4), the 33-frame demo configuration, 720p CoF
