@@ -502,6 +502,19 @@ wan_status_t wan_dit_forward(const void* latent, int latent_dtype, void* out, in
 wan_status_t wan_lincomb(void* out, int dtype, const void* x0, const void* x1, const void* x2, const void* x3,
                          float c0, float c1, float c2, float c3, int64_t n, void* stream);
 
+/* a17b  The flow DPM-Solver++ step as one fused pass, two outputs:
+ *          x0_out[i]   = a_s*sample[i] + a_v*v[i]                          (stored in `dtype`: the scheduler's history entry)
+ *          prev_out[i] = c_s*sample[i] + c_0*x0r[i] + c_1*m1[i] + c_2*m2[i] + c_n*noise[i]    (x0r = x0 as stored)
+ *      sample, v, m1, m2 and both outputs are all fp32 (dtype 0) or all bf16 (dtype 1); `noise` is always fp32; m1, m2 and
+ *      noise may be NULL (m2 only with m1).  fp32 accumulate; the x0 bits equal wan_lincomb's on the same two terms.
+ *      replaces: convert_model_output's x0 prediction (fm_solvers.py:381-383) and the elementwise chains of
+ *      dpm_solver_first_order_update / multistep_dpm_solver_second_order_update / multistep_dpm_solver_third_order_update
+ *      (fm_solvers.py:465-482, 549-592, 666-676) incl. the sde-dpmsolver++ noise term; the scalar algebra stays on the host
+ *      (float64, videocof_amd/fm_solvers.py). */
+wan_status_t wan_solver_step(void* x0_out, void* prev_out, int dtype, const void* sample, const void* v, const void* m1,
+                             const void* m2, const float* noise, float a_s, float a_v, float c_s, float c_0, float c_1,
+                             float c_2, float c_n, int64_t n, void* stream);
+
 /* ===========================================================================
  * WanVAE (videox_fun/models/wan_vae.py).  Activations are CHANNELS-LAST bf16 [T, H, W, C].
  * ------------------------------------------------------------------------- */

@@ -5,6 +5,7 @@ Host side mirrors the reference's interface for this path only:
     videocof_amd.WanTransformer3DModel      <- videox_fun/models/wan_transformer3d.py
     videocof_amd.attention                  <- videox_fun/models/attention_utils.py
     videocof_amd.FlowUniPCMultistepScheduler<- videox_fun/utils/fm_solvers_unipc.py
+    videocof_amd.FlowDPMSolverMultistepScheduler <- videox_fun/utils/fm_solvers.py (+ get_sampling_sigmas, retrieve_timesteps)
     videocof_amd.WanPipeline                <- videox_fun/pipeline/pipeline_wan.py
     videocof_amd.AutoencoderKLWan           <- videox_fun/models/wan_vae.py
     videocof_amd.WanT5EncoderModel          <- videox_fun/models/wan_text_encoder.py (umT5 encoder)
@@ -15,6 +16,7 @@ Host side mirrors the reference's interface for this path only:
 Device arithmetic lives in ``libwan_hip.so`` (csrc/, C ABI in include/wan_hip.h).
 """
 from .fm_solvers_unipc import FlowUniPCMultistepScheduler  # noqa: F401
+from .fm_solvers import FlowDPMSolverMultistepScheduler, get_sampling_sigmas, retrieve_timesteps  # noqa: F401
 from .pipeline_wan import WanPipeline, WanPipelineOutput  # noqa: F401
 from .wan_transformer3d import WanTransformer3DModel  # noqa: F401
 from .graph import GraphedForward, GraphedLoop  # noqa: F401

@@ -882,6 +882,42 @@ def lincomb(terms, out_dtype: torch.dtype) -> torch.Tensor:
     return out
 
 
+solver_step_launches = 0          # wan_solver_step launches so far (read by the tests that count launches per scheduler step)
+
+
+@_on_tensor_device
+def solver_step(sample: torch.Tensor, v: torch.Tensor, a_s: float, a_v: float, m1: Optional[torch.Tensor],
+                m2: Optional[torch.Tensor], noise: Optional[torch.Tensor], c_s: float, c_0: float, c_1: float, c_2: float,
+                c_n: float) -> Tuple[torch.Tensor, torch.Tensor]:
+    """One flow DPM-Solver++ step in one pass (``wan_solver_step``): returns ``(x0, prev)`` with
+    x0 = a_s*sample + a_v*v in the latents' dtype and prev = c_s*sample + c_0*x0 + c_1*m1 + c_2*m2 + c_n*noise (x0 as stored,
+    fp32 accumulate, written in the latents' dtype).  sample, v, m1, m2: same shape, all fp32 or all bf16; noise fp32 or None;
+    m1 / m2 may be None."""
+    global solver_step_launches
+    dt = sample.dtype
+    if dt not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"solver_step: dtype {dt} not supported (fp32 or bf16)")
+    xs = []
+    for name, t, want in (("sample", sample, dt), ("v", v, dt), ("m1", m1, dt), ("m2", m2, dt), ("noise", noise, torch.float32)):
+        if t is None:
+            xs.append(None)
+            continue
+        _need(t, want, "solver_step." + name)
+        if t.shape != sample.shape:
+            raise ValueError(f"solver_step.{name}: shape {tuple(t.shape)} != sample {tuple(sample.shape)}")
+        xs.append(t.contiguous())
+    x0 = torch.empty(sample.shape, device=sample.device, dtype=dt)
+    prev = torch.empty_like(x0)
+    if x0.numel() == 0:
+        return x0, prev                          # (an empty tensor has no storage to point at: nothing to launch)
+    lib = _lib.load()
+    _lib.check(lib.wan_solver_step(_p(x0), _p(prev), 0 if dt == torch.float32 else 1, *[_p(t) for t in xs],
+                                   float(a_s), float(a_v), float(c_s), float(c_0), float(c_1), float(c_2), float(c_n),
+                                   x0.numel(), _stream()), "wan_solver_step")
+    solver_step_launches += 1
+    return x0, prev
+
+
 # ------------------------------------------------------------------ umT5 text encoder rows (SURVEY.md 8f-3)
 def _avail(t: torch.Tensor) -> int:
     """Elements from t's first element to the end of its storage."""

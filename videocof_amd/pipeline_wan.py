@@ -29,6 +29,7 @@ from typing import Callable, Optional, Union
 import numpy as np
 import torch
 
+from .fm_solvers import FlowDPMSolverMultistepScheduler, get_sampling_sigmas, retrieve_timesteps
 from .fm_solvers_unipc import FlowUniPCMultistepScheduler
 
 __all__ = ["WanPipeline", "WanPipelineOutput"]
@@ -283,8 +284,8 @@ class WanPipeline:
                  source_latents: Optional[torch.Tensor] = None, device=None,
                  weight_dtype: torch.dtype = torch.bfloat16, cache_context: bool = True,
                  skip_source_prediction: bool = True, capture_graph=False):
-        # `timesteps`: with a FlowUniPCMultistepScheduler the reference never looks at it (pipeline_wan.py:613-615 calls
-        # set_timesteps(num_inference_steps, device=, shift=) and takes scheduler.timesteps); accepted and ignored here too.
+        # `timesteps`: with either scheduler built here the reference never looks at it (pipeline_wan.py:613-621: UniPC takes
+        # set_timesteps(num_inference_steps, device=, shift=), DPM++ the sigmas of get_sampling_sigmas); accepted and ignored here too.
         del timesteps
         num_videos_per_prompt = 1                  # :561 -- the reference overrides the argument at the top of __call__, whatever was passed
         self.check_inputs(prompt, height, width, negative_prompt, callback_on_step_end_tensor_inputs, prompt_embeds, negative_prompt_embeds)
@@ -300,10 +301,16 @@ class WanPipeline:
         self._stage("text_encoder", t_stage)
         in_prompt_embeds = (negative_prompt_embeds + prompt_embeds) if do_cfg else prompt_embeds   # :605-608
 
-        if not isinstance(self.scheduler, FlowUniPCMultistepScheduler):
-            raise NotImplementedError("only FlowUniPCMultistepScheduler is built (fast_infer.py:152)")
-        self.scheduler.set_timesteps(num_inference_steps, device=device, shift=shift)           # :613-615
-        timesteps = self.scheduler.timesteps
+        if isinstance(self.scheduler, FlowUniPCMultistepScheduler):
+            self.scheduler.set_timesteps(num_inference_steps, device=device, shift=shift)       # :613-615
+            timesteps = self.scheduler.timesteps
+        elif isinstance(self.scheduler, FlowDPMSolverMultistepScheduler):
+            timesteps, _ = retrieve_timesteps(self.scheduler, device=device,
+                                              sigmas=get_sampling_sigmas(num_inference_steps, shift))   # :616-621
+        else:
+            raise NotImplementedError(f"{type(self.scheduler).__name__}: the schedulers built are FlowUniPCMultistepScheduler and "
+                                      "FlowDPMSolverMultistepScheduler (fast_infer.py:328-337)")
+        extra_step_kwargs = self.prepare_extra_step_kwargs(generator, eta)                       # :682
         self._num_timesteps = len(timesteps)
 
         ratio = getattr(self.vae, "temporal_compression_ratio", 4)
@@ -380,7 +387,7 @@ class WanPipeline:
                 if prev_mask is None:
                     noise_pred[:, :, :condition_count] = 0                                      # :736
                 # else: already zero -- written by wan_unpatchify(zero_frames); CFG keeps it (0 + s * (0 - 0))
-                latents = self.scheduler.step(noise_pred, t, latents, return_dict=False)[0]     # :740
+                latents = self.scheduler.step(noise_pred, t, latents, **extra_step_kwargs, return_dict=False)[0]   # :740
                 if callback_on_step_end is not None:
                     # :742-750 -- the tensors named in callback_on_step_end_tensor_inputs; only `latents` coming back has an effect
                     # (there as here: the embeddings of the loop were concatenated before it started, :605-608)
@@ -398,13 +405,18 @@ class WanPipeline:
                     raise NotImplementedError("capture_graph='loop' replays all steps in one launch: no per-step callback")
                 if not getattr(self.transformer, "cache_context", False):
                     raise NotImplementedError("capture_graph='loop' needs cache_context (the text K/V are part of the graph)")
+                if self.scheduler.config.get("algorithm_type") == "sde-dpmsolver++":
+                    raise NotImplementedError("capture_graph='loop' with sde-dpmsolver++: the host generator's noise draws cannot be "
+                                              "recorded into a graph (use capture_graph='step')")
                 if self._graphed_loop is None or self._graphed_loop.model is not self.transformer:
                     from .graph import GraphedLoop
                     self._graphed_loop = GraphedLoop(self.transformer)
                 self.scheduler.set_begin_index(0)       # no device round trip (index_for_timestep) inside a capture
                 key = (int(num_inference_steps), float(shift), bool(do_cfg), float(guidance_scale) if do_cfg else 0.0,
                        int(condition_count), int(ground_latent_count), bool(cot), bool(use_rope_map), int(seq_len),
-                       int(self.scheduler.config.solver_order), bool(self.scheduler.config.lower_order_final))
+                       int(self.scheduler.config.solver_order), bool(self.scheduler.config.lower_order_final),
+                       type(self.scheduler).__name__, self.scheduler.config.get("algorithm_type"), self.scheduler.config.get("solver_type"),
+                       bool(self.scheduler.config.get("euler_at_final", False)))
 
                 def loop_fn(lat, embeds):
                     self.scheduler._reset()
