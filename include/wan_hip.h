@@ -337,6 +337,15 @@ wan_status_t wan_patchify(const void* latent, int in_dtype, void* tokens_bf16, i
                           int Cin, int F, int H, int W, int pt, int ph, int pw, void* stream);
 wan_status_t wan_unpatchify(const float* tokens, int64_t ldt, void* out, int out_dtype,
                             int Cout, int F, int Hp, int Wp, int pt, int ph, int pw, int zero_frames, void* stream);
+/* a14' unpatchify with `rep` copies of the result written by the same pass: copy k goes to out + k * rep_stride elements
+ *     (rep_stride >= Cout*F*pt*Hp*ph*Wp*pw; for a batch of B samples the caller passes B * that, so the result reads
+ *     [rep][B][Cout][...]).  16-byte stores when the rows and both strides allow it, element-wise otherwise; zero_frames applies
+ *     to every copy.  rep = 1 writes what wan_unpatchify writes.
+ *     replaces: `result = torch.cat([result, result], dim=0)` of the cfg_skip decorator
+ *     (videox_fun/utils/cfg_optimization.py:34-36) -- no second read of the output, no concatenation launch. */
+wan_status_t wan_unpatchify_rep(const float* tokens, int64_t ldt, void* out, int out_dtype,
+                                int Cout, int F, int Hp, int Wp, int pt, int ph, int pw, int zero_frames,
+                                int rep, int64_t rep_stride, void* stream);
 
 /* ---------------------------------------------------------------------------
  * a21  Ulysses sequence parallelism: the wire layouts of the head all-to-all (replaces usp_attn_forward's packing,
@@ -493,6 +502,14 @@ wan_status_t wan_dit_forward(const void* latent, int latent_dtype, void* out, in
                              const wan_dit_weights* w, const wan_dit_workspace* ws, const float* rope_cos,
                              const float* rope_sin, const wan_rope_params* rp, int batch, int F, int H, int W,
                              int64_t rows_per_batch, int zero_frames, void* stream);
+/* The same call with the result written `rep` times along the batch axis (out = [rep][batch][out_dim][F][H][W]) by
+ * wan_unpatchify_rep: a cfg_skip step (cfg_optimization.py:5-38) computes the conditional half and returns it twice.
+ * rep = 1 enqueues exactly what wan_dit_forward enqueues. */
+wan_status_t wan_dit_forward_rep(const void* latent, int latent_dtype, void* out, int out_dtype, const float* emod,
+                                 const float* ehead, const void* const* ctx_k, const void* const* ctx_vt,
+                                 const wan_dit_weights* w, const wan_dit_workspace* ws, const float* rope_cos,
+                                 const float* rope_sin, const wan_rope_params* rp, int batch, int F, int H, int W,
+                                 int64_t rows_per_batch, int zero_frames, int rep, void* stream);
 
 /* a17  UniPC updates as one fused pass: out[i] = c0*x0[i] + c1*x1[i] + c2*x2[i] + c3*x3[i] (x1..x3 may be
  *      NULL), fp32 accumulate, all tensors of one dtype (0 fp32, 1 bf16).

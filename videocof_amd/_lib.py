@@ -119,6 +119,9 @@ SIGNATURES = {
     "wan_dit_forward": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, POINTER(c_void_p), POINTER(c_void_p),
                                 POINTER(DitWeights), POINTER(DitWorkspace), c_void_p, c_void_p, POINTER(RopeParams),
                                 c_int, c_int, c_int, c_int, c_int64, c_int, c_void_p]),
+    "wan_dit_forward_rep": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, POINTER(c_void_p), POINTER(c_void_p),
+                                    POINTER(DitWeights), POINTER(DitWorkspace), c_void_p, c_void_p, POINTER(RopeParams),
+                                    c_int, c_int, c_int, c_int, c_int64, c_int, c_int, c_void_p]),
     "wan_dit_block_workspace_bytes": (c_int, [c_int, c_int, c_int, c_int64, c_int64, POINTER(c_int64), POINTER(c_int64)]),
     "wan_gemm_fp8": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64,
                              c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p]),
@@ -178,6 +181,8 @@ SIGNATURES = {
                              c_int, c_int, c_int, c_void_p]),
     "wan_unpatchify": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                c_int, c_int, c_int, c_int, c_void_p]),
+    "wan_unpatchify_rep": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                   c_int, c_int, c_int, c_int, c_int, c_int64, c_void_p]),
     "wan_lincomb": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float,
                             c_int64, c_void_p]),
     "wan_solver_step": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,

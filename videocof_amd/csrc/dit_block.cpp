@@ -116,11 +116,13 @@ extern "C" wan_status_t wan_dit_block_workspace_bytes(int dim, int ffn_dim, int 
 // fp32 residual stream -> num_layers x wan_dit_block_forward -> head LN-modulate -> head GEMM -> unpatchify (with the CoF
 // mask).  The two embedding MLPs that feed it (time: :891-901, text: :915-919 -- a few GFLOP per call, fp32 / bf16 GEMMs of
 // this library or the host's) stay with the host: their results arrive as `emod`, `ehead`, `ctx_k`, `ctx_vt`.
-extern "C" wan_status_t wan_dit_forward(const void* latent, int latent_dtype, void* out, int out_dtype, const float* emod,
-                                        const float* ehead, const void* const* ctx_k, const void* const* ctx_vt,
-                                        const wan_dit_weights* w, const wan_dit_workspace* ws, const float* rope_cos,
-                                        const float* rope_sin, const wan_rope_params* rp, int batch, int F, int H, int W,
-                                        int64_t rows_per_batch, int zero_frames, void* stream) {
+// `rep` > 1 (wan_dit_forward_rep): the result is written `rep` times along the batch axis by the unpatchify store itself
+// (out = [rep][batch][out_dim][F][H][W]) -- the doubled result of a cfg_skip step (videox_fun/utils/cfg_optimization.py:34-36).
+static wan_status_t dit_forward(const void* latent, int latent_dtype, void* out, int out_dtype, const float* emod,
+                                const float* ehead, const void* const* ctx_k, const void* const* ctx_vt,
+                                const wan_dit_weights* w, const wan_dit_workspace* ws, const float* rope_cos,
+                                const float* rope_sin, const wan_rope_params* rp, int batch, int F, int H, int W,
+                                int64_t rows_per_batch, int zero_frames, int rep, void* stream) {
     WAN_REQUIRE(latent && out && emod && ehead && ctx_k && ctx_vt && w && ws && rp, WAN_ERR_INVALID, "wan_dit_forward: null argument");
     WAN_REQUIRE(w->num_layers > 0 && w->blocks && w->pe_w && w->pe_b && w->head_w && w->head_b, WAN_ERR_INVALID,
                 "wan_dit_forward: incomplete weights");
@@ -161,8 +163,33 @@ extern "C" wan_status_t wan_dit_forward(const void* latent, int latent_dtype, vo
     const int64_t bC = (int64_t)batch * C;                    // ehead = [shift][scale], each [batch][C] (Head.forward :545-547)
     WAN_TRY(wan_ln_modulate(ws->x, ehead + bC, ehead, 1, ws->block.h, M, C, Ll, w->blocks[0].eps, stream));
     WAN_TRY(wan_gemm_bf16_ws(ws->block.h, C, w->head_w, C, w->head_b, ws->head_out, Nh, (int)M, Nh, C, WAN_EPI_F32, nullptr, 0, GWS, GWSB, stream));
-    for (int b = 0; b < batch; ++b)
-        WAN_TRY(wan_unpatchify(ws->head_out + (int64_t)b * Ll * Nh, Nh, at(out, (int64_t)b * w->out_dim * F * H * W * out_el), out_dtype,
-                               w->out_dim, gf, gh, gw, pt, ph, pw, zero_frames, stream));
+    WAN_REQUIRE(rep >= 1, WAN_ERR_INVALID, "wan_dit_forward: rep=%d", rep);
+    const int64_t sample = (int64_t)w->out_dim * F * H * W;
+    for (int b = 0; b < batch; ++b) {
+        if (rep == 1)
+            WAN_TRY(wan_unpatchify(ws->head_out + (int64_t)b * Ll * Nh, Nh, at(out, b * sample * out_el), out_dtype,
+                                   w->out_dim, gf, gh, gw, pt, ph, pw, zero_frames, stream));
+        else
+            WAN_TRY(wan_unpatchify_rep(ws->head_out + (int64_t)b * Ll * Nh, Nh, at(out, b * sample * out_el), out_dtype,
+                                       w->out_dim, gf, gh, gw, pt, ph, pw, zero_frames, rep, batch * sample, stream));
+    }
     return WAN_OK;
+}
+
+extern "C" wan_status_t wan_dit_forward(const void* latent, int latent_dtype, void* out, int out_dtype, const float* emod,
+                                        const float* ehead, const void* const* ctx_k, const void* const* ctx_vt,
+                                        const wan_dit_weights* w, const wan_dit_workspace* ws, const float* rope_cos,
+                                        const float* rope_sin, const wan_rope_params* rp, int batch, int F, int H, int W,
+                                        int64_t rows_per_batch, int zero_frames, void* stream) {
+    return dit_forward(latent, latent_dtype, out, out_dtype, emod, ehead, ctx_k, ctx_vt, w, ws, rope_cos, rope_sin, rp, batch, F, H, W,
+                       rows_per_batch, zero_frames, 1, stream);
+}
+
+extern "C" wan_status_t wan_dit_forward_rep(const void* latent, int latent_dtype, void* out, int out_dtype, const float* emod,
+                                            const float* ehead, const void* const* ctx_k, const void* const* ctx_vt,
+                                            const wan_dit_weights* w, const wan_dit_workspace* ws, const float* rope_cos,
+                                            const float* rope_sin, const wan_rope_params* rp, int batch, int F, int H, int W,
+                                            int64_t rows_per_batch, int zero_frames, int rep, void* stream) {
+    return dit_forward(latent, latent_dtype, out, out_dtype, emod, ehead, ctx_k, ctx_vt, w, ws, rope_cos, rope_sin, rp, batch, F, H, W,
+                       rows_per_batch, zero_frames, rep, stream);
 }

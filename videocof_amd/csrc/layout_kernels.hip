@@ -50,6 +50,40 @@ __global__ __launch_bounds__(256) void unpatchify_kernel(const float* __restrict
     }
 }
 
+// The same permutation with `rep` copies of the result, `rep_stride` elements apart, written in the SAME pass: one thread gathers
+// VEC = 16 / sizeof(TOut) consecutive elements of an output row (along W) and stores the chunk once per copy (16-byte vector
+// stores).  VEC = 1 is the element-wise form for rows or base addresses that are not 16-byte multiples.
+template <typename TOut, int VEC>
+__global__ __launch_bounds__(256) void unpatchify_rep_kernel(const float* __restrict__ tok, int64_t ldt,
+                                                             TOut* __restrict__ out, int Cout, int Fp, int Hp, int Wp,
+                                                             int pt, int ph, int pw, int zero_frames, int rep, int64_t rep_stride) {
+    struct alignas(sizeof(TOut) * VEC) chunk_t { TOut v[VEC]; };
+    const int F = Fp * pt, H = Hp * ph, W = Wp * pw;
+    const int Wc = W / VEC;                                   // chunks per row (the host guarantees W % VEC == 0)
+    const int64_t total = (int64_t)Cout * F * H * Wc;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        int64_t r = i;
+        const int w0 = (int)(r % Wc) * VEC; r /= Wc;
+        const int h = (int)(r % H); r /= H;
+        const int f = (int)(r % F); r /= F;
+        const int c = (int)r;
+        const int fq = f / pt, a = f - fq * pt;
+        const int hq = h / ph, b = h - hq * ph;
+        chunk_t ch;
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) {
+            const int w = w0 + j;
+            const int wq = w / pw, d = w - wq * pw;
+            const int64_t t = ((int64_t)fq * Hp + hq) * Wp + wq;
+            const int col = ((a * ph + b) * pw + d) * Cout + c;
+            ch.v[j] = f < zero_frames ? (TOut)0.f : (TOut)tok[t * ldt + col];    // CoF mask on every copy, no token read
+        }
+        TOut* at = out + i * VEC;
+        for (int k = 0; k < rep; ++k)
+            *reinterpret_cast<chunk_t*>(at + (int64_t)k * rep_stride) = ch;
+    }
+}
+
 }  // namespace
 
 extern "C" wan_status_t wan_patchify(const void* latent, int in_dtype, void* tokens_bf16, int64_t ldt,
@@ -91,6 +125,43 @@ extern "C" wan_status_t wan_unpatchify(const float* tokens, int64_t ldt, void* o
         hipLaunchKernelGGL(unpatchify_kernel<bf16_t>, dim3(blocks), dim3(256), 0, s, tokens, ldt, (bf16_t*)out,
                            Cout, F, Hp, Wp, pt, ph, pw, zero_frames);
     WAN_CHECK_LAUNCH("wan_unpatchify");
+    return WAN_OK;
+}
+
+template <typename TOut, int VEC>
+static void launch_unpatchify_rep(const float* tokens, int64_t ldt, void* out, int Cout, int F, int Hp, int Wp, int pt, int ph, int pw,
+                                  int zero_frames, int rep, int64_t rep_stride, hipStream_t s) {
+    const int64_t total = (int64_t)Cout * F * pt * Hp * ph * (Wp * pw / VEC);
+    const unsigned blocks = (unsigned)((total + 255) / 256 > 4096 ? 4096 : (total + 255) / 256);
+    hipLaunchKernelGGL((unpatchify_rep_kernel<TOut, VEC>), dim3(blocks), dim3(256), 0, s, tokens, ldt, (TOut*)out, Cout, F, Hp, Wp,
+                       pt, ph, pw, zero_frames, rep, rep_stride);
+}
+
+extern "C" wan_status_t wan_unpatchify_rep(const float* tokens, int64_t ldt, void* out, int out_dtype,
+                                           int Cout, int F, int Hp, int Wp, int pt, int ph, int pw, int zero_frames,
+                                           int rep, int64_t rep_stride, void* stream) {
+    WAN_REQUIRE(tokens && out, WAN_ERR_INVALID, "wan_unpatchify_rep: null tensor");
+    WAN_REQUIRE(Cout > 0 && F > 0 && Hp > 0 && Wp > 0 && pt > 0 && ph > 0 && pw > 0, WAN_ERR_INVALID, "wan_unpatchify_rep: bad shape");
+    WAN_REQUIRE(ldt >= (int64_t)Cout * pt * ph * pw, WAN_ERR_INVALID, "wan_unpatchify_rep: ldt too small");
+    WAN_REQUIRE(out_dtype == 0 || out_dtype == 1, WAN_ERR_INVALID, "wan_unpatchify_rep: out_dtype=%d", out_dtype);
+    WAN_REQUIRE(zero_frames >= 0, WAN_ERR_INVALID, "wan_unpatchify_rep: zero_frames=%d", zero_frames);
+    const int64_t total = (int64_t)Cout * F * pt * Hp * ph * Wp * pw;
+    WAN_REQUIRE(rep >= 1 && (rep == 1 || rep_stride >= total), WAN_ERR_INVALID,
+                "wan_unpatchify_rep: rep=%d rep_stride=%lld (copies of %lld elements must not overlap)", rep, (long long)rep_stride,
+                (long long)total);
+    hipStream_t s = (hipStream_t)stream;
+    // 16-byte chunks when every row of every copy starts on a 16-byte boundary; element-wise stores otherwise
+    const int vec = out_dtype == 0 ? 4 : 8;
+    const int64_t el = out_dtype == 0 ? 4 : 2;
+    const bool wide = (Wp * pw) % vec == 0 && (uintptr_t)out % 16 == 0 && (rep == 1 || (rep_stride * el) % 16 == 0);
+    if (out_dtype == 0) {
+        if (wide) launch_unpatchify_rep<float, 4>(tokens, ldt, out, Cout, F, Hp, Wp, pt, ph, pw, zero_frames, rep, rep_stride, s);
+        else launch_unpatchify_rep<float, 1>(tokens, ldt, out, Cout, F, Hp, Wp, pt, ph, pw, zero_frames, rep, rep_stride, s);
+    } else {
+        if (wide) launch_unpatchify_rep<bf16_t, 8>(tokens, ldt, out, Cout, F, Hp, Wp, pt, ph, pw, zero_frames, rep, rep_stride, s);
+        else launch_unpatchify_rep<bf16_t, 1>(tokens, ldt, out, Cout, F, Hp, Wp, pt, ph, pw, zero_frames, rep, rep_stride, s);
+    }
+    WAN_CHECK_LAUNCH("wan_unpatchify_rep");
     return WAN_OK;
 }
 

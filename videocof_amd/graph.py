@@ -101,7 +101,9 @@ class GraphedForward:
         key = (tuple(x.shape), x.dtype, key_t, int(seq_len), tuple(frame_split_indices or ()),
                tuple(tuple(g) for g in (ground_frame_indices or ())), int(m.skip_source_frames),
                int(m.mask_source_frames), len(context), torch.cuda.current_device(), tuple(m._fp8),
-               bool(m.use_block_composite), bool(m.use_forward_composite), tuple(m.fp8_attn_exponents), bool(m.fp8_attn_smooth_k), bool(getattr(m, 'fp8_attn_calibrate', False)))
+               bool(m.use_block_composite), bool(m.use_forward_composite), tuple(m.fp8_attn_exponents), bool(m.fp8_attn_smooth_k), bool(getattr(m, 'fp8_attn_calibrate', False)),
+               # a call the model's cfg_skip rule halves enqueues other launches than a full one of the same shape
+               bool(m.cfg_skip_now(x.shape[0])))
         epoch = m._graph_epoch
         for k in [k for k, e in self._entries.items() if e.epoch != epoch]:
             stale = self._entries.pop(k)                 # weights / fp8 copies / workspaces were replaced since the capture
@@ -149,7 +151,7 @@ class GraphedForward:
 
 
 class _LoopEntry:
-    __slots__ = ("x", "ctx", "graph", "out", "calls", "epoch", "bufs", "attn_bufs", "keep")
+    __slots__ = ("x", "ctx", "graph", "out", "calls", "epoch", "bufs", "attn_bufs", "keep", "more_bufs")
 
 
 class GraphedLoop:
@@ -171,10 +173,14 @@ class GraphedLoop:
         self._entries: Dict[tuple, _LoopEntry] = {}
         self.replays = 0
 
+    @staticmethod
+    def _unpin(ent) -> None:
+        for b in ([ent.bufs] if ent.bufs is not None else []) + list(ent.more_bufs or ()):
+            b.pinned = False
+
     def reset(self) -> None:
         for ent in self._entries.values():
-            if ent.bufs is not None:
-                ent.bufs.pinned = False
+            self._unpin(ent)
         self._entries.clear()
 
     def __del__(self):
@@ -196,14 +202,12 @@ class GraphedLoop:
                      tuple(m.fp8_attn_exponents), bool(m.fp8_attn_smooth_k), bool(getattr(m, 'fp8_attn_calibrate', False)))
         epoch = m._graph_epoch
         for k in [k for k, e in self._entries.items() if e.epoch != epoch]:
-            stale = self._entries.pop(k)
-            if stale.bufs is not None:
-                stale.bufs.pinned = False
+            self._unpin(self._entries.pop(k))
         ent = self._entries.get(key)
         if ent is None:
             ent = self._entries[key] = _LoopEntry()
             ent.x, ent.ctx, ent.graph, ent.out, ent.calls, ent.epoch = None, None, None, None, 0, epoch
-            ent.bufs, ent.attn_bufs, ent.keep = None, None, None
+            ent.bufs, ent.attn_bufs, ent.keep, ent.more_bufs = None, None, None, None
         ent.calls += 1
         if ent.calls == 1:
             return loop_fn(latents, context)                 # eager: the result of this call, and the warm-up of the capture
@@ -222,14 +226,20 @@ class GraphedLoop:
             events, m._attn_events = m._attn_events, None
             torch.cuda.synchronize()
             graph = torch.cuda.CUDAGraph()
+            m._bufs_used = used = []
             try:
                 with torch.cuda.graph(graph):
                     ent.out = loop_fn(ent.x, ent.ctx)
             finally:
                 m._attn_events = events
+                m._bufs_used = None
             ent.graph = graph
             ent.bufs = m._bufs[m._bufs_last]
             ent.bufs.pinned = True
+            # a loop with cfg_skip steps runs at two batch sizes: every workspace set the capture touched is baked in
+            ent.more_bufs = [b for b in {id(b): b for b in used}.values() if b is not ent.bufs]
+            for b in ent.more_bufs:
+                b.pinned = True
             ent.attn_bufs = [ws.buf for ws in (m._ws_self, m._ws_cross, m._ws_self_sfx, m._ws_cross_sfx)]
         ent.graph.replay()
         self.replays += 1

@@ -746,9 +746,15 @@ def patchify(latent: torch.Tensor, patch: Tuple[int, int, int], out: Optional[to
 
 @_on_tensor_device
 def unpatchify(tokens: torch.Tensor, grid: Tuple[int, int, int], patch: Tuple[int, int, int], cout: int,
-               out_dtype: torch.dtype, zero_frames: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+               out_dtype: torch.dtype, zero_frames: int = 0, out: Optional[torch.Tensor] = None,
+               rep: Optional[int] = None, rep_stride: Optional[int] = None) -> torch.Tensor:
     """tokens fp32 [L, pt*ph*pw*Cout] -> [Cout, F*pt, Hp*ph, Wp*pw] in out_dtype (fp32|bf16); output frames
-    < zero_frames are written as zeros (the CoF mask of pipeline_wan.py:736)."""
+    < zero_frames are written as zeros (the CoF mask of pipeline_wan.py:736).
+    ``rep`` (``wan_unpatchify_rep``): the result is written ``rep`` times in the same pass, copy k at ``out`` + k * ``rep_stride``
+    elements -- ``out`` is then the first copy's [Cout, ...] view of a larger buffer the caller owns (``rep_stride`` defaults
+    to one result, i.e. a fresh [rep, Cout, ...] tensor is returned when ``out`` is None)."""
+    if rep is not None:
+        return _unpatchify_rep(tokens, grid, patch, cout, out_dtype, zero_frames, out, int(rep), rep_stride)
     _need(tokens, torch.float32, "unpatchify.tokens")
     if out_dtype not in (torch.float32, torch.bfloat16):
         raise ValueError(f"unpatchify: out dtype {out_dtype} not supported")
@@ -766,6 +772,38 @@ def unpatchify(tokens: torch.Tensor, grid: Tuple[int, int, int], patch: Tuple[in
     _lib.check(lib.wan_unpatchify(_p(tokens), tokens.stride(0), _p(out), 0 if out_dtype == torch.float32 else 1,
                                   cout, F, Hp, Wp, pt, ph, pw, int(zero_frames), _stream()), "wan_unpatchify")
     return out
+
+
+def _unpatchify_rep(tokens, grid, patch, cout, out_dtype, zero_frames, out, rep, rep_stride):
+    _need(tokens, torch.float32, "unpatchify.tokens")
+    if out_dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"unpatchify: out dtype {out_dtype} not supported")
+    F, Hp, Wp = grid
+    pt, ph, pw = patch
+    if tokens.shape[0] < F * Hp * Wp:
+        raise ValueError("unpatchify: fewer token rows than the grid")
+    shape = (cout, F * pt, Hp * ph, Wp * pw)
+    n = shape[0] * shape[1] * shape[2] * shape[3]
+    if rep < 1:
+        raise ValueError(f"unpatchify: rep={rep}")
+    ret = out
+    if out is None:
+        if rep_stride not in (None, n):
+            raise ValueError("unpatchify: rep_stride needs the caller's out buffer")
+        ret = torch.empty((rep,) + shape, device=tokens.device, dtype=out_dtype)
+        out, rep_stride = ret[0], n
+    rep_stride = n if rep_stride is None else int(rep_stride)
+    _need(out, out_dtype, "unpatchify.out")
+    if tuple(out.shape) != shape or not out.is_contiguous():
+        raise ValueError(f"unpatchify: out must be contiguous {shape}")
+    # every copy must lie inside the storage `out` is a view of (the kernel writes rep - 1 copies behind it)
+    room = out.untyped_storage().nbytes() // out.element_size() - out.storage_offset()
+    if rep > 1 and (rep_stride < n or (rep - 1) * rep_stride + n > room):
+        raise ValueError(f"unpatchify: {rep} copies {rep_stride} elements apart do not fit behind out ({room} elements)")
+    lib = _lib.load()
+    _lib.check(lib.wan_unpatchify_rep(_p(tokens), tokens.stride(0), _p(out), 0 if out_dtype == torch.float32 else 1,
+                                      cout, F, Hp, Wp, pt, ph, pw, int(zero_frames), rep, rep_stride, _stream()), "wan_unpatchify_rep")
+    return ret
 
 
 # ---------------------------------------------------------------------------------------------

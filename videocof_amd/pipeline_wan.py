@@ -54,6 +54,7 @@ class WanPipeline:
         self._interrupt = False
         self._graphed = None
         self._graphed_loop = None
+        self._cfg_skip_literal = False      # tests: take cfg_skip steps the reference's literal way (doubled batch, then guidance)
         self.release_workspaces_after_denoise = False     # see __call__: hand the DiT's activation buffers back before the VAE decode
         # Set to a dict to get synchronised wall seconds per stage of the next __call__ ("text_encoder", "vae_encode",
         # "denoise_loop", "vae_decode"): a measuring aid (bench.py's `e2e` object); None = no synchronisation anywhere.
@@ -357,13 +358,23 @@ class WanPipeline:
 
         use_rope_map = repeat_rope and (video is not None or source_latents is not None or latents is not None)
 
+        cfg_skip_now = getattr(self.transformer, "cfg_skip_now", None)
+
         def denoise(latents, embeds):
             """The loop of :694-740 on `latents` with the prompt embeddings `embeds`; eager, or recorded into a hipGraph."""
             for i, t in enumerate(timesteps):                                                   # :694
                 self.transformer.current_steps = i
                 if self._interrupt:
                     continue
-                latent_model_input = torch.cat([latents] * 2) if do_cfg else latents           # :700
+                # A step the model's cfg_skip rule halves (enable_cfg_skip; cfg_optimization.py:5-38) returns the conditional
+                # prediction twice, and guidance on two equal halves is that prediction itself: nu + g * (nt - nu) = nu + g * 0 = nu.
+                # So such a step calls the model with the conditional sample and embeddings only -- no doubled batch, no guidance
+                # arithmetic.  `_cfg_skip_literal` keeps the reference's literal order (doubled batch through the model's rule, then
+                # guidance) reachable; both give the same latents (tests/test_gpu_cfg_skip.py).
+                half = do_cfg and cfg_skip_now is not None and cfg_skip_now(2 * latents.shape[0])
+                short = half and not self._cfg_skip_literal
+                step_embeds = embeds[len(embeds) // 2:] if short else embeds
+                latent_model_input = torch.cat([latents] * 2) if do_cfg and not short else latents   # :700
                 latent_model_input = self.scheduler.scale_model_input(latent_model_input, t)
                 timestep = t.expand(latent_model_input.shape[0])                                # :705
                 nb = latent_model_input.shape[0]
@@ -378,10 +389,16 @@ class WanPipeline:
                     fsi = [condition_count] * nb                                                # :713
                     if cot:
                         gfi = [(condition_count, condition_count + ground_latent_count)] * nb  # :716-718
-                noise_pred = forward(x=latent_model_input, context=embeds, t=timestep,
-                                     seq_len=seq_len, frame_split_indices=fsi,
-                                     ground_frame_indices=gfi)                                  # :721-728
-                if do_cfg:
+                if short:
+                    self.transformer._cfg_skip_suspended = True       # this call already is the conditional half
+                try:
+                    noise_pred = forward(x=latent_model_input, context=step_embeds, t=timestep,
+                                         seq_len=seq_len, frame_split_indices=fsi,
+                                         ground_frame_indices=gfi)                              # :721-728
+                finally:
+                    if short:
+                        self.transformer._cfg_skip_suspended = False
+                if do_cfg and not short:
                     nu, nt = noise_pred.chunk(2)
                     noise_pred = nu + self.guidance_scale * (nt - nu)                           # :731-733
                 if prev_mask is None:
@@ -416,7 +433,10 @@ class WanPipeline:
                        int(condition_count), int(ground_latent_count), bool(cot), bool(use_rope_map), int(seq_len),
                        int(self.scheduler.config.solver_order), bool(self.scheduler.config.lower_order_final),
                        type(self.scheduler).__name__, self.scheduler.config.get("algorithm_type"), self.scheduler.config.get("solver_type"),
-                       bool(self.scheduler.config.get("euler_at_final", False)))
+                       bool(self.scheduler.config.get("euler_at_final", False)),
+                       # which steps run on the conditional half only (enable_cfg_skip) is baked into the captured loop
+                       getattr(self.transformer, "cfg_skip_ratio", None), getattr(self.transformer, "num_inference_steps", None),
+                       bool(self._cfg_skip_literal))
 
                 def loop_fn(lat, embeds):
                     self.scheduler._reset()

@@ -90,6 +90,19 @@ class _Block:
                  "n3w", "n3b", "w1", "b1", "w2", "b2", "modulation", "f8", "_cw", "spw")
 
 
+def cfg_skip_active(batch: int, cfg_skip_ratio, current_steps, num_inference_steps) -> bool:
+    """The condition of the reference's ``@cfg_skip()`` decorator (videox_fun/utils/cfg_optimization.py:9, 34), term by term:
+    a batch that can be a guidance pair, the switch set, and the step inside the last ``cfg_skip_ratio`` share of the loop
+    (the comparison in Python floats, as there)."""
+    return bool(batch >= 2 and cfg_skip_ratio is not None and current_steps >= num_inference_steps * (1 - cfg_skip_ratio))
+
+
+def cfg_skip_half(arg, half: int):
+    """cfg_optimization.py:15-26: tensors, lists, tuples and ndarrays lose their first ``half`` entries, anything else passes."""
+    import numpy as np
+    return arg[half:] if isinstance(arg, (torch.Tensor, list, tuple, np.ndarray)) else arg
+
+
 class WanTransformer3DModel(nn.Module):
     def __init__(self, model_type="t2v", patch_size=(1, 2, 2), text_len=512, in_dim=16, dim=2048,
                  ffn_dim=8192, freq_dim=256, text_dim=4096, out_dim=16, num_heads=16, num_layers=32,
@@ -138,6 +151,8 @@ class WanTransformer3DModel(nn.Module):
         self.cfg_skip_ratio = None
         self.current_steps = 0
         self.num_inference_steps = None
+        self._cfg_skip_suspended = False    # WanPipeline: the call it makes already IS the conditional half (no second halving)
+        self._bufs_used = None              # GraphedLoop: list collecting the workspace sets a capture touches
         self.sp_world_size = 1
         self.sp_world_rank = 0
         self._sp = None
@@ -644,12 +659,25 @@ class WanTransformer3DModel(nn.Module):
         self.teacache = None
 
     def enable_cfg_skip(self, cfg_skip_ratio, num_steps):
-        if cfg_skip_ratio:
-            raise NotImplementedError("cfg_skip is identity on every supported config (SURVEY.md section 2, row 8)")
-        self.cfg_skip_ratio, self.current_steps, self.num_inference_steps = None, 0, None
+        """wan_transformer3d.py:752-760.  Lossy and opt-in: in the last ``cfg_skip_ratio`` share of ``num_steps`` a call with a
+        guidance batch (>= 2 samples) runs on ``x[bs // 2:]`` -- the conditional half -- only and returns that result twice, so
+        guidance collapses to the conditional prediction (``cfg_skip_active``; the rule itself is applied by ``forward``).
+        The caller advances ``current_steps`` (``WanPipeline`` sets it every step, and ``num_inference_steps`` on every call)."""
+        if not 0 <= cfg_skip_ratio <= 1:
+            raise ValueError(f"enable_cfg_skip: cfg_skip_ratio={cfg_skip_ratio} is a share of the steps, in [0, 1]")
+        if cfg_skip_ratio != 0:
+            self.cfg_skip_ratio, self.current_steps, self.num_inference_steps = cfg_skip_ratio, 0, num_steps
+        else:
+            self.cfg_skip_ratio, self.current_steps, self.num_inference_steps = None, 0, None
 
     def disable_cfg_skip(self):
         self.cfg_skip_ratio, self.current_steps, self.num_inference_steps = None, 0, None
+
+    def cfg_skip_now(self, batch: int) -> bool:
+        """Would ``forward`` halve a call of ``batch`` samples at the current step?  (``WanPipeline`` asks before it builds the
+        doubled batch; ``GraphedForward`` keys its graphs on it.)"""
+        return not self._cfg_skip_suspended and cfg_skip_active(batch, self.cfg_skip_ratio, self.current_steps,
+                                                                self.num_inference_steps)
 
     def share_cfg_skip(self, transformer=None):
         """wan_transformer3d.py:762-768 (the second transformer of a two-stage pipeline takes the first one's counters)."""
@@ -717,17 +745,27 @@ class WanTransformer3DModel(nn.Module):
         reads -- are overwritten in place."""
         vers = tuple(u._version for u in context)
         if self._ctx_cache is not None:
-            held, v0, kv = self._ctx_cache
+            held, v0, kv = self._ctx_cache[:3]
             if (len(held) == len(context) and all(a is b for a, b in zip(held, context)) and v0 == vers
                     and (into is None or kv is into)):
                 return kv
+            # a cfg_skip step (enable_cfg_skip): the call carries the conditional TAIL of the batch the cache was built for.
+            # It reads that part of the cache through views (sample-major buffers: a leading-dimension offset); the entry itself
+            # stays, so the next full-batch call still hits it.  `into` (a captured graph's buffers) must be that very memory.
+            n = len(context)
+            if (0 < n < len(held) and all(a is b for a, b in zip(held[-n:], context)) and v0[-n:] == vers):
+                tails = self._ctx_cache[3]
+                if n not in tails:
+                    tails[n] = [(ck[-n:], cvt[-n:]) for ck, cvt in kv]
+                if into is None or into is tails[n] or into[0][0].data_ptr() == tails[n][0][0].data_ptr():
+                    return tails[n] if into is None else into
         old = into
         if old is None and self._ctx_cache is not None and self._ctx_cache[2][0][0].shape[0] == B:
             old = self._ctx_cache[2]
         self._ctx_cache = None
         ctx = self._text_embed(context)
         kv = [self._context_kv(blk, ctx, B, out=None if old is None else old[i]) for i, blk in enumerate(self.blocks)]
-        self._ctx_cache = (list(context), vers, kv)
+        self._ctx_cache = (list(context), vers, kv, {})      # {}: tail views handed to cfg_skip steps, by sample count
         return kv
 
     def _last_block_suffix(self, blk, em, xs, h, qk, vt, att, cq, ff, ctx_kv, rp, r0, L):
@@ -808,9 +846,14 @@ class WanTransformer3DModel(nn.Module):
         b = self._bufs.get(key)
         if b is not None:
             self._bufs_last = key
+            if self._bufs_used is not None:
+                self._bufs_used.append(b)
             return b
-        for k in [k for k, v in self._bufs.items() if not getattr(v, "pinned", False)]:
-            del self._bufs[k]                                  # eager use keeps one shape; pinned sets belong to captured graphs
+        # eager use keeps one shape; pinned sets belong to captured graphs.  With cfg_skip set a loop alternates between the guidance
+        # batch and its conditional half: the sets of the same shape at another batch size stay (no re-allocation at the boundary).
+        keep_b = self.cfg_skip_ratio is not None
+        for k in [k for k, v in self._bufs.items() if not getattr(v, "pinned", False) and not (keep_b and k[1:] == key[1:])]:
+            del self._bufs[k]
         C, dev, M = self.dim, self._device, B * Ll
         b = SimpleNamespace()
         b.h = torch.empty(M, C, device=dev, dtype=torch.bfloat16)
@@ -855,6 +898,8 @@ class WanTransformer3DModel(nn.Module):
         b.pinned = False
         self._bufs[key] = b
         self._bufs_last = key
+        if self._bufs_used is not None:
+            self._bufs_used.append(b)
         return b
 
     def release_workspaces(self, keep_pinned: bool = False):
@@ -1174,7 +1219,7 @@ class WanTransformer3DModel(nn.Module):
         holder.cws.gemm_ws_bytes = gws.numel() if gws is not None else 0
         return holder.cws
 
-    def _forward_composite(self, x, emod, ehead, kvs, rp, bufs, B, Ll, L, out_dtype):
+    def _forward_composite(self, x, emod, ehead, kvs, rp, bufs, B, Ll, L, out_dtype, rep=1):
         """The token path of forward as ONE C call (wan_dit_forward, include/wan_hip.h a11'): used when nothing hooks into
         the block loop (no TeaCache, probes, fp8 projections, suffix-only last block, kernel events) on a single device."""
         from ._lib import BlockWeights, DitWeights, DitWorkspace, check, load
@@ -1196,11 +1241,15 @@ class WanTransformer3DModel(nn.Module):
         bufs.dws.block = self._block_cws(bufs, bufs, B, Ll, L)
         ck = (ctypes.c_void_p * n)(*[kv[0].data_ptr() for kv in kvs])
         cvt = (ctypes.c_void_p * n)(*[kv[1].data_ptr() for kv in kvs])
-        out = torch.empty(B, self.out_dim, F, Hh, Ww, device=self._device, dtype=out_dtype)
-        check(lib.wan_dit_forward(p(x), 0 if x.dtype == torch.float32 else 1, p(out), 0 if out_dtype == torch.float32 else 1,
-                                  p(emod), p(ehead), ck, cvt, ctypes.byref(self._cdw[0]), ctypes.byref(bufs.dws),
-                                  p(self._rope_dev[0]), p(self._rope_dev[1]), ctypes.byref(rp), B, F, Hh, Ww, Ll,
-                                  min(int(self.mask_source_frames), F // pt) * pt, ops._stream()), "wan_dit_forward")
+        out = torch.empty(rep * B, self.out_dim, F, Hh, Ww, device=self._device, dtype=out_dtype)
+        args = (p(x), 0 if x.dtype == torch.float32 else 1, p(out), 0 if out_dtype == torch.float32 else 1,
+                p(emod), p(ehead), ck, cvt, ctypes.byref(self._cdw[0]), ctypes.byref(bufs.dws),
+                p(self._rope_dev[0]), p(self._rope_dev[1]), ctypes.byref(rp), B, F, Hh, Ww, Ll,
+                min(int(self.mask_source_frames), F // pt) * pt)
+        if rep == 1:
+            check(lib.wan_dit_forward(*args, ops._stream()), "wan_dit_forward")
+        else:       # a cfg_skip step: the unpatchify store writes the result `rep` times along the batch axis
+            check(lib.wan_dit_forward_rep(*args, rep, ops._stream()), "wan_dit_forward_rep")
         return out
 
     def _block_composite(self, blk: _Block, em, xs, bufs, ctx_kv, rp, B, Ll, L):
@@ -1255,6 +1304,21 @@ class WanTransformer3DModel(nn.Module):
     @torch.no_grad()
     def forward(self, x, t, context, seq_len, clip_fea=None, y=None, y_camera=None, full_ref=None,
                 subject_ref=None, cond_flag=True, frame_split_indices=None, ground_frame_indices=None):
+        """wan_transformer3d.py:818-1106 behind the ``@cfg_skip()`` rule (videox_fun/utils/cfg_optimization.py:5-38): while the rule
+        holds, ``x`` and every tensor / list / tuple / ndarray argument lose their first ``len(x) // 2`` entries, the forward runs on
+        what is left and its result is returned twice along dim 0 (written twice by the unpatchify store, ``wan_unpatchify_rep``).
+        An odd batch computes ``bs - bs // 2`` samples and returns twice that many, as the decorator does."""
+        bs = len(x)
+        if not self.cfg_skip_now(bs):
+            return self._forward(x, t, context, seq_len, clip_fea, y, y_camera, full_ref, subject_ref, cond_flag,
+                                 frame_split_indices, ground_frame_indices)
+        half = bs // 2
+        args = [cfg_skip_half(a, half) for a in (x, t, context, seq_len, clip_fea, y, y_camera, full_ref, subject_ref, cond_flag,
+                                                 frame_split_indices, ground_frame_indices)]
+        return self._forward(*args, rep=2)
+
+    def _forward(self, x, t, context, seq_len, clip_fea=None, y=None, y_camera=None, full_ref=None,
+                 subject_ref=None, cond_flag=True, frame_split_indices=None, ground_frame_indices=None, rep=1):
         if not self.blocks:
             raise RuntimeError("weights are not loaded (call load_state_dict / from_pretrained)")
         if any(v is not None for v in (clip_fea, y, y_camera, full_ref, subject_ref)):
@@ -1293,12 +1357,12 @@ class WanTransformer3DModel(nn.Module):
                 for key in dict.fromkeys(keys):
                     idx = [b for b in range(B) if keys[b] == key]
                     sel = torch.tensor(idx, device=x.device)
-                    y = self.forward(x.index_select(0, sel), t.index_select(0, sel.to(t.device)), [context[b] for b in idx], seq_len,
-                                     cond_flag=cond_flag, frame_split_indices=[key[0]] * len(idx),
-                                     ground_frame_indices=[key[1]] * len(idx) if key[1] is not None else None)
+                    y = self._forward(x.index_select(0, sel), t.index_select(0, sel.to(t.device)), [context[b] for b in idx], seq_len,
+                                      cond_flag=cond_flag, frame_split_indices=[key[0]] * len(idx),
+                                      ground_frame_indices=[key[1]] * len(idx) if key[1] is not None else None)
                     for j, b in enumerate(idx):
                         outs[b] = y[j]
-                return torch.stack(outs)
+                return torch.stack(outs * rep)          # (the group results are gathered by a copy anyway: `rep` rides on it)
         P, rank = self.sp_world_size, self.sp_world_rank
         usp = self._usp = self._sp is not None and (P > 1 or self.force_ulysses)
         if usp:
@@ -1329,7 +1393,8 @@ class WanTransformer3DModel(nn.Module):
                 and dtype in (torch.float32, torch.bfloat16)):
             kvs = ctx_kv if ctx_kv[0] is not None else [self._context_kv(blk, ctx, B) for blk in self.blocks]
             rp = self._rope_map(grid, frame_split_indices, ground_frame_indices, 0, Ll)
-            return self._forward_composite(x.contiguous(), emod, ehead, kvs, rp, self._workspaces(B, Ll, L, seq_len), B, Ll, L, dtype)
+            return self._forward_composite(x.contiguous(), emod, ehead, kvs, rp, self._workspaces(B, Ll, L, seq_len), B, Ll, L, dtype,
+                                           rep=rep)
 
         # -- patch embedding into the fp32 residual stream (this rank's token rows only) --------
         xs = torch.zeros(M, C, device=dev, dtype=torch.float32)
@@ -1383,10 +1448,12 @@ class WanTransformer3DModel(nn.Module):
             yt = self._sp.all_gather_tokens(yt)                                        # :1085-1086
             self._comm_done(cev)
         out_dtype = dtype if dtype in (torch.float32, torch.bfloat16) else torch.float32
-        out = torch.empty(B, self.out_dim, grid[0] * pt, grid[1] * ph, grid[2] * pw, device=dev, dtype=out_dtype)
+        out = torch.empty(rep * B, self.out_dim, grid[0] * pt, grid[1] * ph, grid[2] * pw, device=dev, dtype=out_dtype)
         for b in range(B):
+            # rep > 1 (a cfg_skip step): copy k of sample b lands in batch slot k * B + b, i.e. torch.cat([result] * rep)
             ops.unpatchify(yt[b], grid, self.patch_size, self.out_dim, out_dtype,
-                           zero_frames=min(int(self.mask_source_frames), grid[0]) * pt, out=out[b])
+                           zero_frames=min(int(self.mask_source_frames), grid[0]) * pt, out=out[b],
+                           rep=None if rep == 1 else rep, rep_stride=None if rep == 1 else B * out[0].numel())
         if self.teacache is not None:
             self.teacache.step_done(cond_flag)                                        # :1101-1104
         return out.to(dtype)
