@@ -582,6 +582,30 @@ wan_status_t wan_cl_to_video(const void* x_bf16, int64_t ld, void* out, int out_
                              int clamp, void* stream);
 
 /* ===========================================================================
+ * Frames in, frames out: the uint8 frames of a video reader / writer on the device, on both sides of the VAE.
+ * ------------------------------------------------------------------------- */
+
+/* uint8 [B, T, H, W, 3] (interleaved, as read) -> [B, 3, T, H, W] planar in out_dtype (0 fp32, 1 bf16):
+ *     out = cast(float32(u) * float32(2.0 / 255.0) - 1.0f), two float32 operations rounded one after the other (no FMA),
+ *     then one round-to-nearest-even cast -- what AutoencoderKLWan.encode consumes, no further cast in between.
+ * replaces: load_video_frames' host conversion `permute([3, 0, 1, 2]).unsqueeze(0).float()`, `x * (2.0 / 255.0) - 1.0`
+ *           (fast_infer.py:88-90; inference.py the same) and the pipeline's `video.to(device, dtype)` (pipeline_wan.py:397).
+ * Any H, W, T; B * T <= 65535.  H * W % 16 == 0 with 16-byte aligned tensors moves 16 bytes per access. */
+wan_status_t wan_frames_u8_to_video(const void* frames_u8, void* out, int out_dtype, int B, int T, int H, int W,
+                                    void* stream);
+
+/* the decoder's output [B, 3, T, H, W] (in_dtype 0 fp32, 1 bf16), frames [t0, t0 + nt) -> uint8 [B, T_out, H, W, 3] from
+ * frame t_dst on (so that the grounding and the edit segment of a CoF call land in their slices of one clip):
+ *     u8 = trunc(float32(clamp(x / 2 + 0.5, 0, 1)) * 255.0f), `x / 2` and `+ 0.5` each rounded to in_dtype as a torch
+ *     tensor op of that dtype rounds them.
+ * replaces: decode_latents' `(frames / 2 + 0.5).clamp(0, 1)`, `.cpu().float().numpy()` (pipeline_wan.py:423-428) and
+ *           save_videos_grid's `b c t h w -> t h w c` rearrangement and `(x * 255).numpy().astype(np.uint8)`
+ *           (videox_fun/utils/utils.py:59-68; one video per call: make_grid is the identity).
+ * Any H, W, T; B * nt <= 65535; nt == 0 enqueues nothing. */
+wan_status_t wan_video_to_frames_u8(const void* video, int in_dtype, void* frames_u8, int B, int T, int H, int W,
+                                    int t0, int nt, int T_out, int t_dst, void* stream);
+
+/* ===========================================================================
  * the umT5 text encoder (videox_fun/models/wan_text_encoder.py:256-304), the step
  * before the denoising path.  Its Linear layers are wan_gemm_bf16; the rest:
  * ------------------------------------------------------------------------- */

@@ -336,6 +336,60 @@ static void check_layout() {
     report("unpatchify fp32 out", rel_l2(r2, g2), 0.0);
 }
 
+static void check_frame_io() {
+    printf("wan_frames_u8_to_video / wan_video_to_frames_u8\n");
+    // (T, H, W): a wide shape (H * W % 16 == 0) and one with odd byte rows (the element-wise kernels)
+    const int shapes[2][3] = {{3, 16, 32}, {2, 6, 13}};
+    for (auto& sh : shapes) {
+        const int B = 2, T = sh[0], H = sh[1], W = sh[2];
+        const size_t npix = (size_t)H * W, n = (size_t)B * T * npix * 3;
+        std::vector<uint8_t> fr(n);
+        for (size_t i = 0; i < n; ++i) fr[i] = (uint8_t)(i < 256 * 3 ? i / 3 : rng());      // every byte value, then random
+        Dev<uint8_t> dfr(fr);
+        for (int dt = 0; dt < 2; ++dt) {
+            Dev<float> of(n); Dev<bf16> ob(n);
+            WAN(wan_frames_u8_to_video(dfr.p, dt ? (void*)ob.p : (void*)of.p, dt, B, T, H, W, nullptr));
+            HIP(hipDeviceSynchronize());
+            auto got = dt ? bf_to_f(ob.host()) : of.host();
+            size_t bad = 0;
+            for (int b = 0; b < B; ++b) for (int t = 0; t < T; ++t) for (size_t p = 0; p < npix; ++p) for (int c = 0; c < 3; ++c) {
+                volatile float m = (float)fr[(((size_t)b * T + t) * npix + p) * 3 + c] * (float)(2.0 / 255.0);      // two roundings
+                volatile float r = m - 1.0f;
+                const float want = dt ? bf2f(f2bf(r)) : (float)r;
+                bad += got[(((size_t)b * 3 + c) * T + t) * npix + p] != want;
+            }
+            char name[96]; snprintf(name, sizeof name, "frames -> video %s %dx%dx%d", dt ? "bf16" : "fp32", T, H, W);
+            report(name, (double)bad, 0.0, "mismatches");
+            // back: values spread over [-1.5, 1.5], frames [1, T) of the video into frames [2, T + 1) of a (T + 2)-frame clip
+            auto x = randn(n, 0.7f);
+            for (size_t i = 0; i < 512 && i < n; ++i) x[i] = 2.0f * ((float)(i / 2) / 255.0f) - 1.0f - (i % 2 ? 1e-3f : 0.f);
+            if (dt) x = bf_round(x);
+            Dev<float> xf(x); Dev<bf16> xb(to_bf(x));
+            const int To = T + 2;
+            Dev<uint8_t> clip((size_t)B * To * npix * 3); clip.zero();
+            WAN(wan_video_to_frames_u8(dt ? (const void*)xb.p : (const void*)xf.p, dt, clip.p, B, T, H, W, 1, T - 1, To, 2, nullptr));
+            HIP(hipDeviceSynchronize());
+            auto gb = clip.host();
+            bad = 0;
+            for (int b = 0; b < B; ++b) for (int t = 0; t < To; ++t) for (size_t p = 0; p < npix; ++p) for (int c = 0; c < 3; ++c) {
+                uint8_t want = 0;                                                                   // untouched frames stay zero
+                if (t >= 2 && t - 2 < T - 1) {
+                    volatile float h = x[(((size_t)b * 3 + c) * T + (t - 2 + 1)) * npix + p] * 0.5f;
+                    if (dt) h = bf2f(f2bf(h));
+                    volatile float u = h + 0.5f;
+                    if (dt) u = bf2f(f2bf(u));
+                    const float cl = u < 0.f ? 0.f : u > 1.f ? 1.f : (float)u;
+                    volatile float s = cl * 255.0f;
+                    want = (uint8_t)(int)s;
+                }
+                bad += gb[(((size_t)b * To + t) * npix + p) * 3 + c] != want;
+            }
+            snprintf(name, sizeof name, "video %s -> frames %dx%dx%d (range, offset)", dt ? "bf16" : "fp32", T, H, W);
+            report(name, (double)bad, 0.0, "mismatches");
+        }
+    }
+}
+
 // ------------------------------------------------------------------ perf
 static void perf(bool big, bool attn_only = false, bool gemm_only = false, bool rows_only = false) {
     hipDeviceProp_t prop; HIP(hipGetDeviceProperties(&prop, 0));
@@ -418,7 +472,7 @@ int main(int argc, char** argv) {
     for (int i = 1; i < argc; ++i) if (!strcmp(argv[i], "--big")) big = true;
     printf("libwan_hip ABI %d\n", wan_abi_version());
     if (mode == "check" || mode == "all") {
-        check_ln(); check_rmsnorm_rope(); check_gemm(); check_attn(); check_layout();
+        check_ln(); check_rmsnorm_rope(); check_gemm(); check_attn(); check_layout(); check_frame_io();
         printf("%s (%d failures)\n", g_fail ? "CHECK FAILED" : "ALL CHECKS PASSED", g_fail);
     }
     if (mode == "rows") {         // the HBM-bound row kernels alone: numerics, then the 14B-width timings at L = 67 080 (three rounds)

@@ -12,6 +12,7 @@ Host side mirrors the reference's interface for this path only:
     videocof_amd.lora_utils                 <- videox_fun/utils/lora_utils.py (merge_lora on state dicts)
     videocof_amd.cache_utils                <- videox_fun/models/cache_utils.py (TeaCache, opt-in)
     videocof_amd.dist                       <- videox_fun/dist/{fuser,wan_xfuser}.py (Ulysses on RCCL)
+    videocof_amd.video_io                   <- fast_infer.py load_video_frames + videox_fun/utils/utils.py save_videos_grid's byte conversion
 
 Device arithmetic lives in ``libwan_hip.so`` (csrc/, C ABI in include/wan_hip.h).
 """
@@ -24,5 +25,6 @@ from .cache_utils import TeaCache, get_teacache_coefficients  # noqa: F401
 from .attention_utils import attention, flash_attention  # noqa: F401
 from .wan_vae import AutoencoderKLWan  # noqa: F401
 from .wan_text_encoder import WanT5EncoderModel  # noqa: F401
+from .video_io import frames_to_video, video_to_frames, load_video_frames  # noqa: F401
 
 __version__ = "0.1.0"

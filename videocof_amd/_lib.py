@@ -200,6 +200,9 @@ SIGNATURES = {
     "wan_softmax_rows": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_float, c_void_p]),
     "wan_video_to_cl": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int64, c_void_p]),
     "wan_cl_to_video": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int64, c_int, c_void_p]),
+    "wan_frames_u8_to_video": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "wan_video_to_frames_u8": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                       c_void_p]),
 }
 
 _lib = None

@@ -899,6 +899,60 @@ def cl_to_video(x: torch.Tensor, cv: int, out_dtype: torch.dtype, clamp: bool) -
 
 
 @_on_tensor_device
+def frames_u8_to_video(frames: torch.Tensor, out_dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
+    """uint8 [B,T,H,W,3] frames as a video reader yields them -> [B,3,T,H,W] in out_dtype (fp32|bf16),
+    ``float32(u) * (2.0 / 255.0) - 1.0`` rounded as the reference's host code rounds it (fast_infer.py:88-90)."""
+    _need(frames, torch.uint8, "frames_u8_to_video.frames")
+    if frames.dim() != 5 or frames.shape[-1] != 3:
+        raise ValueError(f"frames_u8_to_video.frames: expected [B, T, H, W, 3], got {tuple(frames.shape)}")
+    if out_dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"frames_u8_to_video: dtype {out_dtype} not supported (float32 or bfloat16)")
+    frames = frames.contiguous()
+    B, T, H, W, _ = frames.shape
+    out = torch.empty(B, 3, T, H, W, device=frames.device, dtype=out_dtype)
+    lib = _lib.load()
+    _lib.check(lib.wan_frames_u8_to_video(_p(frames), _p(out), 0 if out_dtype == torch.float32 else 1, B, T, H, W, _stream()),
+               "wan_frames_u8_to_video")
+    return out
+
+
+@_on_tensor_device
+def video_to_frames_u8(video: torch.Tensor, out: Optional[torch.Tensor] = None, frame_range: Optional[Tuple[int, int]] = None,
+                       dst_frame: int = 0) -> torch.Tensor:
+    """The decoder's [B,3,T,H,W] (fp32|bf16) -> uint8 [B,T,H,W,3], ``trunc(clamp(x / 2 + 0.5, 0, 1) * 255)`` with the inner
+    arithmetic rounded in the video's dtype (pipeline_wan.py:423-428, utils.py:59-68).  ``frame_range`` = (first, end) picks
+    frames of ``video``; ``out`` = a contiguous uint8 [B,T_out,H,W,3] device clip that receives them from frame ``dst_frame`` on
+    (returned as given); without ``out`` a clip of exactly the chosen frames is allocated."""
+    if video.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"video_to_frames_u8.video: expected float32 or bfloat16, got {video.dtype}")
+    _need(video, video.dtype, "video_to_frames_u8.video")
+    if video.dim() != 5 or video.shape[1] != 3:
+        raise ValueError(f"video_to_frames_u8.video: expected [B, 3, T, H, W], got {tuple(video.shape)}")
+    video = video.contiguous()
+    B, _, T, H, W = video.shape
+    t0, t1 = (0, T) if frame_range is None else (int(frame_range[0]), int(frame_range[1]))
+    if not 0 <= t0 <= t1 <= T:
+        raise ValueError(f"video_to_frames_u8: frame_range {(t0, t1)} of {T} frames")
+    if out is None:
+        if dst_frame != 0:
+            raise ValueError("video_to_frames_u8: dst_frame needs `out`")
+        out = torch.empty(B, t1 - t0, H, W, 3, device=video.device, dtype=torch.uint8)
+    else:
+        _need(out, torch.uint8, "video_to_frames_u8.out")
+        if out.dim() != 5 or not out.is_contiguous() or out.device != video.device or \
+                (out.shape[0], out.shape[2], out.shape[3], out.shape[4]) != (B, H, W, 3):
+            raise ValueError(f"video_to_frames_u8.out: expected a contiguous [{B}, T_out, {H}, {W}, 3] on {video.device}, got "
+                             f"{tuple(out.shape)} on {out.device}")
+        if not 0 <= dst_frame <= out.shape[1] - (t1 - t0):
+            raise ValueError(f"video_to_frames_u8: {t1 - t0} frames at dst_frame {dst_frame} of a {out.shape[1]}-frame clip")
+    if t1 > t0:
+        lib = _lib.load()
+        _lib.check(lib.wan_video_to_frames_u8(_p(video), 0 if video.dtype == torch.float32 else 1, _p(out), B, T, H, W,
+                                              t0, t1 - t0, out.shape[1], int(dst_frame), _stream()), "wan_video_to_frames_u8")
+    return out
+
+
+@_on_tensor_device
 def lincomb(terms, out_dtype: torch.dtype) -> torch.Tensor:
     """sum_i c_i * x_i over <= 4 same-shape CUDA tensors in one pass (fp32 accumulate); `terms` is a list
     of (coefficient, tensor).  Inputs are brought to `out_dtype` (fp32 or bf16) if they differ."""

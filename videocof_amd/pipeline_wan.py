@@ -188,7 +188,15 @@ class WanPipeline:
     def _encode_modes(self, video, device, dtype):
         if self.vae is None:
             raise ValueError("no VAE: provide `source_latents` (or full `latents`)")
-        video = video.to(device=device, dtype=dtype)
+        if isinstance(video, np.ndarray):
+            video = torch.from_numpy(video)
+        if video.dtype == torch.uint8:
+            # frames as a video reader yields them, [B, T, H, W, 3] or [T, H, W, 3]: one byte per sample over the host link, then
+            # wan_frames_u8_to_video = the reference loader's `x * (2.0 / 255.0) - 1.0` (fast_infer.py:88-90) and the cast to `dtype`
+            from . import ops
+            video = ops.frames_u8_to_video((video if video.dim() == 5 else video.unsqueeze(0)).to(device), dtype)
+        else:
+            video = video.to(device=device, dtype=dtype)
         return torch.cat([self.vae.encode(video[i:i + 1])[0].mode() for i in range(video.shape[0])])      # mode, no mean / std (:404-409)
 
     def prepare_latents(self, batch_size, num_channels_latents, num_frames, height, width, dtype, device, generator, latents=None):
@@ -250,11 +258,38 @@ class WanPipeline:
     def attention_kwargs(self):
         return getattr(self, "_attention_kwargs", None)
 
-    def decode_latents(self, latents: torch.Tensor, out: Optional[torch.Tensor] = None) -> np.ndarray:
+    def _decode_frames_u8(self, latents, out, clip=None, dst_frame=0) -> np.ndarray:
+        """decode, then wan_video_to_frames_u8 into frames [dst_frame, dst_frame + T) of the device clip `clip` (uint8
+        [B, T_clip, H, W, 3]; None = one of exactly T frames), then ONE asynchronous copy per sample of that frame range -- one
+        contiguous run of bytes -- into `out`, a page-locked uint8 [B, T, H, W, 3] host tensor (or a frame slice of one)."""
+        from . import ops
+        frames = self.vae.decode(latents.to(self.vae.dtype)).sample
+        clip = ops.video_to_frames_u8(frames, out=clip, dst_frame=dst_frame)
+        seg = clip[:, dst_frame:dst_frame + frames.shape[2]]
+        if out is None:
+            out = torch.empty(seg.shape, dtype=torch.uint8, pin_memory=True)
+        if tuple(out.shape) != tuple(seg.shape) or out.dtype != torch.uint8:
+            raise ValueError(f"decode_latents: out {out.dtype} {tuple(out.shape)} for uint8 frames {tuple(seg.shape)}")
+        for b in range(seg.shape[0]):
+            out[b].copy_(seg[b], non_blocking=True)
+        torch.cuda.current_stream(frames.device).synchronize()
+        return out.numpy()
+
+    def decode_latents(self, latents: torch.Tensor, out: Optional[torch.Tensor] = None, **switches) -> np.ndarray:
         """:423-428 -- decode, (x / 2 + 0.5).clamp(0, 1), float32 numpy.  The reference converts on the host
         (``frames.cpu().float().numpy()``: a pageable copy, a CPU cast and, in ``__call__``, a concatenate: ~0.1 s for 81 frames at
         480 x 832); here the cast runs on the device and the frames go ONCE, through page-locked memory, to where they stay:
-        ``out`` = a pinned float32 host tensor [B, 3, T, H, W] (or a frame slice of one) that the result is a view of."""
+        ``out`` = a pinned float32 host tensor [B, 3, T, H, W] (or a frame slice of one) that the result is a view of.
+        ``as_uint8``: the frames a video writer takes instead, uint8 [B, T, H, W, 3] -- the bytes the reference's writer makes of
+        the float frames (``(x * 255).numpy().astype(np.uint8)`` after ``b c t h w -> t h w c``, videox_fun/utils/utils.py:59-68),
+        converted and transposed by wan_video_to_frames_u8 on the device; ``out`` is then a pinned uint8 host tensor of that shape.
+        (``as_uint8=False`` is the one keyword in ``switches``: the named parameters stay the reference's plus ``out``, which
+        tests/test_oracle_vs_reference.py pins.)"""
+        as_uint8 = bool(switches.pop("as_uint8", False))
+        if switches:
+            raise TypeError(f"decode_latents() got an unexpected keyword argument {next(iter(switches))!r}")
+        if as_uint8:
+            return self._decode_frames_u8(latents, out)
         frames = self.vae.decode(latents.to(self.vae.dtype)).sample
         frames = (frames / 2 + 0.5).clamp(0, 1).float()        # the arithmetic in the VAE's dtype, as the reference does it; the cast on the device
         if not frames.is_cuda:
@@ -465,9 +500,10 @@ class WanPipeline:
         # -- decode (:757-790)
         t_stage = self._stage("vae_decode")
         ground_video = edit_video = video_out = None
-        if output_type == "numpy":
+        if output_type in ("numpy", "uint8"):
+            u8 = output_type == "uint8"      # uint8 [B, T, H, W, 3] frames (wan_video_to_frames_u8) instead of float32 [B, 3, T, H, W]
             if self.vae is None:
-                raise ValueError("output_type='numpy' needs a VAE; use output_type='latent'")
+                raise ValueError(f"output_type={output_type!r} needs a VAE; use output_type='latent'")
             if cot:
                 g0, g1 = condition_count, condition_count + ground_latent_count
                 # grounding | edit frames side by side in ONE page-locked clip (what the reference builds with np.concatenate, :786):
@@ -478,26 +514,38 @@ class WanPipeline:
                 ne = nfr(Ftot - g1) if g1 < Ftot else 0
                 scr = self.vae.config.spatial_compression_ratio
                 clip = None
-                if latents.is_cuda and ng + ne > 0:
-                    clip = torch.empty((latents.shape[0], 3, ng + ne, latents.shape[3] * scr, latents.shape[4] * scr),
-                                       dtype=torch.float32, pin_memory=True)
-                parts = []
-                if ng:
-                    ground_video = self.decode_latents(latents[:, :, g0:g1], None if clip is None else clip[:, :, :ng])
-                    parts.append(ground_video)
-                if ne:
-                    edit_video = self.decode_latents(latents[:, :, g1:], None if clip is None else clip[:, :, ng:])
-                    parts.append(edit_video)
-                video_out = clip.numpy() if clip is not None else np.concatenate(parts, axis=2)
+                if u8 and ng + ne > 0:
+                    # the same clip as bytes: both segments are written by the kernel into their frames of ONE device clip and
+                    # copied, one contiguous run per segment and sample, into their frames of ONE page-locked clip
+                    shape = (latents.shape[0], ng + ne, latents.shape[3] * scr, latents.shape[4] * scr, 3)
+                    clip = torch.empty(shape, dtype=torch.uint8, pin_memory=True)
+                    dev_clip = torch.empty(shape, dtype=torch.uint8, device=latents.device)
+                    if ng:
+                        ground_video = self._decode_frames_u8(latents[:, :, g0:g1], clip[:, :ng], dev_clip, 0)
+                    if ne:
+                        edit_video = self._decode_frames_u8(latents[:, :, g1:], clip[:, ng:], dev_clip, ng)
+                    video_out = clip.numpy()
+                elif not u8:
+                    if latents.is_cuda and ng + ne > 0:
+                        clip = torch.empty((latents.shape[0], 3, ng + ne, latents.shape[3] * scr, latents.shape[4] * scr),
+                                           dtype=torch.float32, pin_memory=True)
+                    parts = []
+                    if ng:
+                        ground_video = self.decode_latents(latents[:, :, g0:g1], None if clip is None else clip[:, :, :ng])
+                        parts.append(ground_video)
+                    if ne:
+                        edit_video = self.decode_latents(latents[:, :, g1:], None if clip is None else clip[:, :, ng:])
+                        parts.append(edit_video)
+                    video_out = clip.numpy() if clip is not None else np.concatenate(parts, axis=2)
             else:
                 if condition_count < Ftot:
-                    edit_video = self.decode_latents(latents[:, :, condition_count:])
+                    edit_video = self.decode_latents(latents[:, :, condition_count:], as_uint8=u8)
                 video_out = edit_video
             if not return_dict:
                 video_out = torch.from_numpy(video_out) if isinstance(video_out, np.ndarray) else video_out
                 ground_video = torch.from_numpy(ground_video) if isinstance(ground_video, np.ndarray) else ground_video
                 edit_video = torch.from_numpy(edit_video) if isinstance(edit_video, np.ndarray) else edit_video
         elif output_type != "latent":
-            raise ValueError(f"output_type {output_type!r} not supported ('numpy' or 'latent')")
+            raise ValueError(f"output_type {output_type!r} not supported ('numpy', 'uint8' or 'latent')")
         self._stage("vae_decode", t_stage)
         return WanPipelineOutput(videos=video_out, ground_videos=ground_video, edit_videos=edit_video, latents=latents)
