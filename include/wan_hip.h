@@ -45,7 +45,13 @@ const char* wan_last_error(void);
  * WAN_ATTN_XCD_MAP, WAN_ATTN_REF, WAN_GEMM_W4, WAN_GEMM_GM, WAN_GEMM_PHASES, WAN_GEMM_VARIANT, WAN_CONV_XCD, WAN_DEBUG_CHECKS, WAN_ATTN_PERSIST) are
  * read ONCE, at the first call into the library; the launch paths never call getenv().  Keys: "attn_tail",
  * "attn_fast", "attn_xcd_map", "attn_ref", "conv_head", "gemm_exp", "gemm_w4", "gemm_gm", "gemm_phases", "gemm_variant", "conv_xcd", "debug_checks",
- * "gemm_pk", "gemm_pk_form", "gemm_pk_workers", "gemm_pk_min_units", "gemm_pk_order", "gemm_splitk", "row_group", "sp_inline", "conv_patch", "attn_persist" (1: cross-attention on the persistent form of the 4-wave kernel), "conv_mfma" (0 = by the per-frame plane, 32 / 16 = force v_mfma_f32_32x32x16_bf16 / v_mfma_f32_16x16x32_bf16).
+ * "gemm_pk", "gemm_pk_form", "gemm_pk_workers", "gemm_pk_min_units", "gemm_pk_order", "gemm_splitk", "row_group", "sp_inline", "sp_reserve_cus", "conv_patch", "attn_persist" (1: cross-attention on the persistent form of the 4-wave kernel), "conv_mfma" (0 = by the per-frame plane, 32 / 16 = force v_mfma_f32_32x32x16_bf16 / v_mfma_f32_16x16x32_bf16).
+ * "sp_reserve_cus" (WAN_SP_RESERVE_CUS, default 0): CUs left free for communication kernels that run on another stream beside the
+ * persistent grids.  When > 0, every grid that is "one resident workgroup per CU" -- the persistent stream-K GEMM's (unless
+ * "gemm_pk_workers" names a grid explicitly) and the persistent cross-attention form's -- sizes itself from CU count - sp_reserve_cus
+ * (rounded down to a multiple of 8, at least 8) instead of the CU count; wan_gemm_workspace_bytes / wan_gemm_pk_grid /
+ * wan_gemm_pk_segment follow.  Another worker count moves the stream-K cut points, so results are equal to those at 0 within the
+ * kernels' tolerances, not bit for bit.  0 leaves every plan as it is.
  * "debug_checks" = 1 turns on SYNCHRONISING contract checks (V^T pad columns of wan_attention_fwd are finite).
  * wan_set_tuning is an atomic store: safe against concurrent launches, which see the old or the new value.
  * wan_get_tuning returns -1 for an unknown key.  No reference counterpart (the reference has no native code).
@@ -424,6 +430,17 @@ wan_status_t wan_sp_wait(wan_sp_comm* comm, void* compute_stream);
 int64_t wan_sp_ticket(const wan_sp_comm* comm);
 wan_status_t wan_sp_wait_for(wan_sp_comm* comm, int64_t ticket, void* compute_stream);
 wan_status_t wan_sp_destroy(wan_sp_comm* comm);
+
+/* a21'' MEASUREMENT ONLY: a device-local copy with the launch footprint of a collective (csrc/sp_emulate.hip).  It stands in for the
+ *      RCCL all-to-all / all-gather kernel of ONE rank where there are no peers (videocof_amd.dist.EmulatedRank(concurrent=True) runs
+ *      it on a side stream while the rank's projections run on the compute stream), so that what a communication kernel costs the
+ *      resident GEMM / attention grids -- and what they cost it -- can be seen on one GPU.
+ *      grid: exactly `channels` workgroups (1..32) of `threads` lanes (256 or 512); workgroup c copies the c-th contiguous share of
+ *      `bytes` in 16-byte accesses (buffers misaligned against each other: byte accesses); any byte count, any alignment.  No LDS, no
+ *      barrier, no atomics, nothing a workgroup waits for: it advances on a single free CU.  dst and src must not overlap.
+ *      ASSUMED, NOT MEASURED: that an RCCL collective on this chip occupies "N channels = N workgroups of 256-512 threads" comes from
+ *      RCCL's public channel model; no RCCL kernel was traced here.  It moves no byte between devices: no xGMI, no peer latency. */
+wan_status_t wan_sp_channel_copy(void* dst, const void* src, int64_t bytes, int channels, int threads, void* stream);
 
 /* ---------------------------------------------------------------------------
  * a11  One WanAttentionBlock as a single call (WanAttentionBlock.forward, wan_transformer3d.py:464-515) -- the

@@ -167,6 +167,7 @@ SIGNATURES = {
     "wan_sp_ticket": (c_int64, [c_void_p]),
     "wan_sp_wait_for": (c_int, [c_void_p, c_int64, c_void_p]),
     "wan_sp_destroy": (c_int, [c_void_p]),
+    "wan_sp_channel_copy": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
     "wan_attention_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int64]),
     "wan_gemm_plan": (c_int, [c_int, c_int, c_int]),
     "wan_gemm_ws_plan": (c_int, [c_int, c_int, c_int]),

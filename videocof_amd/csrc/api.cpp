@@ -41,6 +41,13 @@ int wan_cu_count() {
     return v;
 }
 
+// CUs a resident grid may occupy.  With "sp_reserve_cus" = 0 (the default) this IS wan_cu_count(): no plan moves.
+int wan_resident_cus() {
+    const int cus = wan_cu_count(), reserve = wan_tune(WAN_TUNE_SP_RESERVE_CUS);
+    if (reserve <= 0) return cus;
+    return reserve < cus ? cus - reserve : 0;
+}
+
 // ---------------------------------------------------------------------------------------------------------
 // Developer switches.  The environment is read ONCE (first use, thread-safe function-local static); after that the
 // hot path only loads an atomic int.  wan_set_tuning() overrides a switch at run time (A/B harnesses).
@@ -72,6 +79,7 @@ const TuningKey kTuningKeys[WAN_TUNE_COUNT] = {
     {"gemm_splitk", "WAN_GEMM_SPLITK", 1},              // split-K form of the 128^2 GEMM for small shapes that bring a workspace: 1 = by shape, 0 = never, 2..8 = force that many pieces (developer A/B)
     {"conv_mfma", "WAN_CONV_MFMA", 0},                  // matrix instruction of the VAE's LDS-patch convolution: 0 = by the per-frame plane (16x16x32 when four frames of it fill the chip; never by frame count -- chunked decodes stay bit-identical), 32 = v_mfma_f32_32x32x16_bf16, 16 = v_mfma_f32_16x16x32_bf16
     {"attn_persist", "WAN_ATTN_PERSIST", 1},            // short-KV (cross-attention) launches on the persistent form of the 4-wave kernel: one resident workgroup per CU walks the query blocks (0 = one workgroup per block, developer A/B)
+    {"sp_reserve_cus", "WAN_SP_RESERVE_CUS", 0},        // CUs the persistent grids (gemm_pk, persistent cross-attention) leave free for communication kernels on another stream: they size themselves from wan_cu_count() - this (0 = the whole chip; init_sequence_parallel(reserve_cus=N) sets it)
 };
 struct Tuning {
     std::atomic<int> v[WAN_TUNE_COUNT];

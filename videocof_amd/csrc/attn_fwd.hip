@@ -1522,8 +1522,10 @@ static wan_status_t attention_fwd_impl(const void* q, int64_t ldq, int64_t q_bst
         variant = WAN_ATTN_VARIANT_W4_LAZY;
         // short KV streams (cross-attention: 8 tiles per query block): ONE resident workgroup per CU walks the blocks (PERSIST, see the
         // kernel); the grid stays a multiple of 8 so that w & 7 -- the XCD a head is pinned to -- is the same for every block of a workgroup
-        const bool persist = !self && wan_tune(WAN_TUNE_ATTN_PERSIST) != 0 && nwg > (wan_cu_count() & ~7) && (wan_cu_count() & ~7) >= 8;
-        const dim3 pgrid(persist ? (unsigned)(wan_cu_count() & ~7) : (unsigned)nwg);
+        // (wan_resident_cus: the CUs tuning key "sp_reserve_cus" leaves to communication kernels are not occupied)
+        const int pcus = wan_resident_cus() & ~7;
+        const bool persist = !self && wan_tune(WAN_TUNE_ATTN_PERSIST) != 0 && nwg > pcus && pcus >= 8;
+        const dim3 pgrid(persist ? (unsigned)pcus : (unsigned)nwg);
         if (ref2) {
             if (self) hipLaunchKernelGGL((attn_fwd_w4_kernel<0, false, 2>), grid, block4, kLdsBytesW4, st, a);
             else if (persist) hipLaunchKernelGGL((attn_fwd_w4_kernel<1, false, 2, false, false, true>), pgrid, block4, kLdsBytesW4, st, a);

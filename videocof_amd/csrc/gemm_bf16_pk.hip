@@ -992,10 +992,11 @@ wan_status_t launch_pk(const PkArgs& g, hipStream_t s) {
 
 }  // namespace
 
-// grid of the persistent form: one workgroup per CU, a multiple of 8 (one lane set per XCD), never more than the tile count / 1
+// grid of the persistent form: one workgroup per CU -- of those not reserved for communication kernels (tuning key "sp_reserve_cus") --, a
+// multiple of 8 (one lane set per XCD); an explicit "gemm_pk_workers" wins
 int wan_gemm_pk_workers(int M, int N) {
     const int tiles = ((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-    int w = wan_cu_count() & ~7;
+    int w = wan_resident_cus() & ~7;
     if (const int t = wan_tune(WAN_TUNE_GEMM_PK_WORKERS); t > 0) w = t & ~7;
     (void)tiles;
     // the 4 KiB counter header holds the arrival counters in words [0, workers) and the per-XCD ticket counters from word 512 on

@@ -289,17 +289,82 @@ class EmulatedRank:
     into the receive buffer (the byte count a rank receives, the wrong contents: its own slabs where the peers' would arrive), the
     all-gather P copies of the local shard.  The OUTPUT IS THEREFORE NOT A DENOISED LATENT; what the mode gives is the compute side
     of one rank's step on the shard shapes, i.e. the bound a P-GPU run cannot beat and the number its exposed-communication time
-    adds to.  Nothing in the product path or the tests' parity statements uses it."""
+    adds to.  Nothing in the product path or the tests' parity statements uses it.
 
-    def __init__(self, rank: int = 0, world_size: int = 1):
+    CONCURRENT MODE (``concurrent=True``; tools/bench_sp_overlap.py): the exchanges run where a real transport's would -- on a side
+    stream, as a kernel that competes with the projections for CUs.  The object owns ONE side stream and a small pool of events;
+    ``exchange`` records an event on the caller's stream, the side stream waits for it, runs ``wan_sp_channel_copy`` (a grid of exactly
+    ``channels`` workgroups of ``threads`` lanes -- the footprint ASSUMED for an RCCL collective with that many channels, never
+    measured here) and records a done-event; the returned ``wait()`` makes the caller's current stream wait for that event.  The host
+    is never synchronised.  This is the dependency graph the model's ``wait_k`` / ``wait_v`` / ``wait_q`` / ``wait_o`` express for
+    the real transports, so a consumer that does not wait races here as it would there; ``poison=True`` (tests) makes such a race
+    visible: before the hand-over the receive buffer is filled with a NaN pattern on the caller's stream, so a consumer that runs
+    ahead of the copy reads NaN instead of the similar values of the previous layer.  While the caller's stream is being captured
+    into a hipGraph the copy kernel runs on that stream itself (as ``LibraryComm`` does under ``sp_inline``): a captured graph gets no
+    parallel branch from this mode.  One GPU copying to itself: no xGMI, no peer."""
+
+    _RING = 32          # done-events in flight (a recycled one marks a LATER point of the in-order side stream: waiting for it is still correct)
+
+    def __init__(self, rank: int = 0, world_size: int = 1, concurrent: bool = False, channels: int = 16, threads: int = 512,
+                 poison: bool = False):
         if not (0 <= int(rank) < int(world_size)):
             raise ValueError(f"EmulatedRank: rank {rank} outside a group of {world_size}")
         self.rank, self.world_size, self.group = int(rank), int(world_size), None
         self._host_staged = False
+        self.concurrent, self.poison = bool(concurrent), bool(poison)
+        self.channels, self.threads = int(channels), int(threads)
+        if self.concurrent:
+            if not (1 <= self.channels <= 32):
+                raise ValueError(f"EmulatedRank: {channels} channels (1..32)")
+            if self.threads not in (256, 512):
+                raise ValueError(f"EmulatedRank: {threads} threads per channel (256 or 512)")
+        # start-events (caller's stream -> side stream) and done-events (side stream -> caller's stream) never share a ring: a done
+        # handle returned to the caller must only ever name a point of the SIDE stream
+        self._side, self._starts, self._dones, self._n = None, [], [], 0
+
+    def _event_pair(self):
+        if len(self._dones) < self._RING:
+            self._starts.append(torch.cuda.Event())
+            self._dones.append(torch.cuda.Event())
+        i = self._n % len(self._dones)
+        self._n = (self._n + 1) % self._RING
+        return self._starts[i], self._dones[i]
+
+    def _hand_over(self, recv: torch.Tensor, copies):
+        """Concurrent mode: run `copies` [(dst, src), ...] (together they fill `recv`) behind everything already enqueued on the
+        caller's stream, without blocking it; returns the wait callable."""
+        from . import ops
+        dev = recv.device
+        if not recv.is_cuda:
+            raise RuntimeError(f"EmulatedRank(concurrent=True): buffers are on {dev}; the channel copy is a HIP kernel and has no CPU fallback")
+        if self.poison:
+            recv.view(-1).view(torch.uint8).fill_(0xFF)          # all-ones: NaN in bf16 / fp16 / fp32 / e4m3
+        if torch.cuda.is_current_stream_capturing():
+            for d, s_ in copies:
+                ops.sp_channel_copy(d, s_, self.channels, self.threads)
+            return lambda: None
+        if self._side is None or self._side.device != dev:
+            if self._side is not None:
+                raise RuntimeError(f"EmulatedRank: its side stream lives on {self._side.device}, the buffers on {dev}")
+            self._side = torch.cuda.Stream(device=dev)
+        start, done = self._event_pair()
+        start.record(torch.cuda.current_stream(dev))
+        self._side.wait_event(start)
+        with torch.cuda.stream(self._side):
+            for d, s_ in copies:
+                ops.sp_channel_copy(d, s_, self.channels, self.threads)
+        done.record(self._side)
+        return lambda: torch.cuda.current_stream(dev).wait_event(done)
 
     def exchange(self, recv: torch.Tensor, send: torch.Tensor, async_op: bool = False):
         if send.numel() != recv.numel() or send.numel() % self.world_size or not (send.is_contiguous() and recv.is_contiguous()):
             raise ValueError("exchange: send / recv must be contiguous, of equal size, divisible by the group size")
+        if self.concurrent:
+            wait = self._hand_over(recv, [(recv.view(-1), send.view(-1))])
+            if async_op:
+                return wait
+            wait()
+            return None
         recv.view(-1).copy_(send.view(-1))
         return (lambda: None) if async_op else None
 
@@ -310,7 +375,10 @@ class EmulatedRank:
         P = self.world_size
         y = y.contiguous()
         recv, out = _gather_buffers(self, y, P)
-        recv.copy_(y.unsqueeze(0).expand_as(recv))
+        if self.concurrent:
+            self._hand_over(recv, [(recv[r], y) for r in range(P)])()
+        else:
+            recv.copy_(y.unsqueeze(0).expand_as(recv))
         return _gathered_view(recv, out)
 
 
@@ -326,19 +394,40 @@ def get_sequence_parallel_rank() -> int:
     return _SP.rank if _SP is not None else 0
 
 
-def init_sequence_parallel(group=None, backend: str = "torch", rank: Optional[int] = None, world_size: Optional[int] = None):
+def init_sequence_parallel(group=None, backend: str = "torch", rank: Optional[int] = None, world_size: Optional[int] = None,
+                           reserve_cus: int = 0, concurrent: bool = False, channels: int = 16, threads: int = 512, poison: bool = False):
     """Use an already initialised process group (or WORLD) as the Ulysses group.  ``backend="library"``: the collectives run on
-    the communicator libwan_hip.so owns (``LibraryComm``); the torch group, if any, only carries the rendezvous token."""
+    the communicator libwan_hip.so owns (``LibraryComm``); the torch group, if any, only carries the rendezvous token.
+    ``reserve_cus=N`` (any backend): the library's persistent grids (the stream-K GEMM, the persistent cross-attention form) leave
+    N CUs free for the communication kernels that run beside them (tuning key ``sp_reserve_cus``); ``destroy_sequence_parallel``
+    restores 0.  ``concurrent`` / ``channels`` / ``threads`` / ``poison``: the emulated backend's concurrent mode (``EmulatedRank``)."""
     global _SP
+    if int(reserve_cus) < 0:
+        raise ValueError(f"init_sequence_parallel: reserve_cus={reserve_cus}")
     if backend == "library":
         _SP = LibraryComm(rank, world_size, group)
     elif backend == "torch":
         _SP = SequenceParallelGroup(group)
     elif backend == "emulated":         # measurement only: one rank's compute on the shard shapes, no peers (EmulatedRank)
-        _SP = EmulatedRank(0 if rank is None else rank, 1 if world_size is None else world_size)
+        _SP = EmulatedRank(0 if rank is None else rank, 1 if world_size is None else world_size, concurrent=concurrent,
+                           channels=channels, threads=threads, poison=poison)
     else:
         raise ValueError(f"init_sequence_parallel: backend {backend!r} (\"torch\", \"library\" or \"emulated\")")
+    _set_reserve_cus(int(reserve_cus))
     return _SP
+
+
+_RESERVED = False
+
+
+def _set_reserve_cus(n: int) -> None:
+    """Tuning key ``sp_reserve_cus`` of the library.  The library is only touched when a reservation is asked for or has to be
+    taken back: a plain ``init_sequence_parallel()`` / ``destroy_sequence_parallel()`` needs no built library, as before."""
+    global _RESERVED
+    if n > 0 or _RESERVED:
+        from . import ops
+        ops.set_tuning("sp_reserve_cus", n)
+        _RESERVED = n > 0
 
 
 def destroy_sequence_parallel() -> None:
@@ -346,6 +435,7 @@ def destroy_sequence_parallel() -> None:
     if isinstance(_SP, LibraryComm):
         _SP.close()
     _SP = None
+    _set_reserve_cus(0)
 
 
 def set_multi_gpus_devices(ulysses_degree: int, ring_degree: int = 1, classifier_free_guidance_degree: int = 1):

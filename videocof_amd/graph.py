@@ -44,9 +44,13 @@ def _check_capturable(model) -> None:
     test_graph_capture_of_a_sequence_parallel_forward; the development boxes have one GPU).  RCCL kernels of several ranks inside
     graphs that the ranks replay in lockstep are untested, so world_size > 1 is refused unless ``WAN_SP_GRAPH_MULTI_RANK=1`` opts in
     (for whoever has two GPUs to run the check on).  A communicator that was captured once is deliberately NOT destroyed by
-    wan_sp_destroy (the graphs hold its RCCL kernels); it lives until the process exits."""
+    wan_sp_destroy (the graphs hold its RCCL kernels); it lives until the process exits.
+    The emulated rank (``EmulatedRank``, measurement only) is admitted at any degree: it has no peers and no RCCL, and under capture its
+    copies -- the serial ``copy_`` and the concurrent mode's channel copy alike -- are nodes of the capturing stream, no side branch."""
     if model.sp_world_size != 1 or getattr(model, "force_ulysses", False):
-        from .dist import LibraryComm
+        from .dist import EmulatedRank, LibraryComm
+        if isinstance(getattr(model, "_sp", None), EmulatedRank):
+            return          # no peers: its exchanges are device-local copies, enqueued on the capturing stream itself while it is captured
         if not isinstance(getattr(model, "_sp", None), LibraryComm):
             raise NotImplementedError("graph capture of a sequence-parallel forward needs the library-owned communicator "
                                       "(init_sequence_parallel(backend=\"library\")); torch.distributed collectives stay eager")

@@ -220,6 +220,23 @@ def sp_unpack_vt(wire: torch.Tensor, vt: torch.Tensor, P: int, T: int) -> torch.
     return vt
 
 
+@_on_tensor_device
+def sp_channel_copy(dst: torch.Tensor, src: torch.Tensor, channels: int = 16, threads: int = 512) -> torch.Tensor:
+    """``wan_sp_channel_copy`` (MEASUREMENT ONLY): dst <- src, byte for byte, by a grid of exactly ``channels`` workgroups of
+    ``threads`` lanes on the current stream -- the launch footprint assumed for a collective with that many channels (include/wan_hip.h).
+    Contiguous device tensors of equal byte size, any dtypes, not overlapping."""
+    for t, name in ((dst, "sp_channel_copy.dst"), (src, "sp_channel_copy.src")):
+        if not t.is_cuda:
+            raise RuntimeError(f"{name}: tensor is on {t.device}; the HIP path has no CPU fallback")
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: must be contiguous")
+    nbytes = src.numel() * src.element_size()
+    if dst.numel() * dst.element_size() != nbytes or dst.device != src.device:
+        raise ValueError("sp_channel_copy: dst / src must hold the same number of bytes on one device")
+    _lib.check(_lib.load().wan_sp_channel_copy(_p(dst), _p(src), nbytes, int(channels), int(threads), _stream()), "wan_sp_channel_copy")
+    return dst
+
+
 def q_prescale(head_dim: int, softmax_scale: Optional[float] = None) -> float:
     """The factor q must carry for ``attention_fwd(q_prescaled=True)``: softmax_scale * log2(e)."""
     scale = softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(head_dim)
