@@ -129,7 +129,9 @@ wan_status_t wan_rmsnorm_rope(void* x0_bf16, const float* w0, void* x1_bf16, con
  *                           `x = x + y * e[2]`, `x = x + cross_attn(...)`, `x = x + y * e[5]`
  *                           (wan_transformer3d.py:499, 504, 511); gate fp32 [nbatch, N], b = m / rows_per_batch
  *       WAN_EPI_BF16_T      out bf16 [N, ldo] TRANSPOSED: out[n, m] = acc + bias  (V^T for the
- *                           attention kernel; ldo >= M, ldo % 8 == 0)
+ *                           attention kernel; ldo >= M, ldo % 4 == 0).  Columns [M, ldo) of every row are
+ *                           NOT written by any kernel family: a caller that hands the result to
+ *                           wan_attention_fwd zeroes [M, roundup(M, 64)) once (that kernel needs them finite)
  * ------------------------------------------------------------------------- */
 typedef enum {
     WAN_EPI_BF16 = 0,
