@@ -624,6 +624,27 @@ wan_status_t wan_frames_u8_to_video(const void* frames_u8, void* out, int out_dt
 wan_status_t wan_video_to_frames_u8(const void* video, int in_dtype, void* frames_u8, int B, int T, int H, int W,
                                     int t0, int nt, int T_out, int t_dst, void* stream);
 
+/* Fit a clip to another size: resample (antialiased triangle) and crop uint8 [B, T, H, W, 3] -> uint8 [B, T, Ho, Wo, 3] in one launch.
+ * replaces: nothing in the reference's inference path, which hands the clip's own size to the pipeline (fast_infer.py:409-423), so its
+ *           users resize per frame on the host; the geometry is the training loader's resize and centre crop
+ *           (videox_fun/data/dataset_image_video.py:464-477), the filter Pillow's 8-bit BILINEAR resample, whose support widens with
+ *           the downscale factor.
+ * Two separable passes over bytes, horizontal first, the intermediate rounded to a byte; per axis and output index i
+ *     out[i] = min(255, (2^21 + sum_{j < n[i]} in[xmin[i] + j] * k[i][j]) >> 22)           (32-bit integers, k >= 0, sum_j k = 2^22)
+ * xtab / ytab: one table per axis in device memory, for the Wo / Ho output indices that are produced (a crop only selects them):
+ *     int32 xmin[n_out] | int32 n[n_out] | int32 k[n_out][taps]       (taps = kx / ky = the axis' largest n, k zero from n[i] on)
+ *     = wan_frames_resample_table_bytes(n_out, taps) bytes.  The host builds them in float64 (videocof_amd/video_io.py,
+ *     resample_axis_table); the kernel does no floating point.  Windows are clamped to the source and to the tile's staging, so a
+ *     malformed table gives wrong bytes, never an access outside the tensors.
+ * taps <= WAN_RESAMPLE_MAX_TAPS per axis (24: a downscale of about 11x; 8x needs 17, 19 at a border) -> else WAN_ERR_UNSUPPORTED;
+ * B * T <= 65535 -> else WAN_ERR_UNSUPPORTED; a frame below 2 GiB.  Any H, W, Ho, Wo and any alignment: source rows are read with
+ * 16-byte loads from the 16-byte boundary below their first byte, output pieces are stored as dwordx4 where their address allows.
+ * Enqueues one kernel on `stream`; never synchronises. */
+#define WAN_RESAMPLE_MAX_TAPS 24
+int64_t wan_frames_resample_table_bytes(int n_out, int taps);
+wan_status_t wan_frames_u8_resample(const void* src_u8, void* dst_u8, int B, int T, int H, int W, int Ho, int Wo,
+                                    const void* xtab, int kx, const void* ytab, int ky, void* stream);
+
 /* ===========================================================================
  * the umT5 text encoder (videox_fun/models/wan_text_encoder.py:256-304), the step
  * before the denoising path.  Its Linear layers are wan_gemm_bf16; the rest:

@@ -970,6 +970,30 @@ def video_to_frames_u8(video: torch.Tensor, out: Optional[torch.Tensor] = None, 
 
 
 @_on_tensor_device
+def frames_u8_resample(frames: torch.Tensor, out_height: int, out_width: int, xtab: torch.Tensor, kx: int, ytab: torch.Tensor,
+                       ky: int) -> torch.Tensor:
+    """uint8 [B,T,H,W,3] -> uint8 [B,T,out_height,out_width,3]: the integer antialiased-triangle resample and crop of
+    ``wan_frames_u8_resample``.  ``xtab`` / ``ytab``: the int32 device tables of include/wan_hip.h for ``out_width`` / ``out_height``
+    output indices with ``kx`` / ``ky`` taps (video_io.resample_axis_table builds them)."""
+    _need(frames, torch.uint8, "frames_u8_resample.frames")
+    if frames.dim() != 5 or frames.shape[-1] != 3:
+        raise ValueError(f"frames_u8_resample.frames: expected [B, T, H, W, 3], got {tuple(frames.shape)}")
+    frames = frames.contiguous()
+    B, T, H, W, _ = frames.shape
+    lib = _lib.load()
+    for name, tab, n_out, k in (("xtab", xtab, out_width, kx), ("ytab", ytab, out_height, ky)):
+        _need(tab, torch.int32, f"frames_u8_resample.{name}")
+        if tab.device != frames.device or not tab.is_contiguous() or \
+                tab.numel() * 4 != lib.wan_frames_resample_table_bytes(int(n_out), int(k)):
+            raise ValueError(f"frames_u8_resample.{name}: expected {n_out} * (2 + {k}) contiguous int32 on {frames.device}, got "
+                             f"{tuple(tab.shape)} on {tab.device}")
+    out = torch.empty(B, T, int(out_height), int(out_width), 3, device=frames.device, dtype=torch.uint8)
+    _lib.check(lib.wan_frames_u8_resample(_p(frames), _p(out), B, T, H, W, int(out_height), int(out_width), _p(xtab), int(kx),
+                                          _p(ytab), int(ky), _stream()), "wan_frames_u8_resample")
+    return out
+
+
+@_on_tensor_device
 def lincomb(terms, out_dtype: torch.dtype) -> torch.Tensor:
     """sum_i c_i * x_i over <= 4 same-shape CUDA tensors in one pass (fp32 accumulate); `terms` is a list
     of (coefficient, tensor).  Inputs are brought to `out_dtype` (fp32 or bf16) if they differ."""

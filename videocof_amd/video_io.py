@@ -12,9 +12,20 @@ What the reference's command line does on the host on both sides of its pipeline
 ``frames_to_video`` / ``video_to_frames`` take device tensors only (a CPU tensor raises, like every op).  The two
 ``reference_*`` functions restate the reference's host arithmetic in torch, op for op; they are what the kernels are tested
 against (tests/test_video_io_host.py pins them to the reference itself) and are never called by the product path.
+
+Any clip in, same-size clip out: the reference's command line passes the clip's own size straight through (fast_infer.py:409-423),
+so a clip that is no multiple of 16 in the latent's terms, or far larger than what the checkpoints were trained at, has to be
+resized on the host first.  ``fit_size`` / ``fit_plan`` choose the size and the geometry (the training loader's resize and
+centre crop, videox_fun/data/dataset_image_video.py:464-477), ``fit_frames`` runs it on the device in bytes before
+``WanPipeline.__call__`` and ``restore_frames`` brings the edit back to the clip's size after it (``wan_frames_u8_resample``, one
+launch each).  The filter is the 8-bit antialiased triangle in integers; ``reference_fit_frames`` restates it
+in numpy and is what the kernel equals bit for bit.
 """
 from __future__ import annotations
 
+import functools
+import math
+from dataclasses import dataclass
 from typing import Optional, Tuple, Union
 
 import numpy as np
@@ -22,7 +33,11 @@ import torch
 
 from . import ops
 
-__all__ = ["frames_to_video", "video_to_frames", "load_video_frames", "reference_frames_to_video", "reference_video_to_frames"]
+__all__ = ["frames_to_video", "video_to_frames", "load_video_frames", "reference_frames_to_video", "reference_video_to_frames",
+           "fit_size", "fit_plan", "FitPlan", "fit_frames", "restore_frames", "reference_fit_frames"]
+
+COEF_BITS = 22                  # fixed-point bits of a filter coefficient: 8 + 22 bits of product and a sum of weights of 1 fit 32 bits
+MAX_TAPS = 24                   # WAN_RESAMPLE_MAX_TAPS of include/wan_hip.h: an 11x downscale
 
 
 def frames_to_video(frames_u8: torch.Tensor, dtype: torch.dtype = torch.bfloat16) -> torch.Tensor:
@@ -92,3 +107,195 @@ def load_video_frames(video: Union[str, np.ndarray, torch.Tensor], source_frames
     idx += [idx[-1]] * (source_frames - len(idx))
     out = frames[torch.as_tensor(idx, device=frames.device)].contiguous()
     return out, int(out.shape[1]), int(out.shape[2])
+
+
+# ---------------------------------------------------------------------------------------------- fit any clip to the model's grid
+def fit_size(height: int, width: int, max_area: int = 480 * 832, multiple: int = 16) -> Tuple[int, int]:
+    """The size a ``height`` x ``width`` clip is run at: its aspect ratio (up to the rounding), both sides multiples of
+    ``multiple`` (16 = the VAE's 8 x the spatial patch 2) and ``H * W <= max_area`` (the checkpoints were trained around
+    480 x 832).  A clip that already is on that grid and within the area keeps its size.
+
+    Each side is ``sqrt(max_area * ratio)`` rounded down to the grid (at least ``multiple``).  A side whose exact value lies nearer
+    to the next multiple then takes that one where the area still allows it, the longer side first: 1080 x 1920 has the exact
+    sides 473.96 x 842.60, the floors 464 x 832, and 842.60 is nearer to 848, which fits (464 x 848 <= 480 x 832) -- 480 for the
+    height then no longer does.  So no side is more than one grid step from the clip's ratio."""
+    height, width, max_area, multiple = int(height), int(width), int(max_area), int(multiple)
+    if height < 1 or width < 1 or multiple < 1 or max_area < multiple * multiple:
+        raise ValueError(f"fit_size: height={height} width={width} max_area={max_area} multiple={multiple}")
+    if height % multiple == 0 and width % multiple == 0 and height * width <= max_area:
+        return height, width
+    exact = [math.sqrt(max_area * height / width), math.sqrt(max_area * width / height)]
+    size = [max(multiple, int(math.floor(e / multiple)) * multiple) for e in exact]
+    for i in (0, 1):                        # a side held up at `multiple` (an extreme ratio) is paid for by the other one
+        size[i] = max(multiple, min(size[i], max_area // size[1 - i] // multiple * multiple))
+    for i in ((0, 1) if height > width else (1, 0)):
+        if exact[i] - size[i] > multiple / 2 and (size[i] + multiple) * size[1 - i] <= max_area:
+            size[i] += multiple
+    return size[0], size[1]
+
+
+@dataclass(frozen=True)
+class FitPlan:
+    """Resize by ``scale`` to ``new_height`` x ``new_width``, then keep ``out_height`` x ``out_width`` from ``(y0, x0)`` on.
+    ``source_window`` = ``(y, x, h, w)``: the rectangle of the original clip the fitted frame covers."""
+    height: int
+    width: int
+    out_height: int
+    out_width: int
+    scale: float
+    new_height: int
+    new_width: int
+    y0: int
+    x0: int
+    source_window: Tuple[int, int, int, int]
+
+
+def fit_plan(height: int, width: int, out_height: int, out_width: int) -> FitPlan:
+    """The training loader's resize and centre crop (videox_fun/data/dataset_image_video.py:464-477): scale so that the frame
+    covers the target in both axes, crop the centre."""
+    h, w, oh, ow = int(height), int(width), int(out_height), int(out_width)
+    if min(h, w, oh, ow) < 1:
+        raise ValueError(f"fit_plan: {h} x {w} -> {oh} x {ow}")
+    scale = max(oh / h, ow / w)
+    new_h, new_w = int(round(h * scale)), int(round(w * scale))
+    y0, x0 = max((new_h - oh) // 2, 0), max((new_w - ow) // 2, 0)
+    wy = min(max(int(round(y0 / scale)), 0), h - 1)
+    wx = min(max(int(round(x0 / scale)), 0), w - 1)
+    wh = min(max(int(round(oh / scale)), 1), h - wy)
+    ww = min(max(int(round(ow / scale)), 1), w - wx)
+    return FitPlan(h, w, oh, ow, scale, new_h, new_w, y0, x0, (wy, wx, wh, ww))
+
+
+def resample_axis_table(in_size: int, new_size: int, start: int = 0, count: Optional[int] = None):
+    """The integer filter of one axis resampled ``in_size -> new_size``, for the output indices ``[start, start + count)``:
+    ``(xmin, n, k)`` = int32 ``[count]``, ``[count]``, ``[count, taps]``.  Output ``i`` is
+    ``(2**21 + sum_j src[xmin[i] + j] * k[i, j]) >> 22`` clipped to a byte, ``j < n[i]``; ``k`` is zero from ``n[i]`` on and
+    ``taps`` = the largest ``n``.  The antialiased triangle of Pillow's 8-bit BILINEAR resample, coefficients in float64."""
+    in_size, new_size = int(in_size), int(new_size)
+    count = new_size - start if count is None else int(count)
+    if in_size < 1 or new_size < 1 or start < 0 or count < 1 or start + count > new_size:
+        raise ValueError(f"resample_axis_table: {in_size} -> {new_size}, indices [{start}, {start} + {count})")
+    scale = in_size / new_size
+    fs = max(scale, 1.0)
+    support = fs
+    xmin, ns, rows = [], [], []
+    for i in range(start, start + count):
+        center = (i + 0.5) * scale
+        lo = max(int(center - support + 0.5), 0)
+        n = min(int(center + support + 0.5), in_size) - lo
+        w = [max(0.0, 1.0 - abs((j + lo - center + 0.5) / fs)) for j in range(n)]
+        total = 0.0
+        for x in w:
+            total += x
+        if total != 0.0:
+            w = [x / total for x in w]
+        xmin.append(lo)
+        ns.append(n)
+        rows.append([int(0.5 + x * (1 << COEF_BITS)) for x in w])
+    taps = max(ns)
+    k = np.zeros((count, taps), dtype=np.int32)
+    for i, r in enumerate(rows):
+        k[i, :len(r)] = r
+    return np.asarray(xmin, dtype=np.int32), np.asarray(ns, dtype=np.int32), k
+
+
+def _resample_axis(x: np.ndarray, axis: int, table) -> np.ndarray:
+    """One pass of the definition along ``axis`` of an integer array of bytes, in int64."""
+    xmin, n, k = table
+    x = np.moveaxis(x, axis, -1)
+    idx = np.minimum(xmin[:, None].astype(np.int64) + np.arange(k.shape[1])[None, :], x.shape[-1] - 1)      # k is 0 where j >= n
+    acc = (x[..., idx] * k.astype(np.int64)).sum(-1) + (1 << (COEF_BITS - 1))
+    return np.moveaxis(np.clip(acc >> COEF_BITS, 0, 255), -1, axis)
+
+
+def reference_fit_frames(frames_u8, out_height: int, out_width: int, plan: Optional[FitPlan] = None) -> torch.Tensor:
+    """The definition of the fit in numpy on the host: uint8 ``[..., H, W, 3]`` -> ``[..., out_height, out_width, 3]``.  Two
+    separable passes, horizontal first, the intermediate rounded to a byte; with ``plan`` unset the plan is ``fit_plan`` of the
+    two sizes (a ``FitPlan`` without a crop, as ``restore_frames`` uses, resizes straight to the target)."""
+    x = torch.as_tensor(frames_u8)
+    if x.dtype != torch.uint8 or x.dim() < 3 or x.shape[-1] != 3:
+        raise ValueError(f"reference_fit_frames: expected uint8 [..., H, W, 3], got {x.dtype} {tuple(x.shape)}")
+    h, w = int(x.shape[-3]), int(x.shape[-2])
+    plan = fit_plan(h, w, out_height, out_width) if plan is None else plan
+    a = x.cpu().numpy().astype(np.int64)
+    a = _resample_axis(a, -2, resample_axis_table(w, plan.new_width, plan.x0, plan.out_width))
+    a = _resample_axis(a, -3, resample_axis_table(h, plan.new_height, plan.y0, plan.out_height))
+    return torch.from_numpy(np.ascontiguousarray(a.astype(np.uint8)))
+
+
+def _resize_plan(height: int, width: int, out_height: int, out_width: int) -> FitPlan:
+    """A plain resize to the target, no crop (``restore_frames``)."""
+    return FitPlan(height, width, out_height, out_width, max(out_height / height, out_width / width), out_height, out_width, 0, 0,
+                   (0, 0, height, width))
+
+
+@functools.lru_cache(maxsize=32)
+def _device_table(in_size: int, new_size: int, start: int, count: int, device: str):
+    """One axis' table as ``wan_frames_u8_resample`` reads it (include/wan_hip.h): int32 ``xmin[count]``, ``n[count]``,
+    ``k[count][taps]``; built once per geometry and device."""
+    xmin, n, k = resample_axis_table(in_size, new_size, start, count)
+    if k.shape[1] > MAX_TAPS:
+        raise RuntimeError(f"resample {in_size} -> {new_size}: {k.shape[1]} filter taps; the kernel is built for {MAX_TAPS} "
+                           f"(a downscale of about {MAX_TAPS // 2 - 1}x)")
+    packed = torch.from_numpy(np.concatenate([xmin, n, k.ravel()]))
+    return packed.to(device), int(k.shape[1])
+
+
+def _resample(frames: torch.Tensor, plan: FitPlan) -> torch.Tensor:
+    dev = str(frames.device)
+    xtab, kx = _device_table(plan.width, plan.new_width, plan.x0, plan.out_width, dev)
+    ytab, ky = _device_table(plan.height, plan.new_height, plan.y0, plan.out_height, dev)
+    return ops.frames_u8_resample(frames, plan.out_height, plan.out_width, xtab, kx, ytab, ky)
+
+
+def _as_clip(frames_u8, what: str) -> torch.Tensor:
+    x = torch.from_numpy(frames_u8) if isinstance(frames_u8, np.ndarray) else frames_u8
+    if not torch.is_tensor(x) or x.dtype != torch.uint8 or x.dim() not in (4, 5) or x.shape[-1] != 3:
+        raise ValueError(f"{what}: expected uint8 [T, H, W, 3] or [B, T, H, W, 3] frames, got "
+                         f"{getattr(x, 'dtype', type(x))} {tuple(getattr(x, 'shape', ()))}")
+    if not x.is_cuda:
+        x = x.to(torch.device("cuda", torch.cuda.current_device()))          # bytes over the host link, as they are
+    return x
+
+
+def fit_frames(frames_u8, height: Optional[int] = None, width: Optional[int] = None,
+               max_area: int = 480 * 832) -> Tuple[torch.Tensor, FitPlan]:
+    """Fit a clip of any size to a size the model runs at, on the device, in bytes: resize (antialiased triangle) and centre
+    crop in one launch.  ``frames_u8``: uint8 ``[T, H, W, 3]`` or ``[B, T, H, W, 3]``, host or device.  The target is
+    ``(height, width)`` or, with both unset, ``fit_size`` of the clip's size under ``max_area``.  Returns the device frames,
+    which ``WanPipeline.__call__(video=...)`` takes as they are, and the plan (``plan.out_height``, ``plan.out_width`` are the
+    ``height`` / ``width`` of that call; ``plan.source_window`` is where the result belongs in the clip).  A clip already at the
+    target is returned as it is: nothing is launched."""
+    x = _as_clip(frames_u8, "fit_frames")
+    h, w = int(x.shape[-3]), int(x.shape[-2])
+    if (height is None) != (width is None):
+        raise ValueError("fit_frames: pass both `height` and `width`, or neither")
+    oh, ow = fit_size(h, w, max_area) if height is None else (int(height), int(width))
+    plan = fit_plan(h, w, oh, ow)
+    if (oh, ow) == (h, w):
+        return x, plan
+    out = _resample(x if x.dim() == 5 else x.unsqueeze(0), plan)
+    return (out if x.dim() == 5 else out[0]), plan
+
+
+def restore_frames(frames_u8, height: int, width: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The edit back at the clip's size: the same resample without a crop, from the model's size to ``(height, width)`` (usually
+    the size of ``plan.source_window``), on the device.  ``frames_u8``: uint8 ``[T, H, W, 3]`` or ``[B, T, H, W, 3]``.  ``out``: a
+    page-locked uint8 host tensor of the result's shape, filled by one copy and returned, as
+    ``decode_latents(as_uint8=True)`` fills its ``out``; without it the device frames are returned."""
+    x = _as_clip(frames_u8, "restore_frames")
+    h, w = int(x.shape[-3]), int(x.shape[-2])
+    height, width = int(height), int(width)
+    if height < 1 or width < 1:
+        raise ValueError(f"restore_frames: height={height} width={width}")
+    res = x if (height, width) == (h, w) else _resample(x if x.dim() == 5 else x.unsqueeze(0), _resize_plan(h, w, height, width))
+    if x.dim() == 4 and res.dim() == 5:
+        res = res[0]
+    if out is None:
+        return res
+    if out.dtype != torch.uint8 or tuple(out.shape) != tuple(res.shape) or out.is_cuda or not out.is_contiguous():
+        raise ValueError(f"restore_frames: out {out.dtype} {tuple(out.shape)} on {out.device} for uint8 host frames "
+                         f"{tuple(res.shape)}")
+    out.copy_(res.contiguous(), non_blocking=True)
+    torch.cuda.current_stream(res.device).synchronize()
+    return out
