@@ -3,12 +3,13 @@ HIPCC ?= /opt/rocm/bin/hipcc
 ARCH  ?= gfx950
 CSRC  := videocof_amd/csrc
 SRCS  := $(wildcard $(CSRC)/*.cpp) $(wildcard $(CSRC)/*.hip)
-HDRS  := $(CSRC)/common.hpp include/wan_hip.h $(wildcard $(CSRC)/*.inc)
+HDRS  := $(wildcard $(CSRC)/*.hpp) include/wan_hip.h $(wildcard $(CSRC)/*.inc)
 LIB   := videocof_amd/libwan_hip.so
 OBJD  := build/obj
 OBJS  := $(patsubst $(CSRC)/%,$(OBJD)/%.o,$(SRCS))
 # -fno-honor-nans: lets fmaxf/fminf lower to one v_max/v_min (no canonicalising v_max on MFMA outputs)
-# EXPERIMENTS=1 compiles the timing-only variants behind the gemm_exp switch into the kernels (tools/kernel_check gemmx)
+# EXPERIMENTS=1 compiles the timing-only instruments behind the gemm_exp switch into the persistent GEMM (cycle stamps, forced waits:
+# tools/kernel_check gemmcyc) and the 4-phase form of the e4m3 GEMM (gemm_phases = 4)
 EXPERIMENTS ?= 0
 FLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -fno-honor-nans -Iinclude -DWAN_DEV_EXPERIMENTS=$(EXPERIMENTS)
 # attn_fwd.hip only: keep adjacent scalar f32 adds single-instruction -- under plain -O3 the SLP vectoriser packs the

@@ -148,3 +148,119 @@ def test_random_shapes_are_covered_exactly_once_property():
             assert [p[2] for p in ps] == list(range(ps[0][3], ps[0][4] + 1))
 
     check()
+
+
+def _gemm_error_table(lib):
+    """(entry, arguments, status, wan_last_error()) for one invalid call per check of the five Linear entry points.  Pointers are
+    small integers that are never dereferenced: every row is answered by host code before anything is launched."""
+    INV, UNS, OK = _lib.WAN_ERR_INVALID, _lib.WAN_ERR_UNSUPPORTED, _lib.WAN_OK
+    P, MIS = 16, 24                                   # a 16-byte aligned "pointer", and one that is only 8-byte aligned
+    rows = []
+
+    # wan_gemm_bf16(A, lda, W, ldw, bias, out, ldo, M, N, K, epilogue, gate, rows_per_batch, stream); `tail` = (workspace, bytes) of _ws.
+    # `name` answers the checks; `short_gate`: who answers a gate with rows_per_batch < 128 (the _ws entries hand it to the per-tile one)
+    def bf16(entry, name, tail, M, N, K, short_gate=None):
+        def call(A=P, lda=K, W=P, ldw=K, out=P, ldo=N, M=M, N=N, K=K, epi=0, gate=None, rpb=0):
+            return (A, lda, W, ldw, None, out, ldo, M, N, K, epi, gate, rpb) + tail + (None,)
+        add = lambda args, st, msg, who=name: rows.append((entry, args, st, f"{who}: {msg}"))
+        add(call(A=None), INV, "null tensor")
+        add(call(out=None), INV, "null tensor")
+        add(call(lda=K + 4), INV, f"lda={K + 4} ldw={K} must be multiples of 8 and >= K")
+        add(call(ldw=K - 8), INV, f"lda={K} ldw={K - 8} must be multiples of 8 and >= K")
+        add(call(ldo=N - 4), INV, f"ldo={N - 4} < N={N} or not a multiple of 4")
+        add(call(ldo=N + 2), INV, f"ldo={N + 2} < N={N} or not a multiple of 4")
+        add(call(epi=4, ldo=M - 4), INV, f"transposed ldo={M - 4} < M={M} or not a multiple of 4")
+        add(call(epi=4, ldo=M + 2), INV, f"transposed ldo={M + 2} < M={M} or not a multiple of 4")
+        add(call(gate=P, epi=2, rpb=M), INV, "gate needs WAN_EPI_RESID_F32 and rows_per_batch > 0")
+        add(call(gate=P, epi=3, rpb=0), INV, "gate needs WAN_EPI_RESID_F32 and rows_per_batch > 0", short_gate or name)
+        add(call(N=N + 2, ldo=N + 4), UNS, f"N={N + 2} must be a multiple of 4")
+        add(call(epi=7), INV, "unknown epilogue 7")
+        return call, add
+
+    # the per-tile entry; the _ws entry without a workspace and on a shape neither workspace form takes: wan_gemm_bf16 answers
+    for entry, tail in (("wan_gemm_bf16", ()), ("wan_gemm_bf16_ws", (None, 0)), ("wan_gemm_bf16_ws", (P, 1 << 20))):
+        call, add = bf16(entry, "wan_gemm_bf16", tail, 300, 64, 128)
+        add(call(M=-1), INV, "M=-1 N=64 K=128")
+        add(call(N=0, ldo=64), INV, "M=300 N=0 K=128")
+        add(call(K=96, lda=128, ldw=128), UNS, "K=96 must be a multiple of 64")
+        rows.append((entry, call(M=0), OK, None))
+    # (the 256^2 family's dispatcher)
+    rows.append(("wan_gemm_bf16", (P, 5120, P, 5120, None, P, 5120, 67080, 5120, 5120, -1, None, 0, None), INV, "wan_gemm_bf16: unknown epilogue -1"))
+    # a split-K shape with a workspace that holds the pieces: still wan_gemm_bf16's checks and the 128^2 family's dispatcher
+    M, N, K = 2304, 1536, 8960
+    bf16("wan_gemm_bf16_ws", "wan_gemm_bf16", (P, int(lib.wan_gemm_workspace_bytes(M, N, K))), M, N, K)
+    # a persistent-plan shape: the _ws entry's own checks, then its workspace
+    M, N, K = 67080, 5120, 5120
+    need = int(lib.wan_gemm_workspace_bytes(M, N, K))
+    call, add = bf16("wan_gemm_bf16_ws", "wan_gemm_bf16_ws", (P, need), M, N, K, short_gate="wan_gemm_bf16")
+    add(call()[:-3] + (P, need - 1, None), INV, f"workspace of {need - 1} bytes, wan_gemm_workspace_bytes({M}, {N}, {K}) = {need}")
+    add(call()[:-3] + (MIS, need, None), INV, "workspace must be 16-byte aligned")
+
+    # wan_gemm_fp8(A, lda, sa, W, ldw, sw, bias, out, ldo, M, N, K, epilogue, gate, rows_per_batch, stream)
+    def fp8(entry, name, tail, M, N, K, short_gate=None):
+        def call(A=P, lda=K, sa=P, W=P, ldw=K, sw=P, out=P, ldo=N, M=M, N=N, K=K, epi=0, gate=None, rpb=0):
+            return (A, lda, sa, W, ldw, sw, None, out, ldo, M, N, K, epi, gate, rpb) + tail + (None,)
+        add = lambda args, st, msg, who=name: rows.append((entry, args, st, f"{who}: {msg}"))
+        add(call(W=None), INV, "null tensor")
+        add(call(sa=None), INV, "null tensor")
+        add(call(sw=None), INV, "null tensor")
+        add(call(lda=K + 8), INV, f"lda={K + 8} ldw={K} must be multiples of 16 and >= K")
+        add(call(ldw=K - 16), INV, f"lda={K} ldw={K - 16} must be multiples of 16 and >= K")
+        add(call(ldo=N - 4), INV, f"ldo={N - 4} < N={N} or not a multiple of 4")
+        add(call(ldo=N + 2), INV, f"ldo={N + 2} < N={N} or not a multiple of 4")
+        add(call(epi=4, ldo=M - 4), INV, f"transposed ldo={M - 4} < M={M} or not a multiple of 4")
+        add(call(epi=4, ldo=M + 2), INV, f"transposed ldo={M + 2} < M={M} or not a multiple of 4")
+        add(call(gate=P, epi=0, rpb=M), INV, "gate needs WAN_EPI_RESID_F32 and rows_per_batch > 0")
+        add(call(gate=P, epi=3, rpb=-1), INV, "gate needs WAN_EPI_RESID_F32 and rows_per_batch > 0", short_gate or name)
+        add(call(N=N + 2, ldo=N + 4), UNS, f"N={N + 2} must be a multiple of 4")
+        add(call(epi=5), INV, "unknown epilogue 5")
+        return call, add
+
+    for entry, tail in (("wan_gemm_fp8", ()), ("wan_gemm_fp8_ws", (None, 0)), ("wan_gemm_fp8_ws", (P, 1 << 20))):
+        call, add = fp8(entry, "wan_gemm_fp8", tail, 300, 64, 256)
+        add(call(M=-2), INV, "M=-2 N=64 K=256")
+        add(call(K=192), UNS, "K=192 must be a multiple of 128")
+        rows.append((entry, call(M=0), OK, None))
+    M, N, K = 67080, 5120, 5120
+    need = int(lib.wan_gemm_fp8_workspace_bytes(M, N, K))
+    call, add = fp8("wan_gemm_fp8_ws", "wan_gemm_fp8_ws", (P, need), M, N, K, short_gate="wan_gemm_fp8")
+    add(call(sw=MIS), INV, "w_row_scale must be 16-byte aligned")
+    add(call()[:-3] + (P, need - 16, None), INV, f"workspace of {need - 16} bytes, wan_gemm_fp8_workspace_bytes({M}, {N}, {K}) = {need}")
+    add(call()[:-3] + (MIS, need, None), INV, "workspace must be 16-byte aligned")
+
+    # wan_gemm_bf16_batched(A, lda, strideA, W, ldw, strideW, out, ldo, strideO, M, N, K, batch, epilogue, stream)
+    def bat(A=P, lda=128, sA=1024, W=P, ldw=128, sW=1024, out=P, ldo=64, sO=1024, M=8, N=64, K=128, batch=3, epi=0):
+        return (A, lda, sA, W, ldw, sW, out, ldo, sO, M, N, K, batch, epi, None)
+    add = lambda args, st, msg: rows.append(("wan_gemm_bf16_batched", args, st, "wan_gemm_bf16_batched: " + msg))
+    add(bat(W=None), INV, "null tensor")
+    add(bat(M=-1), INV, "M=-1 N=64 K=128 batch=3")
+    add(bat(batch=65536), INV, "M=8 N=64 K=128 batch=65536")
+    add(bat(K=96), UNS, "K=96 % 64 and N=64 % 4 must be 0")
+    add(bat(N=62), UNS, "K=128 % 64 and N=62 % 4 must be 0")
+    add(bat(lda=132), INV, "lda=132 ldw=128 strideA=1024 strideW=1024 must be multiples of 8, ld >= K")
+    add(bat(ldw=64), INV, "lda=128 ldw=64 strideA=1024 strideW=1024 must be multiples of 8, ld >= K")
+    add(bat(sA=1028), INV, "lda=128 ldw=128 strideA=1028 strideW=1024 must be multiples of 8, ld >= K")
+    add(bat(sW=4), INV, "lda=128 ldw=128 strideA=1024 strideW=4 must be multiples of 8, ld >= K")
+    add(bat(ldo=60), INV, "ldo=60 strideO=1024")
+    add(bat(ldo=66), INV, "ldo=66 strideO=1024")
+    add(bat(sO=1026), INV, "ldo=64 strideO=1026")
+    add(bat(epi=1), UNS, "epilogue 1 (only WAN_EPI_BF16 / WAN_EPI_F32)")
+    add(bat(epi=4), UNS, "epilogue 4 (only WAN_EPI_BF16 / WAN_EPI_F32)")
+    rows.append(("wan_gemm_bf16_batched", bat(M=0), OK, None))
+    rows.append(("wan_gemm_bf16_batched", bat(batch=0), OK, None))
+    return rows
+
+
+def test_linear_entry_points_reject_invalid_calls_with_their_messages():
+    """The host contract of wan_gemm_bf16 / _ws / _batched and wan_gemm_fp8 / _ws: status code and the full wan_last_error() text of
+    every argument check -- whichever file the check lives in -- and WAN_OK for M == 0 (nothing to launch)."""
+    lib = _lib.load()
+    assert lib.wan_gemm_ws_plan(67080, 5120, 5120) == 3 == lib.wan_gemm_fp8_ws_plan(67080, 5120, 5120)      # the persistent-plan rows
+    assert lib.wan_gemm_ws_splits(2304, 1536, 8960) == 2 and lib.wan_gemm_ws_plan(300, 64, 128) == 0
+    rows = _gemm_error_table(lib)
+    assert len(rows) > 120
+    for entry, args, status, message in rows:
+        got = getattr(lib, entry)(*args)
+        assert got == status, (entry, args, got, lib.wan_last_error())
+        if message is not None:
+            assert lib.wan_last_error().decode() == message, (entry, args)

@@ -482,28 +482,6 @@ int main(int argc, char** argv) {
     }
     if (mode == "gemm") { check_gemm(); printf("%s (%d failures)\n", g_fail ? "CHECK FAILED" : "ALL CHECKS PASSED", g_fail); perf(big, false, true); }
     if (mode == "attn") { check_attn(); printf("%s (%d failures)\n", g_fail ? "CHECK FAILED" : "ALL CHECKS PASSED", g_fail); perf(big, true); }
-    if (mode == "gemmx") {        // timing attribution of the 4-wave GEMM's main loop: with / without its LDS-DMA instructions
-        if (wan_get_tuning("dev_experiments") != 1) printf("  NOTE: libwan_hip.so was built without the experiment variants (make clean; make EXPERIMENTS=1): every arm below is the product kernel\n");
-        const int M = 67080;
-        struct S { int N, K, epi; const char* what; };
-        for (S sh : {S{10240, 5120, WAN_EPI_BF16, "qk proj"}, S{5120, 13824, WAN_EPI_RESID_F32, "ffn.2+resid"}}) {
-            auto hA = to_bf(randn((size_t)4096 * 64));
-            Dev<bf16> A((size_t)M * sh.K), W((size_t)sh.N * sh.K);
-            for (size_t off = 0; off < A.n; off += hA.size()) HIP(hipMemcpy(A.p + off, hA.data(), std::min(hA.size(), A.n - off) * 2, hipMemcpyHostToDevice));
-            for (size_t off = 0; off < W.n; off += hA.size()) HIP(hipMemcpy(W.p + off, hA.data(), std::min(hA.size(), W.n - off) * 2, hipMemcpyHostToDevice));
-            Dev<float> bias(sh.N), gate(sh.N); bias.zero(); gate.zero();
-            Dev<char> out((size_t)M * sh.N * 4); out.zero();
-            for (int round = 0; round < 2; ++round)
-                for (int e : {0, 16, 4, 1, 9, 3}) {
-                    WAN(wan_set_tuning("gemm_exp", e));
-                    double ms = time_ms([&] { WAN(wan_gemm_bf16(A.p, sh.K, W.p, sh.K, bias.p, out.p, sh.N, M, sh.N, sh.K, sh.epi,
-                                                                sh.epi == WAN_EPI_RESID_F32 ? gate.p : nullptr, M, nullptr)); }, 3, 1);
-                    printf("  gemmx[%-12s gemm_exp=%d (%s)] %.3f ms  %.0f TFLOP/s\n", sh.what, e, e == 0 ? "product" : e == 16 ? "W tile requested one k-step earlier" : e == 4 ? "all DMA, cache-resident source" : e == 1 ? "no W DMA" : e == 9 ? "W bytes by register loads, discarded" : "no DMA at all",
-                           ms, 2.0 * M * sh.N * sh.K / ms / 1e9);
-                }
-            WAN(wan_set_tuning("gemm_exp", 0));
-        }
-    }
     if (mode == "gemmpk") {       // the persistent stream-K GEMM (wan_gemm_bf16_ws): numerics vs the one-tile-per-workgroup kernels, repro, in-process A/B
         WAN(wan_set_tuning("gemm_pk", 2));
         for (int i = 2; i < argc; ++i) {                       // extra "key=value" tuning arguments
@@ -716,37 +694,6 @@ int main(int argc, char** argv) {
             WAN(wan_attention_fwd(q.p, C, 0, k.p, C, 0, vt.p, ldvt, 0, o.p, C, 0, 1, L, L, H, 128, 0.0883883f, WAN_ATTN_Q_PRESCALED, wsb ? ws.p : nullptr, wsb, nullptr));
         HIP(hipDeviceSynchronize());
         printf("attnprof done\n");
-    }
-    if (mode == "gemmring") {     // the four-stage-ring form of the 4-wave GEMM: numerics under every epilogue, then in-process A/B on the 14B shapes
-        if (wan_get_tuning("dev_experiments") != 1) { printf("gemmring needs a `make EXPERIMENTS=1` build\n"); return 2; }
-        WAN(wan_set_tuning("gemm_ring", 1));
-        check_gemm();
-        printf("%s (%d failures)\n", g_fail ? "CHECK FAILED" : "ALL CHECKS PASSED", g_fail);
-        const int L = 67080;
-        struct G { int M, N, K; int epi; const char* what; };
-        std::vector<G> gs = {{L, 5120, 5120, WAN_EPI_BF16, "14B o/q proj"}, {L, 10240, 5120, WAN_EPI_BF16, "14B qk proj"},
-                             {L, 13824, 5120, WAN_EPI_GELU_BF16, "14B ffn.0+gelu"}, {L, 5120, 13824, WAN_EPI_RESID_F32, "14B ffn.2+resid"},
-                             {L, 5120, 5120, WAN_EPI_RESID_F32, "14B o+resid"}, {L, 5120, 5120, WAN_EPI_BF16_T, "14B v proj (T)"},
-                             {8392, 5120, 13824, WAN_EPI_RESID_F32, "14B ffn.2, SP8 shard"}};
-        WAN(wan_set_tuning("gemm_variant", 2)); WAN(wan_set_tuning("gemm_w4", 3));
-        for (auto g : gs) {
-            auto hA = to_bf(randn((size_t)4096 * 64));
-            Dev<bf16> A((size_t)g.M * g.K), W((size_t)g.N * g.K);
-            for (size_t off = 0; off < A.n; off += hA.size()) HIP(hipMemcpy(A.p + off, hA.data(), std::min(hA.size(), A.n - off) * 2, hipMemcpyHostToDevice));
-            for (size_t off = 0; off < W.n; off += hA.size()) HIP(hipMemcpy(W.p + off, hA.data(), std::min(hA.size(), W.n - off) * 2, hipMemcpyHostToDevice));
-            Dev<float> bias(g.N), gate(g.N); bias.zero(); gate.zero();
-            const int64_t ldo = g.epi == WAN_EPI_BF16_T ? (g.M + 63) / 64 * 64 : g.N;
-            const size_t osz = (size_t)(g.epi == WAN_EPI_BF16_T ? g.N : g.M) * ldo * ((g.epi == WAN_EPI_F32 || g.epi == WAN_EPI_RESID_F32) ? 4 : 2);
-            Dev<char> out(osz); out.zero();
-            for (int round = 0; round < 2; ++round)
-            for (int ring = 0; ring < 2; ++ring) {
-                WAN(wan_set_tuning("gemm_ring", ring));
-                double ms = time_ms([&] { WAN(wan_gemm_bf16(A.p, g.K, W.p, g.K, bias.p, out.p, ldo, g.M, g.N, g.K, g.epi,
-                                                            g.epi == WAN_EPI_RESID_F32 ? gate.p : nullptr, g.M, nullptr)); }, 3, 1);
-                printf("  gemm[%s] %-20s M=%d N=%d K=%d: %.3f ms  %.0f TFLOP/s\n", ring ? "ring 4x32" : "2 x 64  ", g.what, g.M, g.N, g.K, ms, 2.0 * g.M * g.N * g.K / ms / 1e9);
-                fflush(stdout);
-            }
-        }
     }
     if (mode == "attnq8") {       // wan_attention_fwd_qk8: exactness against its own (quantised) operands, error against the bf16 operands, speed
         // usage: kernel_check attnq8 [q_exp k_exp]

@@ -67,8 +67,7 @@ const TuningKey kTuningKeys[WAN_TUNE_COUNT] = {
     {"conv_patch", "WAN_CONV_PATCH", 1},        // causal 3x3x3 stride-1 convs with Cout % 96 == 0 on the LDS-patch kernel (0 = the gather kernel)
     {"attn_ref", "WAN_ATTN_REF", 1},            // lazy softmax reference of the 4-wave kernel: 1 = -m splat in the accumulator, 2 = packed subtract
     {"conv_head", "WAN_CONV_HEAD", 1},          // causal 3x3x3 convs with <= 4 output channels on the direct (vector-ALU) kernel (0 = the gather kernel)
-    {"gemm_exp", "WAN_GEMM_EXP", 0},            // TIMING-ONLY experiment of the 4-wave GEMM: bit 0 / 1 = skip the W / A tile DMA of the main loop (results are garbage)
-    {"gemm_ring", "WAN_GEMM_RING", 0},          // `make EXPERIMENTS=1` builds only: 4-wave GEMM over a four-stage ring of 32-k tiles (measured 5-9 % slower than two 64-k stages)
+    {"gemm_exp", "WAN_GEMM_EXP", 0},            // `make EXPERIMENTS=1` builds only, TIMING ONLY: instruments of the persistent GEMM (bit 5 = no epilogue, bit 6 = cycle stamps, ...: gemm_bf16_pk.hip; tools/kernel_check gemmcyc)
     {"gemm_pk", "WAN_GEMM_PK", 1},              // persistent stream-K form of the 4-wave 256^2 GEMM for callers that bring a workspace: 0 never, 1 where the 4-wave kernel would run, 2 whenever K % 128 == 0
     {"gemm_pk_workers", "WAN_GEMM_PK_WORKERS", 0},      // its grid (0 = one workgroup per CU); developer A/B
     {"gemm_pk_min_units", "WAN_GEMM_PK_MIN_UNITS", 0},  // smallest stream-K range in units of two K tiles (0 = a quarter of the tile's K range)
@@ -114,7 +113,7 @@ extern "C" wan_status_t wan_set_tuning(const char* key, int value) {
 
 extern "C" int wan_get_tuning(const char* key) {
     if (key && !strcmp(key, "last_attn_variant")) return g_last_attn_variant.load(std::memory_order_relaxed);
-    if (key && !strcmp(key, "dev_experiments")) return WAN_DEV_EXPERIMENTS;      // 1: built with `make EXPERIMENTS=1` (gemm_exp variants compiled in)
+    if (key && !strcmp(key, "dev_experiments")) return WAN_DEV_EXPERIMENTS;      // 1: built with `make EXPERIMENTS=1` (the gemm_exp instruments of the persistent GEMM compiled in)
     if (key)
         for (int i = 0; i < WAN_TUNE_COUNT; ++i)
             if (!strcmp(key, kTuningKeys[i].key)) return wan_tune(i);

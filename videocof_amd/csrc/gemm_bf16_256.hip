@@ -26,11 +26,7 @@
 // o-projection, 1165 vs 1165-1170 on ffn.2 -- noise; the CUs drift apart on their own.  The same wave tile computed
 // with v_mfma_f32_32x32x16_bf16 (4 x 2 tiles, half the MFMA instructions, same LDS traffic): 5-8 % SLOWER on every
 // shape (profiles/r01/gemm_mfma32x32_ab.log).
-#include <stdlib.h>
-
-#include <type_traits>
-
-#include "common.hpp"
+#include "gemm_common.hpp"
 
 #ifndef WAN_DEV_EXPERIMENTS
 #define WAN_DEV_EXPERIMENTS 0
@@ -58,24 +54,7 @@ struct GemmArgs {
     // FP8 instantiation (wan_gemm_fp8): A / W point at e4m3 bytes, lda / ldw count bytes = elements; the product of the
     // quantised operands is scaled by sa[m] * sw[n] (per-token, per-output-channel) before bias and epilogue
     const float* sa; const float* sw;
-    int exp;              // developer experiment (gemm_exp), TIMING ONLY: bit 0 / bit 1 = the 4-wave kernel's main loop skips its W / A tile DMA, bit 2 = every DMA reads K tile 0 / 1 (cache hits), bit 3 (with bit 0) = the W bytes are fetched by plain register loads instead
 };
-
-__device__ __forceinline__ void tile_coords(const GemmArgs& g, int& tm, int& tn) {
-    const int nwg = g.tiles_m * g.tiles_n;
-    const int bid = blockIdx.x;
-    const int xcd = bid & 7, loc = bid >> 3;
-    const int q = nwg >> 3, r = nwg & 7;
-    const int t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
-    const int GM = g.gm;                     // GM M tiles x all N tiles per group: the 32 CUs of an XCD share GM A panels
-    const int per_group = GM * g.tiles_n;
-    const int grp = t / per_group;
-    const int first_m = grp * GM;
-    const int gm = min(GM, g.tiles_m - first_m);
-    const int in = t - grp * per_group;
-    tm = first_m + in % gm;
-    tn = in / gm;
-}
 
 #define WAIT_LGKM0() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
 #define WAIT_VM0() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
@@ -96,7 +75,7 @@ __global__ __launch_bounds__(kThreads, 2) void gemm256_kernel(GemmArgs g) {
     constexpr int kTileK = FP8 ? 2 * BK : BK;        // elements per K tile (128 bytes either way)
 
     int tm, tn;
-    tile_coords(g, tm, tn);
+    wan_tile_coords(blockIdx.x, g.gm, g.tiles_m, g.tiles_n, tm, tn);
     const int m0 = tm * BM, n0 = tn * BN;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -427,23 +406,17 @@ constexpr int kW4Threads = 256;
 
 __device__ __forceinline__ u32x4 lds16(const char* p) { return *reinterpret_cast<const u32x4*>(p); }
 
-// RING (round 3): the same wave tiles, MFMA order and epilogues over a FOUR-stage LDS ring of 256 x 32-k tiles (4 x 32 KiB, rows of
-// 64 B, chunk' = chunk ^ ((row >> 2) & 3)) instead of two stages of 64 k.  Why: a K tile's 64 KB come through the CU's
-// vector-memory path at 64 B/clk -- half of the tile's MFMA time -- and the two-stage form has to bunch its 16 requests per wave into
-// 2 of 4 k-steps (they must land before the next barrier), at twice the sustainable rate, with ~1 us of flight time.  Here every
-// k-step carries 4 requests (one per 4 MFMA slots), and a request has 2-3 tiles (>= 2048 MFMA cycles) to land: tile t+4's A pieces
-// leave in k-step 1 of tile t (right behind the barrier that frees stage t % 4), its W pieces in k-step 0 of tile t+1; the barrier
-// in the middle of tile t waits (counted vmcnt) for tile t+1 only.  Price: one barrier per 32 MFMA slots instead of per 64, and
-// 64-byte instead of 128-byte row segments per request.  MEASURED (profiles/r03/gemm_ring_ab.log, in process, numerics green under
-// every epilogue): 5-9 % SLOWER on every 14B shape (q|k 1202 vs 1308, ffn.0 1222 vs 1307, ffn.2 1128 vs 1231, o 1219 vs 1285
-// TFLOP/s) -- flight time and request spacing are not what the two-stage form is short of.  Compiled only with `make EXPERIMENTS=1`
-// ("gemm_ring" = 1), like the gemm_exp variants.
-template <int EPI, bool RING = false>
+// Measured and not kept (round 3): the same wave tiles over a FOUR-stage LDS ring of 256 x 32-k tiles, so that every k-step carries
+// four requests with 2-3 tiles of flight time, at the price of a barrier per 32 MFMA slots and 64-byte row segments: 5-9 % SLOWER
+// on every 14B shape (profiles/r03/gemm_ring_ab.log) -- flight time and request spacing are not what the two-stage form is short
+// of.  (What its tile fetch path costs this main loop -- timed with the DMA skipped, fed from cache, replaced by register loads -- is
+// recorded in profiles/r03/gemm_w4_dma_attribution.log)
+template <int EPI>
 __global__ __launch_bounds__(kW4Threads) __attribute__((amdgpu_waves_per_eu(1, 1))) void gemm_w4_kernel(GemmArgs g) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr bool kTransposed = (EPI == WAN_EPI_BF16_T);
     int tm, tn;
-    tile_coords(g, tm, tn);
+    wan_tile_coords(blockIdx.x, g.gm, g.tiles_m, g.tiles_n, tm, tn);
     const int m0 = tm * BM, n0 = tn * BN;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -469,23 +442,9 @@ __global__ __launch_bounds__(kW4Threads) __attribute__((amdgpu_waves_per_eu(1, 1
     const int64_t w_bytes = ((int64_t)(min(g.N - n0, BN) - 1) * g.ldw + g.K) * 2;
     auto rsrc = [&](const char* tile, int64_t bytes, int kt) {
         const int64_t left = kt < nk ? bytes - (int64_t)kt * BK * 2 : 0;
-#if WAN_DEV_EXPERIMENTS
-        const int ke = (g.exp & 4) ? (min(kt, nk - 1) & 1) : min(kt, nk - 1);      // every request hits K tiles 0 / 1 (cache-resident)
-#else
-        const int ke = min(kt, nk - 1);
-#endif
-        return __builtin_amdgcn_make_buffer_rsrc((void*)(tile + (int64_t)ke * BK * 2), 0, (int)min(left, (int64_t)0x7fffffff), 0x00020000);
+        return __builtin_amdgcn_make_buffer_rsrc((void*)(tile + (int64_t)min(kt, nk - 1) * BK * 2), 0, (int)min(left, (int64_t)0x7fffffff), 0x00020000);
     };
     auto stage_piece = [&](__amdgpu_buffer_rsrc_t r, int buf, int operand, int j, int64_t ld) {
-#if WAN_DEV_EXPERIMENTS     // `make EXPERIMENTS=1`: timing-only variants behind gemm_exp (tools/kernel_check gemmx); not in the product build
-        if (g.exp & (operand ? 1 : 2)) {                // what the DMA instructions cost the lone wave of a SIMD
-            if ((g.exp & 8) && operand) {               // ... and what the same bytes cost as plain register loads (results discarded)
-                u32x4 sink;
-                asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen" : "=a"(sink) : "v"(w_voff[j & 1]), "s"(r), "s"((int)((j >> 1) * 16 * ld * 2)));
-            }
-            return;
-        }
-#endif
         __builtin_amdgcn_raw_ptr_buffer_load_lds(
             r, (__attribute__((address_space(3))) void*)(smem + buf * kBufBytes + operand * kOperandBytes + (wid * 8 + j) * 1024), 16,
             operand ? w_voff[j & 1] : a_voff[j & 1], (int)((j >> 1) * 16 * ld * 2), 0, 0);
@@ -500,32 +459,6 @@ __global__ __launch_bounds__(kW4Threads) __attribute__((amdgpu_waves_per_eu(1, 1
         for (int s4 = 0; s4 < 4; ++s4) koff[b][s4] = b * kBufBytes + l31 * 128 + (((2 * s4 + hi) ^ sw) << 4);
     const int a_base = wr * 128 * 128, w_base = kOperandBytes + wc * 128 * 128;
 
-    // ---- RING form: staging and fragment addresses of the 32-k stages
-    constexpr int kStageBytes = 32768, kRingOperand = 16384;
-    int ra_voff = 0, rw_voff = 0;            // piece j of wave w = rows 64 w + 16 j + lane / 4 (64-B rows), LDS chunk lane & 3 <- source chunk
-    int rkoff[4][2];                         // [stage][k-step]
-    if constexpr (RING) {
-        const int row = wid * 64 + (lane >> 2);
-        const int c = (lane & 3) ^ ((lane >> 4) & 3);          // (row >> 2) & 3 == (lane >> 4) & 3 for every piece
-        ra_voff = (int)(((int64_t)row * g.lda + c * 8) * 2);
-        rw_voff = (int)(((int64_t)row * g.ldw + c * 8) * 2);
-#pragma unroll
-        for (int st = 0; st < 4; ++st)
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) rkoff[st][ks] = st * kStageBytes + l31 * 64 + (((2 * ks + hi) ^ ((l31 >> 2) & 3)) << 4);
-    }
-    const int nk32 = g.K / 32;
-    auto rsrc32 = [&](const char* tile, int64_t bytes, int kt) {
-        const int64_t left = kt < nk32 ? bytes - (int64_t)kt * 64 : 0;
-        return __builtin_amdgcn_make_buffer_rsrc((void*)(tile + (int64_t)min(kt, nk32 - 1) * 64), 0, (int)min(left, (int64_t)0x7fffffff), 0x00020000);
-    };
-    auto stage_piece32 = [&](__amdgpu_buffer_rsrc_t r, int stage, int operand, int j, int64_t ld) {
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(
-            r, (__attribute__((address_space(3))) void*)(smem + stage * kStageBytes + operand * kRingOperand + (wid * 4 + j) * 1024), 16,
-            operand ? rw_voff : ra_voff, (int)(j * 16 * ld * 2), 0, 0);
-    };
-    const int ra_base = wr * 128 * 64, rw_base = kRingOperand + wc * 128 * 64;
-
     f32x16 acc[4][4];
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -534,12 +467,6 @@ __global__ __launch_bounds__(kW4Threads) __attribute__((amdgpu_waves_per_eu(1, 1
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
     u32x4 af[2][4], wf[2][4];                // [k-step parity][block]
-#if WAN_DEV_EXPERIMENTS
-    const bool early_w = (g.exp & 16) != 0;        // the W pieces of tile kt+2 leave in k-step 3 of tile kt as well (measured: no gain)
-#else
-    constexpr bool early_w = false;
-#endif
-
 #define GW4_SB() __builtin_amdgcn_sched_barrier(0)
 // 12 of the 16 accumulator tiles (192 registers) are pinned to AGPRs, the last M block (4 tiles, 64 registers) to VGPRs:
 // with all 256 AGPRs claimed by "+a" operands hipcc's allocator has no slack left and shuffles tiles through scratch.
@@ -548,8 +475,7 @@ __global__ __launch_bounds__(kW4Threads) __attribute__((amdgpu_waves_per_eu(1, 1
 #define GW4_MFMA(ACC, X, Y) do { if (i < 3) GW4_MFMA_A(ACC, X, Y); else GW4_MFMA_V(ACC, X, Y); } while (0)
     // k-step S of the K tile in LDS buffer `buf`: 16 MFMAs; the even slots fetch the fragments of the NEXT k-step (from
     // `nbuf`, k-step NS), the odd slots of the steps that carry DMA issue one piece each.
-    auto kstep = [&](auto S_, int buf, int nbuf, auto NS_, auto DMA_, __amdgpu_buffer_rsrc_t ra, __amdgpu_buffer_rsrc_t rw, int dbuf,
-                     __amdgpu_buffer_rsrc_t rw2) __attribute__((always_inline)) {
+    auto kstep = [&](auto S_, int buf, int nbuf, auto NS_, auto DMA_, __amdgpu_buffer_rsrc_t ra, __amdgpu_buffer_rsrc_t rw, int dbuf) __attribute__((always_inline)) {
         constexpr int S = decltype(S_)::value, NS = decltype(NS_)::value, DMA = decltype(DMA_)::value;   // DMA: 0 none, 1 pieces 0..7 (A), 2 pieces 8..15 (W)
         (void)buf;
 #pragma unroll
@@ -564,12 +490,10 @@ __global__ __launch_bounds__(kW4Threads) __attribute__((amdgpu_waves_per_eu(1, 1
                     const int f = slot / 2;
                     if (f < 4) af[NS & 1][f] = lds16(smem + a_base + f * 32 * 128 + koff[nbuf][NS]);
                     else wf[NS & 1][f - 4] = lds16(smem + w_base + (f - 4) * 32 * 128 + koff[nbuf][NS]);
-                    // experiment (gemm_exp & 16): the W pieces of tile kt+2 leave in k-step 3 of tile kt as well (one k-step more flight time)
-                    if (DMA == 1 && early_w) stage_piece(rw2, dbuf, 1, slot / 2, g.ldw);
                 } else if (DMA != 0) {
                     const int pj = slot / 2;
                     if (DMA == 1) stage_piece(ra, dbuf, 0, pj, g.lda);
-                    else if (!early_w) stage_piece(rw, dbuf, 1, pj, g.ldw);
+                    else stage_piece(rw, dbuf, 1, pj, g.ldw);
                 }
                 GW4_SB();
             }
@@ -577,64 +501,6 @@ __global__ __launch_bounds__(kW4Threads) __attribute__((amdgpu_waves_per_eu(1, 1
     using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
     using I2 = std::integral_constant<int, 2>; using I3 = std::integral_constant<int, 3>;
 
-    if constexpr (RING) {
-        // k-step KS (0 / 1) of a tile: 16 MFMAs on registers [KS]; even slots read the NEXT k-step's fragments (stage NST, k-step
-        // 1 - KS) into registers [1 - KS]; slots 1, 5, 9, 13 issue one DMA piece each (operand OP of the tile behind `r`, stage DST)
-        auto rkstep = [&](auto KS_, auto NST_, auto OP_, auto DST_, __amdgpu_buffer_rsrc_t r) __attribute__((always_inline)) {
-            constexpr int KS = decltype(KS_)::value, NST = decltype(NST_)::value, OP = decltype(OP_)::value, DST = decltype(DST_)::value;
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int slot = i * 4 + j;
-                    if constexpr (kTransposed) GW4_MFMA(acc[i][j], af[KS][i], wf[KS][j]);
-                    else GW4_MFMA(acc[i][j], wf[KS][j], af[KS][i]);
-                    GW4_SB();
-                    if (slot % 2 == 0) {
-                        const int f = slot / 2;
-                        if (f < 4) af[1 - KS][f] = lds16(smem + ra_base + f * 32 * 64 + rkoff[NST][1 - KS]);
-                        else wf[1 - KS][f - 4] = lds16(smem + rw_base + (f - 4) * 32 * 64 + rkoff[NST][1 - KS]);
-                    } else if (slot % 4 == 1) {
-                        stage_piece32(r, DST, OP, slot / 4, OP ? g.ldw : g.lda);
-                    }
-                    GW4_SB();
-                }
-        };
-        using J0 = std::integral_constant<int, 0>; using J1 = std::integral_constant<int, 1>;
-        // prologue: tiles 0..2 and the A half of tile 3 in flight; tile 0 waited for
-        for (int t = 0; t < 4; ++t) {
-            const __amdgpu_buffer_rsrc_t ra = rsrc32(a_tile, a_bytes, t), rw = rsrc32(w_tile, w_bytes, t);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) stage_piece32(ra, t, 0, j, g.lda);
-            if (t < 3) {
-#pragma unroll
-                for (int j = 0; j < 4; ++j) stage_piece32(rw, t, 1, j, g.ldw);
-            }
-        }
-        __builtin_amdgcn_s_waitcnt(0x4F74);          // vmcnt(20): everything but tile 0 may still be in flight
-        __builtin_amdgcn_s_barrier();
-#pragma unroll
-        for (int f = 0; f < 4; ++f) {
-            af[0][f] = lds16(smem + ra_base + f * 32 * 64 + rkoff[0][0]);
-            wf[0][f] = lds16(smem + rw_base + f * 32 * 64 + rkoff[0][0]);
-        }
-        auto rtile = [&](int t, auto ST_) __attribute__((always_inline)) {        // tile t lives in stage ST = t % 4
-            constexpr int ST = decltype(ST_)::value;
-            const __amdgpu_buffer_rsrc_t rw3 = rsrc32(w_tile, w_bytes, t + 3);      // W of tile t+3 -> stage (ST + 3) % 4 (its A went out in tile t-1)
-            const __amdgpu_buffer_rsrc_t ra4 = rsrc32(a_tile, a_bytes, t + 4);      // A of tile t+4 -> stage ST, behind the barrier
-            rkstep(J0{}, std::integral_constant<int, ST>{}, J1{}, std::integral_constant<int, (ST + 3) & 3>{}, rw3);
-            __builtin_amdgcn_s_waitcnt(0x4F70);      // vmcnt(16): my pieces of tile t+1 have landed (t+2, t+3 may be in flight) ...
-            __builtin_amdgcn_s_barrier();            // ... everybody's have, and every wave has read the last fragment of tile t
-            GW4_SB();
-            rkstep(J1{}, std::integral_constant<int, (ST + 1) & 3>{}, J0{}, std::integral_constant<int, ST>{}, ra4);
-        };
-        for (int t = 0; t < nk32; t += 4) {           // K % 128 == 0
-            rtile(t, std::integral_constant<int, 0>{});
-            rtile(t + 1, std::integral_constant<int, 1>{});
-            rtile(t + 2, std::integral_constant<int, 2>{});
-            rtile(t + 3, std::integral_constant<int, 3>{});
-        }
-    } else {
     // ---- prologue: K tile 0 -> buffer 0 (waited for), the A half of K tile 1 -> buffer 1 (in flight), fragments of k-step 0
     {
         const __amdgpu_buffer_rsrc_t ra = rsrc(a_tile, a_bytes, 0), rw = rsrc(w_tile, w_bytes, 0);
@@ -645,11 +511,6 @@ __global__ __launch_bounds__(kW4Threads) __attribute__((amdgpu_waves_per_eu(1, 1
         const __amdgpu_buffer_rsrc_t ra1 = rsrc(a_tile, a_bytes, 1);
 #pragma unroll
         for (int j = 0; j < 8; ++j) stage_piece(ra1, 1, 0, j, g.lda);       // its W half goes out in k-step 0 of tile 0
-        if (early_w) {
-            const __amdgpu_buffer_rsrc_t rw1 = rsrc(w_tile, w_bytes, 1);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) stage_piece(rw1, 1, 1, j, g.ldw);
-        }
 #pragma unroll
         for (int f = 0; f < 4; ++f) {
             af[0][f] = lds16(smem + a_base + f * 32 * 128 + koff[0][0]);
@@ -662,19 +523,17 @@ __global__ __launch_bounds__(kW4Threads) __attribute__((amdgpu_waves_per_eu(1, 1
     auto ktile = [&](int kt, int b) __attribute__((always_inline)) {
         const __amdgpu_buffer_rsrc_t rw_prev = rsrc(w_tile, w_bytes, kt + 1);      // W of tile kt+1 -> buffer 1-b (its A went out in tile kt-1)
         const __amdgpu_buffer_rsrc_t ra_next = rsrc(a_tile, a_bytes, kt + 2);      // A of tile kt+2 -> buffer b, after the barrier
-        const __amdgpu_buffer_rsrc_t rw_next = rsrc(w_tile, w_bytes, kt + 2);      // experiment: W of tile kt+2 together with its A
-        kstep(I0{}, b, b, I1{}, I2{}, ra_next, rw_prev, 1 - b, rw_next);
-        kstep(I1{}, b, b, I2{}, I0{}, ra_next, rw_prev, b, rw_next);
-        kstep(I2{}, b, b, I3{}, I0{}, ra_next, rw_prev, b, rw_next);
+        kstep(I0{}, b, b, I1{}, I2{}, ra_next, rw_prev, 1 - b);
+        kstep(I1{}, b, b, I2{}, I0{}, ra_next, rw_prev, b);
+        kstep(I2{}, b, b, I3{}, I0{}, ra_next, rw_prev, b);
         __builtin_amdgcn_s_waitcnt(0x0F70);      // my pieces of tile kt+1 have landed ...
         __builtin_amdgcn_s_barrier();            // ... everybody's have, and every wave has read the last fragment of tile kt
         GW4_SB();
-        kstep(I3{}, b, 1 - b, I0{}, I1{}, ra_next, rw_prev, b, rw_next);
+        kstep(I3{}, b, 1 - b, I0{}, I1{}, ra_next, rw_prev, b);
     };
     for (int kt = 0; kt < nk; kt += 2) {          // nk is even (the dispatcher sends K % 128 != 0 to the 8-wave kernel)
         ktile(kt, 0);
         ktile(kt + 1, 1);
-    }
     }
     __builtin_amdgcn_s_waitcnt(0x0F70);          // zero-length requests past the last tile still write LDS: let them finish
     asm volatile("s_nop 7\n\ts_nop 7" ::: "memory");     // MFMA D -> the accumulator reads of the epilogue
@@ -786,117 +645,20 @@ __global__ __launch_bounds__(kW4Threads) __attribute__((amdgpu_waves_per_eu(1, 1
     }
 }
 
-template <int EPI>
-wan_status_t launch_w4(const GemmArgs& g, hipStream_t s) {
-    static std::atomic<uint64_t> attr_done{0};
-    const wan_status_t st = wan_once_per_device(attr_done, +[]() -> wan_status_t {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_w4_kernel<EPI>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-#if WAN_DEV_EXPERIMENTS
-        if (e == hipSuccess)
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_w4_kernel<EPI, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-#endif
-        if (e != hipSuccess) {
-            wan_set_error("wan_gemm_bf16(w4): cannot reserve %d B of LDS: %s", kLdsBytes, hipGetErrorString(e));
-            return WAN_ERR_LAUNCH;
-        }
-        return WAN_OK;
-    });
-    if (st != WAN_OK) return st;
-#if WAN_DEV_EXPERIMENTS     // `make EXPERIMENTS=1` only: the ring form is a measured alternative, not a product path
-    if (wan_tune(WAN_TUNE_GEMM_RING) != 0) {
-        hipLaunchKernelGGL((gemm_w4_kernel<EPI, true>), dim3((unsigned)(g.tiles_m * g.tiles_n)), dim3(kW4Threads), kLdsBytes, s, g);
-        WAN_CHECK_LAUNCH("wan_gemm_bf16(w4 ring)");
-        return WAN_OK;
-    }
-#endif
-    hipLaunchKernelGGL((gemm_w4_kernel<EPI>), dim3((unsigned)(g.tiles_m * g.tiles_n)), dim3(kW4Threads), kLdsBytes, s, g);
-    WAN_CHECK_LAUNCH("wan_gemm_bf16(w4)");
-    return WAN_OK;
-}
 
-template <int EPI, int PHASES>
-wan_status_t launch256(const GemmArgs& g, hipStream_t s) {
-    static std::atomic<uint64_t> attr_done{0};
-    const wan_status_t st = wan_once_per_device(attr_done, +[]() -> wan_status_t {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_kernel<EPI, PHASES>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        if (e != hipSuccess) {
-            wan_set_error("wan_gemm_bf16(256): cannot reserve %d B of LDS: %s", kLdsBytes, hipGetErrorString(e));
-            return WAN_ERR_LAUNCH;
-        }
-        return WAN_OK;
-    });
-    if (st != WAN_OK) return st;
-    hipLaunchKernelGGL((gemm256_kernel<EPI, PHASES>), dim3((unsigned)(g.tiles_m * g.tiles_n)), dim3(kThreads), kLdsBytes, s, g);
-    WAN_CHECK_LAUNCH("wan_gemm_bf16(256)");
-    return WAN_OK;
-}
-
-template <int EPI>
-wan_status_t launch256_fp8(const GemmArgs& g, hipStream_t s) {
-    static std::atomic<uint64_t> attr_done{0};
-    const wan_status_t st = wan_once_per_device(attr_done, +[]() -> wan_status_t {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_kernel<EPI, 2, true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-        if (e != hipSuccess) {
-            wan_set_error("wan_gemm_fp8: cannot reserve %d B of LDS: %s", kLdsBytes, hipGetErrorString(e));
-            return WAN_ERR_LAUNCH;
-        }
-        return WAN_OK;
-    });
-    if (st != WAN_OK) return st;
-#if WAN_DEV_EXPERIMENTS      // `make EXPERIMENTS=1`: the 4-phase form of the fp8 instantiation for A/B timing (gemm_phases = 4)
-    if (wan_tune(WAN_TUNE_GEMM_PHASES) == 4) {
-        static std::atomic<uint64_t> attr4{0};
-        const wan_status_t st4 = wan_once_per_device(attr4, +[]() -> wan_status_t {
-            return hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm256_kernel<EPI, 4, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes) == hipSuccess ? WAN_OK : WAN_ERR_LAUNCH;
-        });
-        if (st4 != WAN_OK) return st4;
-        hipLaunchKernelGGL((gemm256_kernel<EPI, 4, true>), dim3((unsigned)(g.tiles_m * g.tiles_n)), dim3(kThreads), kLdsBytes, s, g);
-        WAN_CHECK_LAUNCH("wan_gemm_fp8");
-        return WAN_OK;
-    }
-#endif
-    hipLaunchKernelGGL((gemm256_kernel<EPI, 2, true>), dim3((unsigned)(g.tiles_m * g.tiles_n)), dim3(kThreads), kLdsBytes, s, g);
-    WAN_CHECK_LAUNCH("wan_gemm_fp8");
-    return WAN_OK;
+GemmArgs make_args(const WanGemmCall& c) {
+    GemmArgs g;
+    g.A = (const bf16_t*)c.A; g.lda = c.lda; g.W = (const bf16_t*)c.W; g.ldw = c.ldw; g.bias = c.bias;
+    g.out = c.out; g.ldo = c.ldo; g.gate = c.gate; g.rows_per_batch = c.rows_per_batch;
+    g.M = c.M; g.N = c.N; g.K = c.K; g.sa = c.a_row_scale; g.sw = c.w_row_scale;
+    g.tiles_m = (c.M + BM - 1) / BM; g.tiles_n = (c.N + BN - 1) / BN;
+    // M tiles per rasterisation group, measured at M = 67 080 (profiles/r01/gemm_raster_group_ab.log): 2 for wide N
+    // (qk projection +5 %, ffn.0 +2 % over the former 4), 3 otherwise (+2 %); 8 and 16 lose 10-15 %.
+    g.gm = g.tiles_n >= 40 ? 2 : 3;
+    return g;
 }
 
 }  // namespace
-
-extern "C" wan_status_t wan_gemm_fp8(const void* A_fp8, int64_t lda, const float* a_row_scale, const void* W_fp8, int64_t ldw,
-                                     const float* w_row_scale, const float* bias, void* out, int64_t ldo, int M, int N, int K,
-                                     int epilogue, const float* gate, int64_t rows_per_batch, void* stream) {
-    WAN_REQUIRE(A_fp8 && W_fp8 && out && a_row_scale && w_row_scale, WAN_ERR_INVALID, "wan_gemm_fp8: null tensor");
-    WAN_REQUIRE(M >= 0 && N > 0 && K > 0, WAN_ERR_INVALID, "wan_gemm_fp8: M=%d N=%d K=%d", M, N, K);
-    WAN_REQUIRE(K % 128 == 0, WAN_ERR_UNSUPPORTED, "wan_gemm_fp8: K=%d must be a multiple of 128", K);
-    WAN_REQUIRE(N % 4 == 0, WAN_ERR_UNSUPPORTED, "wan_gemm_fp8: N=%d must be a multiple of 4", N);
-    WAN_REQUIRE(lda % 16 == 0 && ldw % 16 == 0 && lda >= K && ldw >= K, WAN_ERR_INVALID,
-                "wan_gemm_fp8: lda=%lld ldw=%lld must be multiples of 16 and >= K", (long long)lda, (long long)ldw);
-    if (epilogue == WAN_EPI_BF16_T)
-        WAN_REQUIRE(ldo >= M && ldo % 4 == 0, WAN_ERR_INVALID, "wan_gemm_fp8: transposed ldo=%lld < M=%d or not a multiple of 4", (long long)ldo, M);
-    else
-        WAN_REQUIRE(ldo >= N && ldo % 4 == 0, WAN_ERR_INVALID, "wan_gemm_fp8: ldo=%lld < N=%d or not a multiple of 4", (long long)ldo, N);
-    WAN_REQUIRE(gate == nullptr || (epilogue == WAN_EPI_RESID_F32 && rows_per_batch > 0), WAN_ERR_INVALID,
-                "wan_gemm_fp8: gate needs WAN_EPI_RESID_F32 and rows_per_batch > 0");
-    if (M == 0) return WAN_OK;
-    GemmArgs g;
-    g.A = (const bf16_t*)A_fp8; g.lda = lda; g.W = (const bf16_t*)W_fp8; g.ldw = ldw; g.bias = bias;
-    g.out = out; g.ldo = ldo; g.gate = gate; g.rows_per_batch = rows_per_batch > 0 ? rows_per_batch : 1;
-    g.M = M; g.N = N; g.K = K; g.sa = a_row_scale; g.sw = w_row_scale; g.exp = 0;
-    g.tiles_m = (M + BM - 1) / BM; g.tiles_n = (N + BN - 1) / BN;
-    g.gm = g.tiles_n >= 40 ? 2 : 3;
-    hipStream_t s = (hipStream_t)stream;
-    switch (epilogue) {
-        case WAN_EPI_BF16: return launch256_fp8<WAN_EPI_BF16>(g, s);
-        case WAN_EPI_GELU_BF16: return launch256_fp8<WAN_EPI_GELU_BF16>(g, s);
-        case WAN_EPI_F32: return launch256_fp8<WAN_EPI_F32>(g, s);
-        case WAN_EPI_RESID_F32: return launch256_fp8<WAN_EPI_RESID_F32>(g, s);
-        case WAN_EPI_BF16_T: return launch256_fp8<WAN_EPI_BF16_T>(g, s);
-        default: wan_set_error("wan_gemm_fp8: unknown epilogue %d", epilogue); return WAN_ERR_INVALID;
-    }
-}
 
 // the 4-wave form of the 256^2 tile for this K?  (host arithmetic; also behind wan_gemm_plan)
 bool wan_gemm256_uses_w4(int K) {
@@ -904,33 +666,34 @@ bool wan_gemm256_uses_w4(int K) {
     return K % (2 * BK) == 0 && ((w4mode == 1 && K >= 4096) || (w4mode == 2 && K >= 8192) || w4mode == 3);
 }
 
-// called by wan_gemm_bf16 (gemm_bf16.hip) for large shapes; arguments already validated there
-wan_status_t wan_gemm_bf16_256(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias,
-                               void* out, int64_t ldo, int M, int N, int K, int epilogue,
-                               const float* gate, int64_t rows_per_batch, hipStream_t s) {
-    GemmArgs g;
-    g.A = (const bf16_t*)A; g.lda = lda; g.W = (const bf16_t*)W; g.ldw = ldw; g.bias = bias;
-    g.out = out; g.ldo = ldo; g.gate = gate; g.rows_per_batch = rows_per_batch > 0 ? rows_per_batch : 1;
-    g.M = M; g.N = N; g.K = K; g.sa = nullptr; g.sw = nullptr; g.exp = wan_tune(WAN_TUNE_GEMM_EXP);
-    g.tiles_m = (M + BM - 1) / BM; g.tiles_n = (N + BN - 1) / BN;
-    // M tiles per rasterisation group, measured at M = 67 080 (profiles/r01/gemm_raster_group_ab.log): 2 for wide N
-    // (qk projection +5 %, ffn.0 +2 % over the former 4), 3 otherwise (+2 %); 8 and 16 lose 10-15 %.
-    g.gm = g.tiles_n >= 40 ? 2 : 3;
+// the bf16 Linear on one workgroup per 256^2 tile (large shapes: see wan_gemm_plan)
+wan_status_t wan_gemm_bf16_256(const WanGemmCall& c, hipStream_t s) {
+    GemmArgs g = make_args(c);
     if (const int gm = wan_tune(WAN_TUNE_GEMM_GM); gm > 0) g.gm = gm;       // developer A/B switches (wan_set_tuning)
     const int phases = wan_tune(WAN_TUNE_GEMM_PHASES) > 0 ? wan_tune(WAN_TUNE_GEMM_PHASES) : kDefaultPhases;
     // gemm_w4: 0 never, 1 (default) for K % 128 == 0 and K >= 4096, 2 deep K only (K >= 8192), 3 whenever K % 128 == 0.  With the
     // batched epilogues the 4-wave kernel is ahead on every 14B shape in process (o/q 2.675 vs 2.686 ms, q|k 5.43 vs 5.46, ffn.0
     // 7.33 vs 7.68, ffn.2 7.72 vs 7.98; 8-way shards +3..7 %) and by 0.45 % of a whole step in situ
     // (profiles/r02/gemm_epilogue_ab.txt); at K = 1536 it loses 10-15 % (profiles/r02/gemm_w4_ab.log).
-    const bool w4 = wan_gemm256_uses_w4(K);
-#define WAN_G256(E) (w4 ? launch_w4<E>(g, s) : phases == 4 ? launch256<E, 4>(g, s) : launch256<E, 2>(g, s))
-    switch (epilogue) {
-        case WAN_EPI_BF16: return WAN_G256(WAN_EPI_BF16);
-        case WAN_EPI_GELU_BF16: return WAN_G256(WAN_EPI_GELU_BF16);
-        case WAN_EPI_F32: return WAN_G256(WAN_EPI_F32);
-        case WAN_EPI_RESID_F32: return WAN_G256(WAN_EPI_RESID_F32);
-        case WAN_EPI_BF16_T: return WAN_G256(WAN_EPI_BF16_T);
-        default: wan_set_error("wan_gemm_bf16: unknown epilogue %d", epilogue); return WAN_ERR_INVALID;
-    }
-#undef WAN_G256
+    const bool w4 = wan_gemm256_uses_w4(c.K);
+    const dim3 grid((unsigned)(g.tiles_m * g.tiles_n));
+    return wan_gemm_epilogue("wan_gemm_bf16", c.epilogue, [&](auto epi) {
+        constexpr int E = decltype(epi)::value;
+        if (w4) return wan_gemm_launch<gemm_w4_kernel<E>, kLdsBytes>("wan_gemm_bf16(w4)", grid, kW4Threads, s, g);
+        if (phases == 4) return wan_gemm_launch<gemm256_kernel<E, 4>, kLdsBytes>("wan_gemm_bf16(256)", grid, kThreads, s, g);
+        return wan_gemm_launch<gemm256_kernel<E, 2>, kLdsBytes>("wan_gemm_bf16(256)", grid, kThreads, s, g);
+    });
+}
+
+// the e4m3 Linear: the 8-wave kernel's FP8 instantiation
+wan_status_t wan_gemm_fp8_256(const WanGemmCall& c, hipStream_t s) {
+    const GemmArgs g = make_args(c);
+    const dim3 grid((unsigned)(g.tiles_m * g.tiles_n));
+    return wan_gemm_epilogue("wan_gemm_fp8", c.epilogue, [&](auto epi) {
+        constexpr int E = decltype(epi)::value;
+#if WAN_DEV_EXPERIMENTS      // `make EXPERIMENTS=1`: the 4-phase form of the fp8 instantiation for A/B timing (gemm_phases = 4)
+        if (wan_tune(WAN_TUNE_GEMM_PHASES) == 4) return wan_gemm_launch<gemm256_kernel<E, 4, true>, kLdsBytes>("wan_gemm_fp8", grid, kThreads, s, g);
+#endif
+        return wan_gemm_launch<gemm256_kernel<E, 2, true>, kLdsBytes>("wan_gemm_fp8", grid, kThreads, s, g);
+    });
 }

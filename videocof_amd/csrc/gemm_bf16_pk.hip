@@ -22,11 +22,7 @@
 //
 // Contract differences to wan_gemm_bf16: the caller passes a workspace (wan_gemm_workspace_bytes) that no other stream uses
 // concurrently; its first 4 KiB (arrival counters) are zeroed by a memset node ahead of the launch.
-#include <stdlib.h>
-
-#include <type_traits>
-
-#include "common.hpp"
+#include "gemm_common.hpp"
 
 #ifndef WAN_DEV_EXPERIMENTS
 #define WAN_DEV_EXPERIMENTS 0
@@ -109,7 +105,7 @@ __host__ __device__ __forceinline__ Slab make_slab(const PkArgs& g, int worker, 
     const int nt = g.tiles_m * g.tiles_n;
     s.x = worker & 7; s.c = worker >> 3; s.W = g.nworkers >> 3;
     const int q = nt >> 3, r = nt & 7;
-    s.start = s.x < r ? s.x * (q + 1) : r * (q + 1) + (s.x - r) * q;
+    s.start = wan_xcd_slab_start(nt, s.x);
     s.n = q + (s.x < r ? 1 : 0);
     s.nk = g.K / ktile;
     s.n2 = s.nk >> 1;
@@ -968,28 +964,6 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
 #undef GP_SB
 }
 
-template <int EPI, int FORM, bool FP8 = false>
-wan_status_t launch_pk(const PkArgs& g, hipStream_t s) {
-    static std::atomic<uint64_t> attr_done{0};
-    const wan_status_t st = wan_once_per_device(attr_done, +[]() -> wan_status_t {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_pk_kernel<EPI, FORM, FP8>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes + 64);
-        if (e != hipSuccess) {
-            wan_set_error("wan_gemm_bf16_ws: cannot reserve %d B of LDS: %s", kLdsBytes + 64, hipGetErrorString(e));
-            return WAN_ERR_LAUNCH;
-        }
-        return WAN_OK;
-    });
-    if (st != WAN_OK) return st;
-    if (hipMemsetAsync(g.counters, 0, kCounterBytes, s) != hipSuccess) {
-        wan_set_error("wan_gemm_bf16_ws: cannot clear the arrival counters: %s", hipGetErrorString(hipGetLastError()));
-        return WAN_ERR_LAUNCH;
-    }
-    hipLaunchKernelGGL((gemm_pk_kernel<EPI, FORM, FP8>), dim3((unsigned)g.nworkers), dim3(kThreads), kLdsBytes + 64, s, g);
-    WAN_CHECK_LAUNCH("wan_gemm_bf16_ws");
-    return WAN_OK;
-}
-
 }  // namespace
 
 // grid of the persistent form: one workgroup per CU -- of those not reserved for communication kernels (tuning key "sp_reserve_cus") --, a
@@ -1043,10 +1017,10 @@ static void pk_plan_args(PkArgs& g, int M, int N, int K, int ktile = BK) {
 // Host arithmetic only: segment `index` of worker `worker` of the persistent GEMM's plan for this shape -- the SAME functions the
 // kernel evaluates (tests: every (tile, K tile) is covered exactly once, pieces and slots are consistent).
 // out[11] = tm, tn, kb, ke, partial, slot, counter, j_lo, j_hi, me, tau; returns 1 when the segment exists, 0 past the end.
-extern "C" int wan_gemm_pk_segment(int M, int N, int K, int worker, int index, int* out) {
-    if (M <= 0 || N <= 0 || K <= 0 || K % 128 != 0 || worker < 0 || index < 0 || out == nullptr) return 0;
+static int pk_segment(int M, int N, int K, int ktile, int worker, int index, int* out) {
+    if (M <= 0 || N <= 0 || K <= 0 || K % (2 * ktile) != 0 || worker < 0 || index < 0 || out == nullptr) return 0;
     PkArgs g;
-    pk_plan_args(g, M, N, K);
+    pk_plan_args(g, M, N, K, ktile);
     if (worker >= g.nworkers) return 0;
     const Slab slab = make_slab(g, worker, g.ktile);
     const Seg e = get_seg(g, slab, index);
@@ -1054,63 +1028,39 @@ extern "C" int wan_gemm_pk_segment(int M, int N, int K, int worker, int index, i
     for (int i = 0; i < 11; ++i) out[i] = v[i];
     return e.valid;
 }
+extern "C" int wan_gemm_pk_segment(int M, int N, int K, int worker, int index, int* out) { return pk_segment(M, N, K, BK, worker, index, out); }
 
 extern "C" int wan_gemm_pk_grid(int M, int N) { return wan_gemm_pk_workers(M, N); }
 
-// called by wan_gemm_bf16_ws (gemm_bf16.hip) for shapes the 4-wave 256^2 kernel takes; arguments already validated there
-wan_status_t wan_gemm_bf16_pk(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias,
-                              void* out, int64_t ldo, int M, int N, int K, int epilogue,
-                              const float* gate, int64_t rows_per_batch, void* workspace, hipStream_t s) {
+// Both operand types: fill the arguments, clear the 4 KiB counter header, launch one workgroup per resident CU.  `name`: the `_ws` entry.
+static wan_status_t launch_pk(const char* name, const WanGemmCall& c, int ktile, void* workspace, hipStream_t s) {
     PkArgs g;
-    g.A = (const bf16_t*)A; g.lda = lda; g.W = (const bf16_t*)W; g.ldw = ldw; g.bias = bias;
-    g.out = out; g.ldo = ldo; g.gate = gate; g.rows_per_batch = rows_per_batch > 0 ? rows_per_batch : 1;
-    pk_plan_args(g, M, N, K);
-    WAN_REQUIRE(g.nworkers <= kMaxWorkers && g.nworkers % 8 == 0, WAN_ERR_INVALID, "wan_gemm_bf16_ws: %d workers (at most %d, a multiple of 8)", g.nworkers, kMaxWorkers);
+    g.A = (const bf16_t*)c.A; g.lda = c.lda; g.W = (const bf16_t*)c.W; g.ldw = c.ldw; g.bias = c.bias;
+    g.out = c.out; g.ldo = c.ldo; g.gate = c.gate; g.rows_per_batch = c.rows_per_batch;
+    pk_plan_args(g, c.M, c.N, c.K, ktile);
+    g.sa = c.a_row_scale; g.sw = c.w_row_scale;
+    WAN_REQUIRE(g.nworkers <= kMaxWorkers && g.nworkers % 8 == 0, WAN_ERR_INVALID, "%s: %d workers (at most %d, a multiple of 8)", name, g.nworkers, kMaxWorkers);
     g.counters = (int*)workspace;
     g.slots = (char*)workspace + kCounterBytes;
-#define WAN_PK(E) (((g.form >> (E)) & 1) ? launch_pk<E, 1>(g, s) : launch_pk<E, 0>(g, s))
-    switch (epilogue) {
-        case WAN_EPI_BF16: return WAN_PK(WAN_EPI_BF16);
-        case WAN_EPI_GELU_BF16: return WAN_PK(WAN_EPI_GELU_BF16);
-        case WAN_EPI_F32: return WAN_PK(WAN_EPI_F32);
-        case WAN_EPI_RESID_F32: return WAN_PK(WAN_EPI_RESID_F32);
-        case WAN_EPI_BF16_T: return WAN_PK(WAN_EPI_BF16_T);
-        default: wan_set_error("wan_gemm_bf16_ws: unknown epilogue %d", epilogue); return WAN_ERR_INVALID;
-    }
-#undef WAN_PK
+    const bool fp8 = ktile != BK;
+    return wan_gemm_epilogue(name, c.epilogue, [&](auto epi) {
+        constexpr int E = decltype(epi)::value;
+        if (hipMemsetAsync(g.counters, 0, kCounterBytes, s) != hipSuccess) {
+            wan_set_error("%s: cannot clear the arrival counters: %s", name, hipGetErrorString(hipGetLastError()));
+            return WAN_ERR_LAUNCH;
+        }
+        const dim3 grid((unsigned)g.nworkers);
+        if (fp8) return wan_gemm_launch<gemm_pk_kernel<E, 1, true>, kLdsBytes + 64>(name, grid, kThreads, s, g);
+        if ((g.form >> E) & 1) return wan_gemm_launch<gemm_pk_kernel<E, 1>, kLdsBytes + 64>(name, grid, kThreads, s, g);
+        return wan_gemm_launch<gemm_pk_kernel<E, 0>, kLdsBytes + 64>(name, grid, kThreads, s, g);
+    });
 }
 
-// the e4m3 instantiation (wan_gemm_fp8_ws, gemm_bf16_256.hip): same plan with K tiles of 128 elements; arguments already validated there
-wan_status_t wan_gemm_fp8_pk(const void* A, int64_t lda, const float* a_row_scale, const void* W, int64_t ldw, const float* w_row_scale,
-                             const float* bias, void* out, int64_t ldo, int M, int N, int K, int epilogue,
-                             const float* gate, int64_t rows_per_batch, void* workspace, hipStream_t s) {
-    PkArgs g;
-    g.A = (const bf16_t*)A; g.lda = lda; g.W = (const bf16_t*)W; g.ldw = ldw; g.bias = bias;
-    g.out = out; g.ldo = ldo; g.gate = gate; g.rows_per_batch = rows_per_batch > 0 ? rows_per_batch : 1;
-    pk_plan_args(g, M, N, K, 2 * BK);
-    g.sa = a_row_scale; g.sw = w_row_scale;
-    WAN_REQUIRE(g.nworkers <= kMaxWorkers && g.nworkers % 8 == 0, WAN_ERR_INVALID, "wan_gemm_fp8_ws: %d workers (at most %d, a multiple of 8)", g.nworkers, kMaxWorkers);
-    g.counters = (int*)workspace;
-    g.slots = (char*)workspace + kCounterBytes;
-    switch (epilogue) {
-        case WAN_EPI_BF16: return launch_pk<WAN_EPI_BF16, 1, true>(g, s);
-        case WAN_EPI_GELU_BF16: return launch_pk<WAN_EPI_GELU_BF16, 1, true>(g, s);
-        case WAN_EPI_F32: return launch_pk<WAN_EPI_F32, 1, true>(g, s);
-        case WAN_EPI_RESID_F32: return launch_pk<WAN_EPI_RESID_F32, 1, true>(g, s);
-        case WAN_EPI_BF16_T: return launch_pk<WAN_EPI_BF16_T, 1, true>(g, s);
-        default: wan_set_error("wan_gemm_fp8_ws: unknown epilogue %d", epilogue); return WAN_ERR_INVALID;
-    }
-}
+// wan_gemm_bf16_ws for the shapes wan_gemm_ws_plan gives to the persistent kernel
+wan_status_t wan_gemm_bf16_pk(const WanGemmCall& c, void* workspace, hipStream_t s) { return launch_pk("wan_gemm_bf16_ws", c, BK, workspace, s); }
+
+// the e4m3 instantiation (wan_gemm_fp8_ws): same plan with K tiles of 128 elements
+wan_status_t wan_gemm_fp8_pk(const WanGemmCall& c, void* workspace, hipStream_t s) { return launch_pk("wan_gemm_fp8_ws", c, 2 * BK, workspace, s); }
 
 // segment `index` of worker `worker` of the e4m3 plan (K tiles of 128 elements): see wan_gemm_pk_segment
-extern "C" int wan_gemm_fp8_pk_segment(int M, int N, int K, int worker, int index, int* out) {
-    if (M <= 0 || N <= 0 || K <= 0 || K % 256 != 0 || worker < 0 || index < 0 || out == nullptr) return 0;
-    PkArgs g;
-    pk_plan_args(g, M, N, K, 2 * BK);
-    if (worker >= g.nworkers) return 0;
-    const Slab slab = make_slab(g, worker, g.ktile);
-    const Seg e = get_seg(g, slab, index);
-    const int v[11] = {e.tm, e.tn, e.kb, e.ke, e.partial, e.slot, e.cnt, e.j_lo, e.j_hi, e.me, e.tau};
-    for (int i = 0; i < 11; ++i) out[i] = v[i];
-    return e.valid;
-}
+extern "C" int wan_gemm_fp8_pk_segment(int M, int N, int K, int worker, int index, int* out) { return pk_segment(M, N, K, 2 * BK, worker, index, out); }
