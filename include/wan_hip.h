@@ -646,6 +646,53 @@ int64_t wan_frames_resample_table_bytes(int n_out, int taps);
 wan_status_t wan_frames_u8_resample(const void* src_u8, void* dst_u8, int B, int T, int H, int W, int Ho, int Wo,
                                     const void* xtab, int kx, const void* ytab, int ky, void* stream);
 
+/* The writer's grid and the side-by-side compare clip: n_src source clips placed into rectangles of ONE uint8 [T_out, Hc, Wc, 3]
+ * canvas in one launch, each converted to bytes on the way; every canvas byte is written, what no source covers with the byte `pad`
+ * (make_grid's border and empty cells are 0 BEFORE the writer's `rescale`: pad = 0, or trunc((0 + 1) / 2 * 255) = 127 with it).
+ * replaces: save_videos_grid for more than one sample -- torchvision's make_grid(nrow=6, padding=2, pad_value=0) mosaic, `rescale`,
+ *           `(x * 255).numpy().astype(np.uint8)` (videox_fun/utils/utils.py:59-68) -- and save_side_by_side (fast_infer.py:183-206):
+ *           _normalize_to_01 of both clips, the crop to the common T/H/W from the start of each axis, torch.cat(dim=4), the writer.
+ * A source (wan_compose_src) is a strided view: `base` = its element [0, 0, 0, 0], strides in elements, `extent` = the elements
+ * addressable from `base` (the geometry is checked against it).  kind: uint8 interleaved [T, H, W, 3] (stride_c = 1 between the
+ * channels of a pixel) or planar float32 / bf16 [3, T, H, W].  Frames [t0, t0 + nt), rows [y0, y0 + h), columns [x0, x0 + w) of it
+ * go to the canvas frames [0, nt) at (dst_y, dst_x); canvas frames from nt on are pad there.  mode:
+ *     COPY              (uint8)  the bytes as they are
+ *     LOADER_ROUNDTRIP  (uint8)  what the reference's compare clip shows of a clip it loaded:  v = float32(u) * float32(2.0 / 255.0) - 1.0f
+ *                                (fast_infer.py:88-90), _normalize_to_01(v), trunc(. * 255.0f) -- NOT the identity on bytes
+ *     WRITER            (float)  trunc(x * 255.0f), of (x + 1.0f) / 2.0f when `rescale` is set (utils.py:65-67); no clamp, as there: outside
+ *                                [0, 256) the reference's conversion is undefined, here it is the low byte of the truncated int32
+ *     NORMALIZE         (float)  _normalize_to_01 (fast_infer.py:183-189), then the writer: trunc(clamp(r(x), 0, 1) * 255.0f) with
+ *                                r(x) = (x + 1.0f) / 2.0f if the tensor's minimum is < 0 or its maximum > 1, else x
+ * Every float32 operation is rounded on its own (no FMA); a bf16 source rounds `x + 1.0` and `/ 2.0` to bf16 as torch's tensor ops do.
+ * The range rule is decided ON THE DEVICE: `rescale_flag` points to the int32 wan_video_range_flag wrote for the WHOLE tensor the
+ * reference would hand to _normalize_to_01 (required for NORMALIZE; optional for LOADER_ROUNDTRIP, where NULL means the rescale is
+ * taken -- true of every clip with a byte below 128; not allowed otherwise); the host never reads it.
+ * Destination rectangles may not overlap; n_src <= WAN_COMPOSE_MAX_SRC (16), T_out <= 65535 -> else WAN_ERR_UNSUPPORTED.  A window
+ * that leaves its tensor or a rectangle that leaves the canvas is WAN_ERR_INVALID before anything is enqueued.  Any H, W and
+ * alignment: the canvas is stored in 16-byte pieces cut at 16-byte addresses (dwordx4 inside a row, bytes at its two ends); a piece
+ * inside one interleaved uint8 source is read as two aligned 16-byte words, everything else element by element.
+ * Enqueues one kernel on `stream`; never synchronises. */
+#define WAN_COMPOSE_MAX_SRC 16
+enum { WAN_COMPOSE_U8 = 0, WAN_COMPOSE_F32 = 1, WAN_COMPOSE_BF16 = 2 };
+enum { WAN_COMPOSE_COPY = 0, WAN_COMPOSE_LOADER_ROUNDTRIP = 1, WAN_COMPOSE_WRITER = 2, WAN_COMPOSE_NORMALIZE = 3 };
+typedef struct {
+    const void* base;
+    const int* rescale_flag; /* device int32 of wan_video_range_flag, or NULL */
+    int64_t extent;
+    int64_t stride_c, stride_t, stride_y, stride_x;
+    int kind, mode, rescale;
+    int t0, y0, x0, nt, h, w;
+    int dst_y, dst_x;
+} wan_compose_src;
+wan_status_t wan_frames_u8_compose(const wan_compose_src* srcs, int n_src, void* canvas_u8, int T_out, int Hc, int Wc,
+                                   int pad, void* stream);
+
+/* _normalize_to_01's range rule (fast_infer.py:185-187) over n contiguous elements (kind as above; uint8 = the loader's float32 video
+ * of those bytes) into one int32 in device memory: bit 0 = an element < 0 or > 1 was seen, bit 1 = a NaN was seen; the rule's
+ * `vmin < 0.0 or vmax > 1.0` holds exactly when the word is 1 (torch's min / max of a tensor with a NaN are NaN, and both
+ * comparisons with a NaN are false: no rescale).  Zeroes the word and enqueues one kernel on `stream`; never synchronises. */
+wan_status_t wan_video_range_flag(const void* x, int kind, int64_t n, int* flag, void* stream);
+
 /* ===========================================================================
  * the umT5 text encoder (videox_fun/models/wan_text_encoder.py:256-304), the step
  * before the denoising path.  Its Linear layers are wan_gemm_bf16; the rest:

@@ -22,6 +22,10 @@ without it the pipeline gets a bf16 device tensor and returns float32 planar fra
        as_uint8=True) (wan_video_to_frames_u8 + one copy).
   in:  uint8 frames in host memory -> the VAE's input on the device.  old = the reference loader's host conversion to float32
        (fast_infer.py:88-90) + `.to(device, dtype)`; new = bytes to the device + wan_frames_u8_to_video.
+  cmp: the compare clip (save_side_by_side, fast_infer.py:183-206) as uint8 [T, H, 2 W, 3] in host memory.  old = the float32 planes
+       both paths above leave on the host (the loader's video, the pipeline's frames), _normalize_to_01 of each, the crop, the
+       cat and the writer's host conversion; new = the source's bytes to the device + compare_frames (wan_video_range_flag +
+       wan_frames_u8_compose) on the edit's device frames + one copy into page-locked memory.
 and each kernel alone with HIP events (bytes read + written per second)."""
 import argparse
 import json
@@ -64,7 +68,7 @@ def writer_bytes(videos):
 def io_only(args):
     import numpy as np
     from videocof_amd import WanPipeline, ops
-    from videocof_amd.video_io import reference_frames_to_video
+    from videocof_amd.video_io import compare_frames, reference_compare_frames, reference_frames_to_video
     dev = torch.device("cuda:0")
     T, H, W = args.frames, args.height, args.width
     dtype = torch.bfloat16
@@ -88,6 +92,17 @@ def io_only(args):
     def in_new():
         return ops.frames_u8_to_video(frames_host[None].to(dev), dtype)
 
+    src_planes = reference_frames_to_video(frames_host[None])                   # what the reference's loader leaves on the host
+    edit_planes = torch.from_numpy(pipe.decode_latents(z)).clone()             # what its pipeline returns: float32 [1, 3, T, H, W]
+    edit_dev = ops.video_to_frames_u8(decoded)                                  # what output_type="uint8" keeps on the device
+    cmp_host = torch.empty(1, T, H, 2 * W, 3, dtype=torch.uint8, pin_memory=True)
+
+    def cmp_old():
+        return reference_compare_frames(src_planes, edit_planes)
+
+    def cmp_new():
+        return compare_frames(frames_host[None].to(dev), edit_dev, out=cmp_host)
+
     def wall(fn):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
@@ -95,14 +110,16 @@ def io_only(args):
         torch.cuda.synchronize()
         return time.perf_counter() - t0, r
 
-    res = {k: [] for k in ("out_old", "out_new", "in_old", "in_new")}
-    for fn in (out_old, out_new, in_old, in_new):
+    res = {k: [] for k in ("out_old", "out_new", "in_old", "in_new", "cmp_old", "cmp_new")}
+    for fn in (out_old, out_new, in_old, in_new, cmp_old, cmp_new):
         fn()                                             # warm-up: allocator, page-locked buffers
     for _ in range(args.reps):                           # alternating old / new
-        for name, fn in (("out_old", out_old), ("out_new", out_new), ("in_old", in_old), ("in_new", in_new)):
+        for name, fn in (("out_old", out_old), ("out_new", out_new), ("in_old", in_old), ("in_new", in_new),
+                         ("cmp_old", cmp_old), ("cmp_new", cmp_new)):
             res[name].append(round(wall(fn)[0], 5))
     assert np.array_equal(out_old(), out_new()), "old and new output paths disagree"
     assert torch.equal(in_old(), in_new()), "old and new input paths disagree"
+    assert torch.equal(cmp_old(), cmp_new()), "old and new compare clips disagree"
 
     def kernel_seconds(fn, iters=20):
         for _ in range(3):
@@ -123,13 +140,22 @@ def io_only(args):
     st = torch.cuda.current_stream().cuda_stream
     k_in = kernel_seconds(lambda: lib.wan_frames_u8_to_video(P(fr_dev), P(vid), 1, 1, T, H, W, st))
     k_out = kernel_seconds(lambda: lib.wan_video_to_frames_u8(P(decoded), 1, P(clip), 1, T, H, W, 0, T, T, 0, st))
+    canvas = torch.empty(T, H, 2 * W, 3, device=dev, dtype=torch.uint8)
+    flag = ops.video_range_flag(fr_dev)
+    srcs = [dict(tensor=fr_dev[0], mode=ops.COMPOSE_LOADER_ROUNDTRIP, flag=flag, dst=(0, 0)),
+            dict(tensor=edit_dev[0], mode=ops.COMPOSE_COPY, dst=(0, W))]
+    k_cmp = kernel_seconds(lambda: ops.frames_u8_compose(canvas, srcs))
+    k_flag = kernel_seconds(lambda: ops.video_range_flag(fr_dev))
     med = lambda v: sorted(v)[len(v) // 2]
     print(json.dumps({"what": f"frame I/O alone, {T}f@{H}x{W}, bf16 VAE dtype, {args.reps} alternating repetitions, wall seconds",
                       "seconds": res, "median": {k: med(v) for k, v in res.items()},
-                      "old_path_spread": {k: round(max(res[k]) - min(res[k]), 5) for k in ("out_old", "in_old")},
-                      "kernel_seconds": {"wan_frames_u8_to_video": round(k_in, 7), "wan_video_to_frames_u8": round(k_out, 7)},
+                      "old_path_spread": {k: round(max(res[k]) - min(res[k]), 5) for k in ("out_old", "in_old", "cmp_old")},
+                      "kernel_seconds": {"wan_frames_u8_to_video": round(k_in, 7), "wan_video_to_frames_u8": round(k_out, 7),
+                                         "wan_frames_u8_compose": round(k_cmp, 7), "wan_video_range_flag": round(k_flag, 7)},
                       "kernel_tbps": {"wan_frames_u8_to_video": round(n * 3 / k_in / 1e12, 3),
-                                      "wan_video_to_frames_u8": round(n * 3 / k_out / 1e12, 3)},
+                                      "wan_video_to_frames_u8": round(n * 3 / k_out / 1e12, 3),
+                                      "wan_frames_u8_compose": round(n * 4 / k_cmp / 1e12, 3),
+                                      "wan_video_range_flag": round(n / k_flag / 1e12, 3)},
                       "bytes": {"uint8": n, "bf16": 2 * n, "float32": 4 * n}}))
 
 

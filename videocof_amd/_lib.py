@@ -53,6 +53,18 @@ class BoxProbeResult(Structure):
     _fields_ = [("mfma_mix_tflops", c_float), ("copy_tbps", c_float), ("mfma_ms", c_float), ("copy_ms", c_float)]
 
 
+class ComposeSrc(Structure):
+    """``wan_compose_src`` of include/wan_hip.h."""
+    _fields_ = ([("base", c_void_p), ("rescale_flag", c_void_p), ("extent", c_int64)] +
+                [(n, c_int64) for n in ("stride_c", "stride_t", "stride_y", "stride_x")] +
+                [(n, c_int) for n in ("kind", "mode", "rescale", "t0", "y0", "x0", "nt", "h", "w", "dst_y", "dst_x")])
+
+
+COMPOSE_MAX_SRC = 16                                                                  # WAN_COMPOSE_MAX_SRC
+COMPOSE_U8, COMPOSE_F32, COMPOSE_BF16 = 0, 1, 2                                       # wan_compose_src.kind
+COMPOSE_COPY, COMPOSE_LOADER_ROUNDTRIP, COMPOSE_WRITER, COMPOSE_NORMALIZE = 0, 1, 2, 3  # wan_compose_src.mode
+
+
 class ConvParams(Structure):
     """``wan_conv_params`` of include/wan_hip.h."""
     _fields_ = [(n, c_int) for n in ("T_in", "H_in", "W_in", "Cin", "T_out", "H_out", "W_out", "Cout",
@@ -207,6 +219,8 @@ SIGNATURES = {
     "wan_frames_resample_table_bytes": (c_int64, [c_int, c_int]),
     "wan_frames_u8_resample": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int,
                                        c_void_p]),
+    "wan_frames_u8_compose": (c_int, [POINTER(ComposeSrc), c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "wan_video_range_flag": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_void_p]),
 }
 
 _lib = None

@@ -145,6 +145,221 @@ __global__ __launch_bounds__(256) void video_to_frames_kernel(const TIn* __restr
     }
 }
 
+// ---- compose: n_src source clips -> rectangles of one uint8 [T_out, Hc, Wc, 3] canvas, the rest of it the pad byte
+// A thread owns one 16-byte piece of a canvas row, cut at the 16-byte boundaries of the row's ADDRESS (as the resample kernel cuts
+// its output): a piece that lies inside the row is one dwordx4 store whatever Wc * 3 and the base are, the one or two pieces that
+// stick out of the row are stored byte by byte.  The destination rectangles do not overlap (checked on the host), so every source
+// that touches the piece ORs its bytes into the piece's four words and what no source touches becomes the pad byte.  A piece that lies inside ONE
+// interleaved uint8 source is read as the two aligned 16-byte words around its (arbitrarily aligned) source bytes and shifted into
+// place; everything else -- planar float sources, pieces across a rectangle's edge, words that would reach outside the source
+// tensor -- is read element by element.
+struct compose_args {
+    wan_compose_src src[WAN_COMPOSE_MAX_SRC];
+    uint8_t* canvas;
+    int n_src, Hc, Wc;
+    unsigned int pad;        // the pad byte in all four bytes of a word
+    int ppr;                 // pieces per row, an upper bound: (15 + Wc * 3 + 15) / 16
+};
+
+// fast_infer.py:188-189 `(video + 1.0) / 2.0` where the range rule asks for it, `.clamp(0.0, 1.0)`: tensor ops in the video's dtype
+// (a bf16 op computes in float32 and rounds its result to bf16; halving is exact in both).
+__device__ __forceinline__ float rescale_half(float x, bool rescale, bool bf) {
+#pragma clang fp contract(off)
+    if (rescale) {
+        float a = x + 1.0f;
+        if (bf) a = (float)(bf16_t)a;
+        x = a * 0.5f;
+        if (bf) x = (float)(bf16_t)x;
+    }
+    return x;
+}
+// utils.py:67 `(x * 255)` in float32, `.astype(np.uint8)` = truncation
+__device__ __forceinline__ unsigned int unit_to_byte(float x) {
+#pragma clang fp contract(off)
+    return (unsigned int)(fminf(fmaxf(x, 0.f), 1.f) * 255.0f);
+}
+// the writer without a clamp in front (WAN_COMPOSE_WRITER): low byte of the truncated int32 outside [0, 256)
+__device__ __forceinline__ unsigned int writer_byte(float x) {
+#pragma clang fp contract(off)
+    return (unsigned int)(int)(x * 255.0f) & 0xffu;
+}
+__device__ __forceinline__ unsigned int compose_u8(unsigned int u, int mode, bool rescale) {
+    return mode == WAN_COMPOSE_COPY ? u : unit_to_byte(rescale_half(byte_to_video(u), rescale, false));
+}
+__device__ __forceinline__ unsigned int compose_float(float x, int mode, bool rescale, bool bf) {
+    const float v = rescale_half(x, rescale, bf);
+    return mode == WAN_COMPOSE_WRITER ? writer_byte(v) : unit_to_byte(v);
+}
+
+__device__ __forceinline__ bool compose_rescale(const wan_compose_src& s) {
+    return s.rescale_flag ? *s.rescale_flag == 1 : s.rescale != 0;
+}
+
+// 16 bytes from the byte address `addr` (any alignment) out of the aligned words lo = [addr & ~15], hi = the next one
+__device__ __forceinline__ void shift16(const u32x4 lo, const u32x4 hi, int sh, unsigned int (&w)[4]) {
+    const unsigned int v[8] = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
+    const unsigned int sb = (unsigned int)sh & 3u;
+    switch (sh >> 2) {
+#define WAN_SHIFT16_CASE(o)                                                                              \
+    case o:                                                                                              \
+        _Pragma("unroll") for (int i = 0; i < 4; ++i) w[i] = __builtin_amdgcn_alignbyte(v[i + o + 1], v[i + o], sb); \
+        break;
+        WAN_SHIFT16_CASE(0)
+        WAN_SHIFT16_CASE(1)
+        WAN_SHIFT16_CASE(2)
+        default:
+        WAN_SHIFT16_CASE(3)
+#undef WAN_SHIFT16_CASE
+    }
+}
+
+__global__ __launch_bounds__(256) void frames_compose_kernel(const compose_args a) {
+    const int t = blockIdx.y;
+    const int row_bytes = a.Wc * 3;
+    const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (int64_t)a.Hc * a.ppr) return;
+    const int y = (int)((unsigned int)idx / (unsigned int)a.ppr), q = (int)idx - y * a.ppr;
+    uint8_t* row = a.canvas + ((int64_t)t * a.Hc + y) * row_bytes;
+    const int mis = (int)(reinterpret_cast<uintptr_t>(row) & 15);
+    const int b0 = 16 * q - mis;                                   // row byte at the piece's first byte (< 0 in front of the row)
+    const int lo = max(b0, 0), hi = min(b0 + 16, row_bytes);       // the piece's bytes of this row: [lo, hi)
+    if (lo >= hi) return;
+    const int xa = lo / 3, xb = (hi - 1) / 3;                      // first and last pixel it touches
+    const bool full = hi - lo == 16;
+    unsigned int w[4] = {0u, 0u, 0u, 0u}, cov[4] = {0u, 0u, 0u, 0u};   // the piece's bytes; 0xff in every byte a source has written
+
+    for (int k = 0; k < a.n_src; ++k) {
+        const wan_compose_src& s = a.src[k];
+        const int yy = y - s.dst_y;
+        if (t >= s.nt || yy < 0 || yy >= s.h || xb < s.dst_x || xa >= s.dst_x + s.w) continue;
+        const bool rescale = compose_rescale(s);
+        // element offset of (frame t, row yy, column 0) of the crop window
+        const int64_t off = (int64_t)(s.t0 + t) * s.stride_t + (int64_t)(s.y0 + yy) * s.stride_y + (int64_t)s.x0 * s.stride_x;
+        if (s.kind == WAN_COMPOSE_U8) {
+            const uint8_t* base = (const uint8_t*)s.base;
+            bool done = false;
+            if (full && xa >= s.dst_x && xb < s.dst_x + s.w && s.stride_x == 3 && s.stride_c == 1) {
+                // source byte of row byte b: off + (b - 3 * dst_x); contiguous over the piece
+                const int64_t so = off + (int64_t)b0 - 3 * (int64_t)s.dst_x;
+                const int sh = (int)((reinterpret_cast<uintptr_t>(base) + (uintptr_t)so) & 15);
+                const int64_t first = so - sh, end = first + (sh ? 32 : 16);
+                if (first >= 0 && end <= s.extent) {
+                    const u32x4* p = reinterpret_cast<const u32x4*>(base + first);
+                    const u32x4 v0 = p[0];
+                    const u32x4 v1 = sh ? p[1] : v0;
+                    shift16(v0, v1, sh, w);
+                    if (s.mode != WAN_COMPOSE_COPY) {
+                        unsigned int r[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+                        for (int j = 0; j < 16; ++j)
+                            r[j >> 2] |= compose_u8((w[j >> 2] >> ((j & 3) * 8)) & 0xffu, s.mode, rescale) << ((j & 3) * 8);
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) w[i] = r[i];
+                    }
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) cov[i] = 0xffffffffu;
+                    done = true;
+                }
+            }
+            if (!done) {
+#pragma unroll
+                for (int j = 0; j < 16; ++j) {
+                    const int b = b0 + j;
+                    if (b < lo || b >= hi) continue;
+                    const int x = (int)((unsigned int)b / 3u), c = b - 3 * x, xx = x - s.dst_x;
+                    if (xx < 0 || xx >= s.w) continue;
+                    const unsigned int u = base[off + (int64_t)xx * s.stride_x + (int64_t)c * s.stride_c];
+                    w[j >> 2] |= compose_u8(u, s.mode, rescale) << ((j & 3) * 8);
+                    cov[j >> 2] |= 0xffu << ((j & 3) * 8);
+                }
+            }
+        } else {
+            const bool bf = s.kind == WAN_COMPOSE_BF16;
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const int b = b0 + j;
+                if (b < lo || b >= hi) continue;
+                const int x = (int)((unsigned int)b / 3u), c = b - 3 * x, xx = x - s.dst_x;
+                if (xx < 0 || xx >= s.w) continue;
+                const int64_t e = off + (int64_t)xx * s.stride_x + (int64_t)c * s.stride_c;
+                const float v = bf ? (float)((const bf16_t*)s.base)[e] : ((const float*)s.base)[e];
+                w[j >> 2] |= compose_float(v, s.mode, rescale, bf) << ((j & 3) * 8);
+                cov[j >> 2] |= 0xffu << ((j & 3) * 8);
+            }
+        }
+    }
+
+#pragma unroll
+    for (int i = 0; i < 4; ++i) w[i] |= a.pad & ~cov[i];
+    uint8_t* d = row + b0;                                         // 16-byte aligned
+    if (full) {
+        *reinterpret_cast<u32x4*>(d) = u32x4{w[0], w[1], w[2], w[3]};
+    } else {
+#pragma unroll
+        for (int j = 0; j < 16; ++j)
+            if (b0 + j >= lo && b0 + j < hi) d[j] = (uint8_t)(w[j >> 2] >> ((j & 3) * 8));
+    }
+}
+
+// ---- the range rule of _normalize_to_01 (fast_infer.py:185-187) as a word in device memory
+// bit 0: an element < 0 or > 1 was seen; bit 1: a NaN was seen.  Decided on the bits of the float32 value (the library is built
+// with -fno-honor-nans, which lets the compiler fold float comparisons with a NaN).
+__device__ __forceinline__ unsigned int range_bits(float x) {
+    const unsigned int u = __float_as_uint(x), m = u & 0x7fffffffu;
+    if (m > 0x7f800000u) return 2u;
+    const bool neg = (u >> 31) != 0u && m != 0u;                   // -0.0 < 0.0 is false
+    return (neg || (!(u >> 31) && m > 0x3f800000u)) ? 1u : 0u;
+}
+template <typename T> struct range_vec;
+template <> struct range_vec<uint8_t> {
+    static constexpr int N = 16;
+    __device__ static unsigned int elem(const uint8_t* p) { return range_bits(byte_to_video(*p)); }
+    __device__ static unsigned int vec(const u32x4 v) {
+        unsigned int r = 0u;
+#pragma unroll
+        for (int j = 0; j < 16; ++j) r |= range_bits(byte_to_video((v[j >> 2] >> ((j & 3) * 8)) & 0xffu));
+        return r;
+    }
+};
+template <> struct range_vec<float> {
+    static constexpr int N = 4;
+    __device__ static unsigned int elem(const float* p) { return range_bits(*p); }
+    __device__ static unsigned int vec(const u32x4 v) {
+        return range_bits(__uint_as_float(v[0])) | range_bits(__uint_as_float(v[1])) | range_bits(__uint_as_float(v[2])) |
+               range_bits(__uint_as_float(v[3]));
+    }
+};
+template <> struct range_vec<bf16_t> {
+    static constexpr int N = 8;
+    __device__ static unsigned int elem(const bf16_t* p) { return range_bits((float)*p); }
+    __device__ static unsigned int vec(const u32x4 v) {
+        unsigned int r = 0u;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) r |= range_bits(bf16lo_to_f32(v[j])) | range_bits(bf16hi_to_f32(v[j]));
+        return r;
+    }
+};
+
+// nvec 16-byte words from x (0 when x is not 16-byte aligned), then the elements [nvec * N, n) one by one
+template <typename T>
+__global__ __launch_bounds__(256) void range_flag_kernel(const T* __restrict__ x, int64_t n, int64_t nvec, int* __restrict__ flag) {
+    using V = range_vec<T>;
+    const int64_t tid = (int64_t)blockIdx.x * 256 + threadIdx.x, step = (int64_t)gridDim.x * 256;
+    unsigned int bits = 0u;
+    const u32x4* xv = reinterpret_cast<const u32x4*>(x);
+    for (int64_t i = tid; i < nvec; i += step) bits |= V::vec(xv[i]);
+    for (int64_t i = nvec * V::N + tid; i < n; i += step) bits |= V::elem(x + i);
+    const unsigned int wave = (__any((int)(bits & 1u)) ? 1u : 0u) | (__any((int)(bits & 2u)) ? 2u : 0u);
+    if ((threadIdx.x & (WAN_WAVE - 1)) == 0 && wave) atomicOr(flag, (int)wave);
+}
+
+template <typename T> void launch_range_flag(const void* x, int64_t n, int* flag, hipStream_t s) {
+    const int64_t nvec = (uintptr_t)x % 16 == 0 ? n / range_vec<T>::N : 0;
+    const int64_t items = std::max<int64_t>(nvec, n - nvec * range_vec<T>::N);
+    const unsigned blocks = (unsigned)std::min<int64_t>((items + 255) / 256, 2048);
+    hipLaunchKernelGGL(range_flag_kernel<T>, dim3(blocks), dim3(256), 0, s, (const T*)x, n, nvec, flag);
+}
+
 // grid: x over the items (16-pixel chunks or pixels) of one frame, y = frames
 dim3 grid_for(int64_t items_per_frame, int64_t frames) {
     return dim3((unsigned)std::min<int64_t>((items_per_frame + 255) / 256, 4096), (unsigned)frames);
@@ -198,5 +413,74 @@ extern "C" wan_status_t wan_video_to_frames_u8(const void* video, int in_dtype, 
         else hipLaunchKernelGGL(video_to_frames_kernel<bf16_t>, blocks, dim3(256), 0, s, (const bf16_t*)video, dst, T, npix, t0, nt, T_out, t_dst);
     }
     WAN_CHECK_LAUNCH("wan_video_to_frames_u8");
+    return WAN_OK;
+}
+
+extern "C" wan_status_t wan_video_range_flag(const void* x, int kind, int64_t n, int* flag, void* stream) {
+    WAN_REQUIRE(x && flag, WAN_ERR_INVALID, "wan_video_range_flag: null tensor");
+    WAN_REQUIRE(kind == WAN_COMPOSE_U8 || kind == WAN_COMPOSE_F32 || kind == WAN_COMPOSE_BF16, WAN_ERR_INVALID,
+                "wan_video_range_flag: kind=%d (0 uint8, 1 fp32, 2 bf16)", kind);
+    WAN_REQUIRE(n > 0, WAN_ERR_INVALID, "wan_video_range_flag: n=%lld elements", (long long)n);
+    hipStream_t s = (hipStream_t)stream;
+    const hipError_t e = hipMemsetAsync(flag, 0, sizeof(int), s);
+    WAN_REQUIRE(e == hipSuccess, WAN_ERR_LAUNCH, "wan_video_range_flag: hipMemsetAsync: %s", hipGetErrorString(e));
+    if (kind == WAN_COMPOSE_U8) launch_range_flag<uint8_t>(x, n, flag, s);
+    else if (kind == WAN_COMPOSE_F32) launch_range_flag<float>(x, n, flag, s);
+    else launch_range_flag<bf16_t>(x, n, flag, s);
+    WAN_CHECK_LAUNCH("wan_video_range_flag");
+    return WAN_OK;
+}
+
+extern "C" wan_status_t wan_frames_u8_compose(const wan_compose_src* srcs, int n_src, void* canvas_u8, int T_out, int Hc, int Wc,
+                                              int pad, void* stream) {
+    WAN_REQUIRE(srcs && canvas_u8, WAN_ERR_INVALID, "wan_frames_u8_compose: null argument");
+    WAN_REQUIRE(n_src >= 0 && n_src <= WAN_COMPOSE_MAX_SRC, n_src < 0 ? WAN_ERR_INVALID : WAN_ERR_UNSUPPORTED,
+                "wan_frames_u8_compose: n_src=%d sources (at most %d per canvas)", n_src, WAN_COMPOSE_MAX_SRC);
+    WAN_REQUIRE(T_out > 0 && Hc > 0 && Wc > 0, WAN_ERR_INVALID, "wan_frames_u8_compose: bad canvas T=%d H=%d W=%d", T_out, Hc, Wc);
+    compose_args a;
+    a.canvas = (uint8_t*)canvas_u8;
+    a.n_src = n_src; a.Hc = Hc; a.Wc = Wc;
+    WAN_REQUIRE(pad >= 0 && pad <= 255, WAN_ERR_INVALID, "wan_frames_u8_compose: pad=%d is no byte", pad);
+    a.pad = (unsigned int)pad * 0x01010101u;
+    WAN_REQUIRE(T_out <= 65535 && Wc <= (1 << 28), WAN_ERR_UNSUPPORTED, "wan_frames_u8_compose: canvas T=%d W=%d too large", T_out, Wc);
+    a.ppr = (15 + Wc * 3 + 15) / 16;
+    const int64_t items = (int64_t)Hc * a.ppr;
+    WAN_REQUIRE(items < (1ll << 31), WAN_ERR_UNSUPPORTED, "wan_frames_u8_compose: canvas frame %d x %d too large", Hc, Wc);
+    for (int k = 0; k < n_src; ++k) {
+        wan_compose_src s = srcs[k];
+        WAN_REQUIRE(s.base && s.extent > 0, WAN_ERR_INVALID, "wan_frames_u8_compose: source %d: null or empty tensor", k);
+        const bool u8 = s.kind == WAN_COMPOSE_U8, fl = s.kind == WAN_COMPOSE_F32 || s.kind == WAN_COMPOSE_BF16;
+        WAN_REQUIRE(u8 || fl, WAN_ERR_INVALID, "wan_frames_u8_compose: source %d: kind=%d (0 uint8, 1 fp32, 2 bf16)", k, s.kind);
+        WAN_REQUIRE(u8 ? (s.mode == WAN_COMPOSE_COPY || s.mode == WAN_COMPOSE_LOADER_ROUNDTRIP)
+                       : (s.mode == WAN_COMPOSE_WRITER || s.mode == WAN_COMPOSE_NORMALIZE),
+                    WAN_ERR_INVALID, "wan_frames_u8_compose: source %d: mode=%d does not go with kind=%d", k, s.mode, s.kind);
+        WAN_REQUIRE(s.mode != WAN_COMPOSE_NORMALIZE || s.rescale_flag, WAN_ERR_INVALID,
+                    "wan_frames_u8_compose: source %d: NORMALIZE needs the flag of wan_video_range_flag", k);
+        WAN_REQUIRE((s.mode != WAN_COMPOSE_WRITER && s.mode != WAN_COMPOSE_COPY) || !s.rescale_flag, WAN_ERR_INVALID,
+                    "wan_frames_u8_compose: source %d: mode=%d takes no rescale flag", k, s.mode);
+        if (s.mode == WAN_COMPOSE_LOADER_ROUNDTRIP && !s.rescale_flag) s.rescale = 1;       // the loader's video always has a byte < 128
+        WAN_REQUIRE(s.stride_c >= 0 && s.stride_t >= 0 && s.stride_y >= 0 && s.stride_x >= 0, WAN_ERR_UNSUPPORTED,
+                    "wan_frames_u8_compose: source %d: negative stride", k);
+        WAN_REQUIRE(s.t0 >= 0 && s.y0 >= 0 && s.x0 >= 0 && s.nt > 0 && s.h > 0 && s.w > 0, WAN_ERR_INVALID,
+                    "wan_frames_u8_compose: source %d: window (t0=%d y0=%d x0=%d nt=%d h=%d w=%d)", k, s.t0, s.y0, s.x0, s.nt, s.h, s.w);
+        const __int128 last = (__int128)2 * s.stride_c + ((__int128)s.t0 + s.nt - 1) * s.stride_t +
+                              ((__int128)s.y0 + s.h - 1) * s.stride_y + ((__int128)s.x0 + s.w - 1) * s.stride_x;
+        WAN_REQUIRE(last < (__int128)s.extent, WAN_ERR_INVALID,
+                    "wan_frames_u8_compose: source %d: window (t0=%d y0=%d x0=%d nt=%d h=%d w=%d) reads outside its %lld elements", k,
+                    s.t0, s.y0, s.x0, s.nt, s.h, s.w, (long long)s.extent);
+        WAN_REQUIRE(s.nt <= T_out && s.dst_y >= 0 && s.dst_x >= 0 && (int64_t)s.dst_y + s.h <= Hc && (int64_t)s.dst_x + s.w <= Wc,
+                    WAN_ERR_INVALID, "wan_frames_u8_compose: source %d: %d frames of %d x %d at (%d, %d) leave the %d x %d x %d canvas", k,
+                    s.nt, s.h, s.w, s.dst_y, s.dst_x, T_out, Hc, Wc);
+        for (int j = 0; j < k; ++j) {
+            const wan_compose_src& o = a.src[j];
+            WAN_REQUIRE(s.dst_y >= o.dst_y + o.h || o.dst_y >= s.dst_y + s.h || s.dst_x >= o.dst_x + o.w || o.dst_x >= s.dst_x + s.w,
+                        WAN_ERR_INVALID, "wan_frames_u8_compose: sources %d and %d overlap on the canvas", j, k);
+        }
+        a.src[k] = s;
+    }
+    for (int k = n_src; k < WAN_COMPOSE_MAX_SRC; ++k) a.src[k] = wan_compose_src{};
+    const dim3 grid((unsigned)((items + 255) / 256), (unsigned)T_out);
+    hipLaunchKernelGGL(frames_compose_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
+    WAN_CHECK_LAUNCH("wan_frames_u8_compose");
     return WAN_OK;
 }

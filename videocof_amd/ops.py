@@ -993,6 +993,79 @@ def frames_u8_resample(frames: torch.Tensor, out_height: int, out_width: int, xt
     return out
 
 
+_COMPOSE_KIND = {torch.uint8: _lib.COMPOSE_U8, torch.float32: _lib.COMPOSE_F32, torch.bfloat16: _lib.COMPOSE_BF16}
+COMPOSE_COPY, COMPOSE_LOADER_ROUNDTRIP, COMPOSE_WRITER, COMPOSE_NORMALIZE = (
+    _lib.COMPOSE_COPY, _lib.COMPOSE_LOADER_ROUNDTRIP, _lib.COMPOSE_WRITER, _lib.COMPOSE_NORMALIZE)
+
+
+@_on_tensor_device
+def video_range_flag(x: torch.Tensor) -> torch.Tensor:
+    """``_normalize_to_01``'s range rule (fast_infer.py:185-187) over every element of ``x`` (float32 | bfloat16, or uint8 frames
+    standing for the loader's float video of them) as an int32 ``[1]`` ON THE DEVICE (``wan_video_range_flag``): 1 = rescale by
+    ``(x + 1) / 2``.  Nothing is read back; ``frames_u8_compose`` takes the tensor as a source's ``flag``."""
+    if x.dtype not in _COMPOSE_KIND:
+        raise ValueError(f"video_range_flag.x: expected uint8, float32 or bfloat16, got {x.dtype}")
+    _need(x, x.dtype, "video_range_flag.x")
+    x = x.contiguous()
+    if x.numel() == 0:
+        raise ValueError("video_range_flag.x: empty tensor")
+    flag = torch.empty(1, device=x.device, dtype=torch.int32)
+    _lib.check(_lib.load().wan_video_range_flag(_p(x), _COMPOSE_KIND[x.dtype], x.numel(), _p(flag), _stream()), "wan_video_range_flag")
+    return flag
+
+
+@_on_tensor_device
+def frames_u8_compose(canvas: torch.Tensor, sources, pad: int = 0) -> torch.Tensor:
+    """Place clips into rectangles of ``canvas`` (a contiguous uint8 [T_out, Hc, Wc, 3] device tensor; EVERY byte of it is written,
+    what no source covers with the byte ``pad``) in one launch of ``wan_frames_u8_compose``.  ``sources``: dicts with
+
+        tensor   uint8 [T, H, W, 3] (the three channels of a pixel adjacent) or float32 / bfloat16 [3, T, H, W]; any other strides
+        mode     COMPOSE_COPY | COMPOSE_LOADER_ROUNDTRIP (uint8), COMPOSE_WRITER | COMPOSE_NORMALIZE (float): include/wan_hip.h
+        window   (t0, y0, x0, nt, h, w) of the tensor; default: all of it
+        dst      (y, x) on the canvas; default (0, 0)
+        rescale  WRITER's ``rescale``
+        flag     the int32 device tensor of ``video_range_flag`` (NORMALIZE: required; LOADER_ROUNDTRIP: optional)
+    """
+    _need(canvas, torch.uint8, "frames_u8_compose.canvas")
+    if canvas.dim() != 4 or canvas.shape[-1] != 3 or not canvas.is_contiguous():
+        raise ValueError(f"frames_u8_compose.canvas: expected a contiguous [T, H, W, 3], got {tuple(canvas.shape)}")
+    sources = list(sources)
+    if len(sources) > _lib.COMPOSE_MAX_SRC:
+        raise RuntimeError(f"frames_u8_compose: {len(sources)} sources; the kernel takes {_lib.COMPOSE_MAX_SRC} per canvas")
+    arr = (_lib.ComposeSrc * max(len(sources), 1))()
+    for k, s in enumerate(sources):
+        t = s["tensor"]
+        if t.dtype not in _COMPOSE_KIND:
+            raise ValueError(f"frames_u8_compose.sources[{k}]: expected uint8, float32 or bfloat16, got {t.dtype}")
+        if not t.is_cuda:
+            raise RuntimeError(f"frames_u8_compose.sources[{k}]: tensor is on {t.device}; the HIP path has no CPU fallback")
+        u8 = t.dtype == torch.uint8
+        if t.dim() != 4 or t.shape[-1 if u8 else 0] != 3 or t.device != canvas.device:
+            raise ValueError(f"frames_u8_compose.sources[{k}]: expected {'[T, H, W, 3]' if u8 else '[3, T, H, W]'} on {canvas.device}, "
+                             f"got {tuple(t.shape)} on {t.device}")
+        T, H, W = (t.shape[0], t.shape[1], t.shape[2]) if u8 else (t.shape[1], t.shape[2], t.shape[3])
+        st = t.stride()
+        d = arr[k]
+        d.stride_t, d.stride_y, d.stride_x, d.stride_c = (st[0], st[1], st[2], st[3]) if u8 else (st[1], st[2], st[3], st[0])
+        d.base = t.data_ptr()
+        d.extent = t.untyped_storage().nbytes() // t.element_size() - t.storage_offset()
+        d.kind, d.mode, d.rescale = _COMPOSE_KIND[t.dtype], int(s["mode"]), int(bool(s.get("rescale", False)))
+        d.t0, d.y0, d.x0, d.nt, d.h, d.w = (int(v) for v in s.get("window", (0, 0, 0, T, H, W)))
+        if d.t0 + d.nt > T or d.y0 + d.h > H or d.x0 + d.w > W:
+            raise ValueError(f"frames_u8_compose.sources[{k}]: window {tuple(s['window'])} of a {T} x {H} x {W} clip")
+        d.dst_y, d.dst_x = (int(v) for v in s.get("dst", (0, 0)))
+        flag = s.get("flag")
+        if flag is not None:
+            _need(flag, torch.int32, f"frames_u8_compose.sources[{k}].flag")
+            if flag.numel() != 1 or flag.device != canvas.device:
+                raise ValueError(f"frames_u8_compose.sources[{k}].flag: expected one int32 on {canvas.device}")
+            d.rescale_flag = flag.data_ptr()
+    T_out, Hc, Wc, _ = canvas.shape
+    _lib.check(_lib.load().wan_frames_u8_compose(arr, len(sources), _p(canvas), T_out, Hc, Wc, int(pad), _stream()),
+               "wan_frames_u8_compose")
+    return canvas
+
+
 @_on_tensor_device
 def lincomb(terms, out_dtype: torch.dtype) -> torch.Tensor:
     """sum_i c_i * x_i over <= 4 same-shape CUDA tensors in one pass (fp32 accumulate); `terms` is a list

@@ -41,6 +41,7 @@ class WanPipelineOutput:
     ground_videos: Optional[Union[torch.Tensor, np.ndarray]] = None
     edit_videos: Optional[Union[torch.Tensor, np.ndarray]] = None
     latents: Optional[torch.Tensor] = None          # extension: final latents (output_type="latent")
+    compare_videos: Optional[Union[torch.Tensor, np.ndarray]] = None   # extension: source | edit side by side (compare=True)
 
 
 class WanPipeline:
@@ -258,14 +259,17 @@ class WanPipeline:
     def attention_kwargs(self):
         return getattr(self, "_attention_kwargs", None)
 
-    def _decode_frames_u8(self, latents, out, clip=None, dst_frame=0) -> np.ndarray:
+    def _decode_frames_u8(self, latents, out, clip=None, dst_frame=0, keep=None) -> np.ndarray:
         """decode, then wan_video_to_frames_u8 into frames [dst_frame, dst_frame + T) of the device clip `clip` (uint8
         [B, T_clip, H, W, 3]; None = one of exactly T frames), then ONE asynchronous copy per sample of that frame range -- one
-        contiguous run of bytes -- into `out`, a page-locked uint8 [B, T, H, W, 3] host tensor (or a frame slice of one)."""
+        contiguous run of bytes -- into `out`, a page-locked uint8 [B, T, H, W, 3] host tensor (or a frame slice of one).
+        `keep`: a list that receives the device frames of the segment (the compare clip is composed from them)."""
         from . import ops
         frames = self.vae.decode(latents.to(self.vae.dtype)).sample
         clip = ops.video_to_frames_u8(frames, out=clip, dst_frame=dst_frame)
         seg = clip[:, dst_frame:dst_frame + frames.shape[2]]
+        if keep is not None:
+            keep.append(seg)
         if out is None:
             out = torch.empty(seg.shape, dtype=torch.uint8, pin_memory=True)
         if tuple(out.shape) != tuple(seg.shape) or out.dtype != torch.uint8:
@@ -319,7 +323,24 @@ class WanPipeline:
                  # extensions of this package (keyword-only in spirit; the names above are the reference's, :516-548)
                  source_latents: Optional[torch.Tensor] = None, device=None,
                  weight_dtype: torch.dtype = torch.bfloat16, cache_context: bool = True,
-                 skip_source_prediction: bool = True, capture_graph=False):
+                 skip_source_prediction: bool = True, capture_graph=False, **switches):
+        # `compare=False` is the one keyword in `switches` (as `as_uint8` is decode_latents'): the named parameters stay the reference's
+        # plus the extensions tests/test_oracle_vs_reference.py lists.  compare=True: also return the reference's compare clip (save_side_by_side, fast_infer.py:183-206, as its writer's bytes) in
+        # `compare_videos`, composed on the device from the uint8 source frames and the edit segment (video_io.compare_frames)
+        compare = bool(switches.pop("compare", False))
+        if switches:
+            raise TypeError(f"__call__() got an unexpected keyword argument {next(iter(switches))!r}")
+        compare_source = None
+        if compare:
+            if output_type != "uint8":
+                raise ValueError(f"compare=True composes the compare clip from uint8 frames on the device: it needs "
+                                 f"output_type='uint8', not {output_type!r}")
+            compare_source = torch.from_numpy(video) if isinstance(video, np.ndarray) else video
+            if not torch.is_tensor(compare_source) or compare_source.dtype != torch.uint8 or compare_source.dim() not in (4, 5) \
+                    or compare_source.shape[-1] != 3:
+                raise ValueError("compare=True needs the uint8 source frames as `video` ([T, H, W, 3] or [B, T, H, W, 3]), got "
+                                 f"{getattr(compare_source, 'dtype', type(compare_source))} "
+                                 f"{tuple(getattr(compare_source, 'shape', ()))}")
         # `timesteps`: with either scheduler built here the reference never looks at it (pipeline_wan.py:613-621: UniPC takes
         # set_timesteps(num_inference_steps, device=, shift=), DPM++ the sigmas of get_sampling_sigmas); accepted and ignored here too.
         del timesteps
@@ -499,7 +520,8 @@ class WanPipeline:
 
         # -- decode (:757-790)
         t_stage = self._stage("vae_decode")
-        ground_video = edit_video = video_out = None
+        ground_video = edit_video = video_out = compare_out = None
+        edit_dev = [] if compare else None         # the edit segment's device frames, kept for the compare clip only
         if output_type in ("numpy", "uint8"):
             u8 = output_type == "uint8"      # uint8 [B, T, H, W, 3] frames (wan_video_to_frames_u8) instead of float32 [B, 3, T, H, W]
             if self.vae is None:
@@ -523,7 +545,7 @@ class WanPipeline:
                     if ng:
                         ground_video = self._decode_frames_u8(latents[:, :, g0:g1], clip[:, :ng], dev_clip, 0)
                     if ne:
-                        edit_video = self._decode_frames_u8(latents[:, :, g1:], clip[:, ng:], dev_clip, ng)
+                        edit_video = self._decode_frames_u8(latents[:, :, g1:], clip[:, ng:], dev_clip, ng, edit_dev)
                     video_out = clip.numpy()
                 elif not u8:
                     if latents.is_cuda and ng + ne > 0:
@@ -539,13 +561,24 @@ class WanPipeline:
                     video_out = clip.numpy() if clip is not None else np.concatenate(parts, axis=2)
             else:
                 if condition_count < Ftot:
-                    edit_video = self.decode_latents(latents[:, :, condition_count:], as_uint8=u8)
+                    if compare:
+                        edit_video = self._decode_frames_u8(latents[:, :, condition_count:], None, keep=edit_dev)
+                    else:
+                        edit_video = self.decode_latents(latents[:, :, condition_count:], as_uint8=u8)
                 video_out = edit_video
+            if edit_dev:
+                from . import video_io
+                src = (compare_source if compare_source.dim() == 5 else compare_source.unsqueeze(0)).to(edit_dev[0].device)
+                T, H, W = (min(int(a), int(b)) for a, b in zip(src.shape[1:4], edit_dev[0].shape[1:4]))
+                pinned = torch.empty((edit_dev[0].shape[0], T, H, 2 * W, 3), dtype=torch.uint8, pin_memory=True)
+                compare_out = video_io.compare_frames(src, edit_dev[0], out=pinned).numpy()
             if not return_dict:
                 video_out = torch.from_numpy(video_out) if isinstance(video_out, np.ndarray) else video_out
                 ground_video = torch.from_numpy(ground_video) if isinstance(ground_video, np.ndarray) else ground_video
                 edit_video = torch.from_numpy(edit_video) if isinstance(edit_video, np.ndarray) else edit_video
+                compare_out = torch.from_numpy(compare_out) if isinstance(compare_out, np.ndarray) else compare_out
         elif output_type != "latent":
             raise ValueError(f"output_type {output_type!r} not supported ('numpy', 'uint8' or 'latent')")
         self._stage("vae_decode", t_stage)
-        return WanPipelineOutput(videos=video_out, ground_videos=ground_video, edit_videos=edit_video, latents=latents)
+        return WanPipelineOutput(videos=video_out, ground_videos=ground_video, edit_videos=edit_video, latents=latents,
+                                 compare_videos=compare_out)

@@ -20,6 +20,14 @@ centre crop, videox_fun/data/dataset_image_video.py:464-477), ``fit_frames`` run
 ``WanPipeline.__call__`` and ``restore_frames`` brings the edit back to the clip's size after it (``wan_frames_u8_resample``, one
 launch each).  The filter is the 8-bit antialiased triangle in integers; ``reference_fit_frames`` restates it
 in numpy and is what the kernel equals bit for bit.
+
+What the writer makes of more than one sample, and the compare clip: ``grid_frames`` is ``save_videos_grid`` up to the encoder
+(videox_fun/utils/utils.py:59-68: the ``make_grid(nrow=6)`` mosaic with its 2-pixel zero border, ``rescale``, the byte conversion)
+and ``compare_frames`` is ``save_side_by_side`` (fast_infer.py:183-206: ``_normalize_to_01`` of source and edit, the crop to the
+common T/H/W, ``torch.cat(dim=4)``) followed by that writer -- both one launch of ``wan_frames_u8_compose`` per clip, the range
+rule of ``_normalize_to_01`` decided on the device (``wan_video_range_flag``).  The left half of the compare clip is NOT the
+source's bytes: the reference shows ``trunc(((u * (2 / 255) - 1) + 1) / 2 * 255)`` in float32, which moves some byte values.
+``reference_grid_frames`` / ``reference_compare_frames`` restate the host code in torch.
 """
 from __future__ import annotations
 
@@ -34,7 +42,8 @@ import torch
 from . import ops
 
 __all__ = ["frames_to_video", "video_to_frames", "load_video_frames", "reference_frames_to_video", "reference_video_to_frames",
-           "fit_size", "fit_plan", "FitPlan", "fit_frames", "restore_frames", "reference_fit_frames"]
+           "fit_size", "fit_plan", "FitPlan", "fit_frames", "restore_frames", "reference_fit_frames",
+           "grid_layout", "grid_frames", "compare_frames", "reference_grid_frames", "reference_compare_frames"]
 
 COEF_BITS = 22                  # fixed-point bits of a filter coefficient: 8 + 22 bits of product and a sum of weights of 1 fit 32 bits
 MAX_TAPS = 24                   # WAN_RESAMPLE_MAX_TAPS of include/wan_hip.h: an 11x downscale
@@ -299,3 +308,150 @@ def restore_frames(frames_u8, height: int, width: int, out: Optional[torch.Tenso
     out.copy_(res.contiguous(), non_blocking=True)
     torch.cuda.current_stream(res.device).synchronize()
     return out
+
+
+# ---------------------------------------------------------------------------------------------- the writer's grid, the compare clip
+GRID_PADDING = 2                # torchvision.utils.make_grid's default, which save_videos_grid leaves as it is (pad_value 0)
+
+
+def grid_layout(batch: int, height: int, width: int, n_rows: int = 6):
+    """torchvision's ``make_grid(nrow=n_rows, padding=2)`` of ``batch`` images of ``height`` x ``width``:
+    ``(canvas_height, canvas_width, [(y, x) of sample k])``.  One image is returned as it is, without a border."""
+    batch, height, width, n_rows = int(batch), int(height), int(width), int(n_rows)
+    if batch < 1 or height < 1 or width < 1 or n_rows < 1:
+        raise ValueError(f"grid_layout: batch={batch} height={height} width={width} n_rows={n_rows}")
+    if batch == 1:
+        return height, width, [(0, 0)]
+    xmaps = min(n_rows, batch)
+    ymaps = -(-batch // xmaps)
+    ch, cw = height + GRID_PADDING, width + GRID_PADDING
+    return (ymaps * ch + GRID_PADDING, xmaps * cw + GRID_PADDING,
+            [(GRID_PADDING + (k // xmaps) * ch, GRID_PADDING + (k % xmaps) * cw) for k in range(batch)])
+
+
+def _videos_kind(videos, what: str):
+    """-> (is_uint8, B, T, H, W) of float ``[B, 3, T, H, W]`` or uint8 ``[B, T, H, W, 3]``."""
+    if not torch.is_tensor(videos) or videos.dim() != 5:
+        raise ValueError(f"{what}: expected float32 / bfloat16 [B, 3, T, H, W] or uint8 [B, T, H, W, 3], got "
+                         f"{getattr(videos, 'dtype', type(videos))} {tuple(getattr(videos, 'shape', ()))}")
+    if videos.dtype == torch.uint8 and videos.shape[-1] == 3:
+        return (True,) + tuple(int(v) for v in videos.shape[:4])
+    if videos.dtype in (torch.float32, torch.bfloat16) and videos.shape[1] == 3:
+        return (False, int(videos.shape[0])) + tuple(int(v) for v in videos.shape[2:])
+    raise ValueError(f"{what}: expected float32 / bfloat16 [B, 3, T, H, W] or uint8 [B, T, H, W, 3], got {videos.dtype} "
+                     f"{tuple(videos.shape)}")
+
+
+def _need_device(t: torch.Tensor, what: str) -> None:
+    if not t.is_cuda:
+        raise RuntimeError(f"{what}: tensor is on {t.device}; the HIP path has no CPU fallback")
+
+
+def _to_host(res: torch.Tensor, out: Optional[torch.Tensor], what: str) -> torch.Tensor:
+    """``out`` = a page-locked uint8 host tensor of the result's shape, filled by one copy (as ``restore_frames`` fills its own)."""
+    if out is None:
+        return res
+    if out.dtype != torch.uint8 or tuple(out.shape) != tuple(res.shape) or out.is_cuda or not out.is_contiguous():
+        raise ValueError(f"{what}: out {out.dtype} {tuple(out.shape)} on {out.device} for uint8 host frames {tuple(res.shape)}")
+    out.copy_(res, non_blocking=True)
+    torch.cuda.current_stream(res.device).synchronize()
+    return out
+
+
+def grid_frames(videos: torch.Tensor, rescale: bool = False, n_rows: int = 6, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The frames ``save_videos_grid(videos, rescale=rescale, n_rows=n_rows)`` hands to its encoder (utils.py:59-68), made on the
+    device: float32 / bfloat16 ``[B, 3, T, H, W]`` -> uint8 ``[T, Hg, Wg, 3]``, ``trunc(x * 255)`` (of ``(x + 1) / 2`` with
+    ``rescale``) of every sample at its place in ``grid_layout``; the border and the unused cells of a last row are the writer's
+    byte of ``make_grid``'s 0: 0, or 127 = ``trunc((0 + 1) / 2 * 255)`` with ``rescale``, which the reference applies to the whole grid.  uint8
+    ``[B, T, H, W, 3]`` frames (``output_type="uint8"``) are laid out as they are (``rescale`` does not apply to bytes).  One sample
+    gives its own frames, no border.  ``out``: a page-locked uint8 host tensor of the result's shape, filled by one copy."""
+    u8, B, T, H, W = _videos_kind(videos, "grid_frames")
+    _need_device(videos, "grid_frames")
+    if u8 and rescale:
+        raise ValueError("grid_frames: rescale applies to float videos, not to uint8 frames")
+    hg, wg, cells = grid_layout(B, H, W, n_rows)
+    canvas = torch.empty(T, hg, wg, 3, device=videos.device, dtype=torch.uint8)
+    mode = ops.COMPOSE_COPY if u8 else ops.COMPOSE_WRITER
+    ops.frames_u8_compose(canvas, [dict(tensor=videos[k], mode=mode, rescale=rescale, dst=cells[k]) for k in range(B)],
+                          pad=127 if rescale else 0)
+    return _to_host(canvas, out, "grid_frames")
+
+
+def compare_frames(source: torch.Tensor, edit: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The frames of the reference's compare clip (``save_side_by_side``, fast_infer.py:183-206, then the writer), made on the
+    device: uint8 ``[B, T', H', 2 W', 3]`` with ``T'``, ``H'``, ``W'`` the smaller of the two clips' along each axis (both are cropped
+    from the start of the axis), the source on the left, the edit on the right.
+
+    ``source``: the uint8 ``[B, T, H, W, 3]`` frames the clip was loaded from -- shown as the reference shows the float video its
+    loader makes of them (``LOADER_ROUNDTRIP``, include/wan_hip.h) -- or that float video ``[B, 3, T, H, W]`` itself.  ``edit``: the
+    uint8 frames of ``output_type="uint8"`` (the writer's bytes of a video in [0, 1], which ``_normalize_to_01`` leaves alone: copied)
+    or the float video.  A float clip goes through ``_normalize_to_01``; whether it rescales is decided on the device over the whole
+    tensor, as there.  ``out``: a page-locked uint8 host tensor of the result's shape, filled by one copy."""
+    su8, B, Ts, Hs, Ws = _videos_kind(source, "compare_frames.source")
+    eu8, Be, Te, He, We = _videos_kind(edit, "compare_frames.edit")
+    _need_device(source, "compare_frames.source")
+    _need_device(edit, "compare_frames.edit")
+    if B != Be or source.device != edit.device:
+        raise ValueError(f"compare_frames: {B} source clips on {source.device}, {Be} edits on {edit.device}")
+    T, H, W = min(Ts, Te), min(Hs, He), min(Ws, We)
+    sflag = ops.video_range_flag(source)
+    eflag = None if eu8 else ops.video_range_flag(edit)
+    canvas = torch.empty(B, T, H, 2 * W, 3, device=source.device, dtype=torch.uint8)
+    for b in range(B):
+        left = dict(tensor=source[b], mode=ops.COMPOSE_LOADER_ROUNDTRIP if su8 else ops.COMPOSE_NORMALIZE, flag=sflag,
+                    window=(0, 0, 0, T, H, W), dst=(0, 0))
+        right = dict(tensor=edit[b], mode=ops.COMPOSE_COPY if eu8 else ops.COMPOSE_NORMALIZE, flag=eflag,
+                     window=(0, 0, 0, T, H, W), dst=(0, W))
+        ops.frames_u8_compose(canvas[b], [left, right])
+    return _to_host(canvas, out, "compare_frames")
+
+
+def _reference_normalize_to_01(video: torch.Tensor) -> torch.Tensor:
+    """fast_infer.py:183-189."""
+    vmin = float(video.min())
+    vmax = float(video.max())
+    if vmin < 0.0 or vmax > 1.0:
+        video = (video + 1.0) / 2.0
+    return video.clamp(0.0, 1.0)
+
+
+def _reference_writer_bytes(x: torch.Tensor) -> torch.Tensor:
+    """utils.py:67 ``(x * 255).numpy().astype(np.uint8)`` (truncation), on float32 (a bfloat16 tensor has no numpy form: ``.float()``
+    first, as the pipeline's ``decode_latents`` does before its frames reach the writer)."""
+    return torch.from_numpy((x.float() * 255).numpy().astype(np.uint8))
+
+
+def reference_grid_frames(videos: torch.Tensor, rescale: bool = False, n_rows: int = 6) -> torch.Tensor:
+    """utils.py:60-67 on the host: ``[B, 3, T, H, W]`` -> uint8 ``[T, Hg, Wg, 3]`` (``make_grid`` restated by ``grid_layout``: a
+    zero canvas, sample k copied to its cell).  uint8 ``[B, T, H, W, 3]`` frames are laid out as bytes."""
+    u8, B, T, H, W = _videos_kind(videos, "reference_grid_frames")
+    x = videos.detach().cpu()
+    x = x.permute(1, 0, 4, 2, 3) if u8 else x.permute(2, 0, 1, 3, 4)          # "b c t h w -> t b c h w"
+    hg, wg, cells = grid_layout(B, H, W, n_rows)
+    grid = torch.zeros(T, 3, hg, wg, dtype=x.dtype)
+    for k, (y0, x0) in enumerate(cells):
+        grid[:, :, y0:y0 + H, x0:x0 + W] = x[:, k]
+    grid = grid.permute(0, 2, 3, 1)                                            # .transpose(0, 1).transpose(1, 2) per frame
+    if u8:
+        return grid.contiguous()
+    if rescale:
+        grid = (grid + 1.0) / 2.0
+    return _reference_writer_bytes(grid).contiguous()
+
+
+def reference_compare_frames(source: torch.Tensor, edit: torch.Tensor) -> torch.Tensor:
+    """fast_infer.py:192-205 and the writer on the host -> uint8 ``[B, T', H', 2 W', 3]`` (one grid-less clip per sample).  uint8
+    source frames first become the loader's float32 video (fast_infer.py:88-90); uint8 edit frames are the writer's bytes of a
+    video in [0, 1] already -- ``_normalize_to_01`` and the writer give those bytes back -- and are placed as they are."""
+    su8, B, _, _, _ = _videos_kind(source, "reference_compare_frames.source")
+    eu8, Be, _, _, _ = _videos_kind(edit, "reference_compare_frames.edit")
+    if B != Be:
+        raise ValueError(f"reference_compare_frames: {B} source clips, {Be} edits")
+    a = source.detach().cpu()
+    a = _reference_normalize_to_01(reference_frames_to_video(a) if su8 else a)
+    b = edit.detach().cpu()
+    b = b.permute(0, 4, 1, 2, 3) if eu8 else _reference_normalize_to_01(b)
+    T, H, W = min(a.shape[2], b.shape[2]), min(a.shape[3], b.shape[3]), min(a.shape[4], b.shape[4])
+    a = _reference_writer_bytes(a[:, :, :T, :H, :W])                           # the writer is element-wise: bytes before the cat
+    b = b[:, :, :T, :H, :W] if eu8 else _reference_writer_bytes(b[:, :, :T, :H, :W])
+    return torch.cat([a, b], dim=4).permute(0, 2, 3, 4, 1).contiguous()
