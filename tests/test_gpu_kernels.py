@@ -305,6 +305,54 @@ def test_attention_ragged_batch_long_launch_skips_the_split_tail():
         ops.attention_fwd(q, k, vt, H, k_lens=torch.tensor([kv, kv], device=DEV, dtype=torch.int32))
 
 
+def test_attention_launcher_launches_what_the_plan_says():
+    """One plan per call (csrc/attn_api.cpp), carried out by wan_attn_launch (csrc/attn_fwd.hip): what a launch reports through
+    "last_attn_variant" is what wan_attention_plan answers for the same shape, flags and the workspace size actually passed -- on the
+    persistent cross-attention form and its one-workgroup-per-block twin (bit-equal outputs), on the lazy / max-free forms of a
+    pre-scaled call, on the fp8-QK^T and all-fp8 entry points, and on a ragged call (the uniform plan less its split tail)."""
+    lib = _lib.load()
+
+    def plan(B, Lq, Lk, H, flags):
+        return lib.wan_attention_plan(B, Lq, Lk, H, 128, flags, lib.wan_attention_workspace_bytes(B, Lq, Lk, H, 128))
+
+    def last():
+        return ops.get_tuning("last_attn_variant")
+    g = torch.Generator().manual_seed(21)
+
+    def operands(Lq, Lk, H):
+        q, k, v = (bf(torch.randn(1, n, H * 128, generator=g)).to(DEV) for n in (Lq, Lk, Lk))
+        return q, k, torch.stack([ops.transpose_pad(v[0])])
+    try:
+        Lq, Lk, H = 8448, 512, 8                  # 33 query blocks x 8 heads = 264 workgroups' worth on 256 CUs: the persistent form runs
+        q, k, vt = operands(Lq, Lk, H)
+        outs = []
+        for persist in (0, 1):
+            ops.set_tuning("attn_persist", persist)
+            outs.append(ops.attention_fwd(q, k, vt, H))
+            assert last() == plan(1, Lq, Lk, H, 0) and last() & 15 == 1
+        assert torch.equal(outs[0], outs[1])
+        Lq, Lk, H = 600, 1300, 2
+        q, k, vt = operands(Lq, Lk, H)
+        q8, k8 = (q.float() * 4.0).clamp(-448, 448).to(ops.FP8), (k.float() * 4.0).clamp(-448, 448).to(ops.FP8)
+        v8, vs = ops.vt_quantize_mx(vt, H, Lk)
+        for fast, family in ((0, 1), (2, 2)):
+            ops.set_tuning("attn_fast", fast)
+            ops.attention_fwd(q, k, vt, H, q_prescaled=True)
+            assert last() == plan(1, Lq, Lk, H, _lib.ATTN_Q_PRESCALED) and last() & 15 == family
+            ops.attention_fwd_qk8(q8, k8, vt, H, 2, 2)
+            assert last() == plan(1, Lq, Lk, H, _lib.ATTN_Q_PRESCALED | 2) and last() & 15 == 4         # | WAN_ATTN_QK_FP8
+            ops.attention_fwd_f8(q8, k8, v8, vs, vt, H, 2, 2)
+            assert last() == plan(1, Lq, Lk, H, _lib.ATTN_Q_PRESCALED | 2 | 4) and last() & 15 == 5     # | WAN_ATTN_PV_FP8
+    finally:
+        ops.set_tuning("attn_persist", 1)
+        ops.set_tuning("attn_fast", 1)
+    L, H, kv = 13568, 5, 10000                    # the ragged call of the test above
+    q, k, vt = operands(L, L, H)
+    ops.attention_fwd(q, k, vt, H, k_lens=torch.tensor([kv], device=DEV, dtype=torch.int32))
+    uniform = plan(1, L, L, H, 0)
+    assert uniform & _lib.ATTN_VARIANT_SPLIT_TAIL and last() == uniform & ~_lib.ATTN_VARIANT_SPLIT_TAIL
+
+
 def test_attention_online_softmax_rescale_branch():
     """A key tile whose scores jump far above the running max forces the rescale path
     (guide rule 26): spike one key against every query late in the sequence."""

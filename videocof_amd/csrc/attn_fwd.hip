@@ -26,22 +26,21 @@
 #include <stdlib.h>
 #include <stdint.h>
 
-#include <algorithm>
 #include <atomic>
 #include <type_traits>
 
-#include "common.hpp"
+#include "attn_common.hpp"
 
 namespace {
 
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 
-constexpr int kD = 128;          // head dim
+constexpr int kD = kWanAttnD;    // head dim
 constexpr int kQPerWave = 64;    // two 32-query blocks per wave
 constexpr int kWavesPerWG = 4;   // one wave per SIMD
 constexpr int kQPerWG = kQPerWave * kWavesPerWG;   // 256
-constexpr int kKV = 64;          // keys per tile
-constexpr int kThreads = kWavesPerWG * 64;
+constexpr int kKV = kWanAttnKV;  // keys per tile
+static_assert(kQPerWG == kWanAttnQPerWG, "the plan arithmetic of attn_api.cpp counts 256-query workgroups");
 constexpr int kKTileBytes = kKV * kD * 2;    // 16 KiB
 constexpr int kVTileBytes = kD * kKV * 2;    // 16 KiB
 
@@ -80,12 +79,6 @@ struct AttnArgs {
 // VARIANT (template parameter of the kernels below) only names the instantiation so profiles separate the two
 // call sites:  0 = attn_self (long KV stream: self-attention, Lk ~ 1e4..1e5),
 //              1 = attn_cross (short KV: the 512 text tokens of WanT2VCrossAttention).
-// History: rounds 1-3 also carried an 8-wave kernel here (8 waves x 32 query rows, two waves per SIMD, running max per tile;
-// 1.18-1.28 PFLOP/s) -- the product kernel of round 1 and from round 3 on only the developer A/B partner behind "attn_w4" = 0.  It was
-// retired in round 5 (no product path reached it); what it taught is kept in DESIGN.md section 4.1 and in the A/B logs under
-// profiles/r01 - r03.  Its workgroup geometry survives in the constants above (a workgroup is still 256 queries of one head,
-// KV tiles are still 64 keys, the LDS images and the key permutation are the ones described at the top of this file).
-
 
 // 32 scores -> 1.  Written as max(max(m, a), b) so that the DAG combiner has exactly one way to fuse each
 // step into v_max3_f32 (15 v_max3 + 1 v_max); max(m, max(a, b)) makes it fuse the wrong pair and emit 31 ops.
@@ -113,16 +106,16 @@ __device__ __forceinline__ float rowmax32(const f32x16 (&s)[2]) {
 }
 
 // ====================================================================================================
-// 4-wave kernel: every product launch of wan_attention_fwd (round 2: the max-free main launch only).
+// 4-wave kernel: every launch of wan_attention_fwd except the all-fp8 main launch (attn_fwd_f8_kernel, below).
 //
-// Same workgroup (256 queries of one (batch, head)), same LDS images, same products and key permutation as the 8-wave
-// kernel above, but FOUR waves of 64 query rows each -- one wave per SIMD with the whole 512-register file:
+// The workgroup, LDS images, products and key permutation described at the top of this file, on FOUR waves of 64 query rows
+// each -- one wave per SIMD with the whole 512-register file (why not eight waves of 32 rows: DESIGN.md section 4.1):
 //   * O^T accumulators (2 query blocks x 4 d-blocks x 16) and the Q fragments (2 x 8 x 4) live in AGPRs
 //     (192 of 256); the MFMAs are inline asm so that A/B/C operands can be named in either file -- hipcc's own
 //     allocation of this shape spills (576 B/lane) and copies every S tile through v_accvgpr_read;
 //   * every K / V^T fragment read from LDS feeds TWO MFMAs (one per query block): 32 ds_read_b128 per 64 MFMAs instead
-//     of 32 per 32, and fragments are requested 3 fragments (6+ MFMA slots) ahead of use -- the 8-wave kernel reads each
-//     fragment right before its MFMA (no registers left) and its waves sit in s_waitcnt lgkmcnt 31 % of the time;
+//     of 32 per 32, and fragments are requested 3 fragments (6+ MFMA slots) ahead of use, which only a whole register file
+//     has room for (read right before their MFMA, waves sat in s_waitcnt lgkmcnt 31 % of the time);
 //   * with a single instruction stream per SIMD the order of the stream IS the schedule: one interval is 64 slots of
 //     `MFMA ; <= 5 fillers ; sched_barrier(0)` (attn_w4_sched.inc, emitted by tools/gen_attn_w4_sched.py).
 // Hazards that hipcc does not see for an asm MFMA are handled by construction (CDNA4 guide, section 5.7):
@@ -140,7 +133,7 @@ __device__ __forceinline__ u32x4 lds_read16_at(unsigned lds_byte_address) {
 }
 
 // Pipeline: K(t+2) / V(t+1) are requested (LDS-DMA) during the S segment of interval t and waited for (vmcnt(0) + barrier)
-// at its end; rings K 2 x 16 KiB + V 2 x 16 KiB, as in the 8-wave kernel.  Measured alternative that did not pay
+// at its end; rings K 2 x 16 KiB + V 2 x 16 KiB.  Measured alternative that did not pay
 // (profiles/r02/attn_w4_ab.log): requesting K(t+3) / V(t+2) in the PV segment, waiting for them at ONE barrier between the two
 // segments of the next interval (V ring of 3) and fetching the first K fragments of an interval before the previous one
 // ends -- no LDS latency exposed at the seam -- 68.7 vs 68.5 ms: the seam is not where the time goes.
@@ -156,7 +149,7 @@ constexpr int kLdsBytesW4 = 2 * kKTileBytes + 2 * kVTileBytes;
 // MAXFREE = false: the SAME loop with a LAZY softmax reference, which needs no second launch and has no input-dependent
 // cliff (1.36 vs 1.40 PFLOP/s for the max-free attempt at L = 67 080 x 40 heads, profiles/r03/attn_lazy_ab.log):
 //   * the reference m of a query row starts as the exact row max of tile 0 and rides in the MFMA accumulator (every S chain
-//     starts from a 16-register splat of -m, as in the 8-wave PRE form), so p = exp2(S') costs no extra VALU;
+//     starts from a 16-register splat of -m), so p = exp2(S') costs no extra VALU;
 //   * softmax does not care WHICH reference is used as long as nothing overflows or vanishes, and bf16 P / fp32 sums have
 //     ~2^127 of head-room: instead of a row max per tile (32 v_max3 + a lane exchange + a branch), the loop tests the row
 //     SUMS it computes anyway -- one v_max + one v_cmp per tile at MIDCHECK, where all four P fragments of the tile exist
@@ -604,11 +597,7 @@ void attn_fwd_w4_kernel(AttnArgs a) {
         } else if constexpr (PKSUB) {
 #include "attn_w4_sched_pk.inc"
         } else {
-#ifdef WAN_ATTN_SCHED_ALT       // developer A/B builds only (a second library next to the product one); never defined by the Makefile
-#include WAN_ATTN_SCHED_ALT
-#else
 #include "attn_w4_sched.inc"
-#endif
         }
 #undef RDK
 #undef RDK8
@@ -1051,12 +1040,8 @@ void attn_fwd_f8_kernel(AttnArgs a) {
                             else { const i32x8 p_ = F8_PBLOCK(p8b); F8V_MFMA(o[1][dt], dt, p_, vsc, psb); } SB(); } while (0)
 #define G8F(j) do { if ((j) < 2) stage_k(rk, 1 - kslot_next, (j)); else if ((j) < 4) stage_v(rv, 1 - vslot, (j) - 2); else stage_s(rs, 1 - vslot); } while (0)
 // block 1 reads S(t) of query block 1, block 0 reads S(t+1) of query block 0; score i of a block = key-half kt = i >> 4, register i & 15
-#ifndef F8_TIMING
-#define F8_TIMING 0      // developer timing builds only (-DF8_TIMING=bits: 1 no row-sum adds, 2 no conversions, 4 no exponentials, 8 no scale chain); results are garbage
-#endif
-#define E8(blk, i) do { if constexpr ((F8_TIMING & 4) != 0) e[i] = (blk) ? sc[1][(i) >> 4][(i) & 15] : sn[0][(i) >> 4][(i) & 15]; \
-                        else e[i] = __builtin_amdgcn_exp2f((blk) ? sc[1][(i) >> 4][(i) & 15] : sn[0][(i) >> 4][(i) & 15]); } while (0)
-#define A8(blk, i) do { if constexpr ((F8_TIMING & 1) == 0 || (i) % 16 == 0) { if (blk) { if ((i) < 16) s1k0 += e[i]; else s1k1 += e[i]; } else { if ((i) < 16) s0k0 += e[i]; else s0k1 += e[i]; } } } while (0)
+#define E8(blk, i) do { e[i] = __builtin_amdgcn_exp2f((blk) ? sc[1][(i) >> 4][(i) & 15] : sn[0][(i) >> 4][(i) & 15]); } while (0)
+#define A8(blk, i) do { if (blk) { if ((i) < 16) s1k0 += e[i]; else s1k1 += e[i]; } else { if ((i) < 16) s0k0 += e[i]; else s0k1 += e[i]; } } while (0)
 // the six steps of block_scales() as single instructions: exchange | total | * 2^-7 | keep the exponent | its byte for the MFMA | broadcast both
 #define F8_SC(k, SK0, SK1, XA, XB, C0, C1, PS) do { \
         if ((k) == 0) { XA = SK0; XB = SK1; asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(XA), "+v"(XB)); } \
@@ -1065,9 +1050,8 @@ void attn_fwd_f8_kernel(AttnArgs a) {
         else if ((k) == 3) C0 = __uint_as_float(__float_as_uint(XA) & 0x7f800000u); \
         else if ((k) == 4) PS = __float_as_uint(C0) >> 23; \
         else { C1 = C0; asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(C0), "+v"(C1)); } } while (0)
-#define SC8(blk, k) do { if constexpr ((F8_TIMING & 8) != 0) { if ((k) == 0) { if (blk) { sc1k0 = s1k0; sc1k1 = s1k1; psb = 127; } else { sc0k0 = s0k0; sc0k1 = s0k1; psa_next = 127; } } } \
-                         else if (blk) F8_SC(k, s1k0, s1k1, x1a, x1b, sc1k0, sc1k1, psb); else F8_SC(k, s0k0, s0k1, x0a, x0b, sc0k0, sc0k1, psa_next); } while (0)
-#define C8(blk, w) do { if constexpr ((F8_TIMING & 2) != 0 && (w) % 8 != 0) break; if (blk) p8b[(w) >> 1] = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(p8b[(w) >> 1], e[2 * (w)], e[2 * (w) + 1], (w) < 8 ? sc1k0 : sc1k1, ((w) & 1) != 0); \
+#define SC8(blk, k) do { if (blk) F8_SC(k, s1k0, s1k1, x1a, x1b, sc1k0, sc1k1, psb); else F8_SC(k, s0k0, s0k1, x0a, x0b, sc0k0, sc0k1, psa_next); } while (0)
+#define C8(blk, w) do { if (blk) p8b[(w) >> 1] = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(p8b[(w) >> 1], e[2 * (w)], e[2 * (w) + 1], (w) < 8 ? sc1k0 : sc1k1, ((w) & 1) != 0); \
                         else pa_next[(w) >> 1] = __builtin_amdgcn_cvt_scalef32_pk_fp8_f32(pa_next[(w) >> 1], e[2 * (w)], e[2 * (w) + 1], (w) < 8 ? sc0k0 : sc0k1, ((w) & 1) != 0); } while (0)
 #define MIDPOINT() do { l_run[1] += s1k0 + s1k1; } while (0)
 #include "attn_f8_sched.inc"
@@ -1248,46 +1232,6 @@ __global__ __launch_bounds__(256) void transpose_bf16_kernel(const bf16_t* __res
     }
 }
 
-}  // namespace
-
-namespace {
-
-// Tail balancing.  Every workgroup of a launch costs the same (all stream the whole K/V of their head) and one
-// fits per CU, so W workgroups take ceil(W / CUs) rounds and the last round may be nearly empty: the 5 heads of
-// an 8-way Ulysses shard at L = 67 080 give 1315 = 5 x 256 + 35 workgroups -> 6 rounds for 5.14 rounds of work
-// (measured 1007 vs 1165 TFLOP/s).  When the remainder is small, the last `tq` query blocks of every
-// (batch, head) leave the main launch; a second launch covers them with the SAME 8-wave kernel, each workgroup
-// taking 1/nsplit of the keys (so that the tail fills the chip for 1/nsplit of a round), and a small kernel
-// merges the partial (O, max, sum) triples.  Needs caller-provided workspace; without it the plain launch runs.
-struct TailPlan { int tq = 0, nsplit = 1, tiles_per_split = 0, main_qb = 0, rows_tail = 0; int64_t ws_bytes = 0; };
-
-TailPlan plan_tail(int batch, int Lq, int Lk, int num_heads) {
-    TailPlan p;
-    const int ncu = wan_cu_count();
-    const int nqb = (Lq + kQPerWG - 1) / kQPerWG, nkv = (Lk + kKV - 1) / kKV;
-    p.main_qb = nqb;
-    const int64_t hb = (int64_t)num_heads * batch, items = hb * nqb;
-    if (wan_tune(WAN_TUNE_ATTN_TAIL) == 0 || Lk <= 1024 || items <= ncu || items % ncu == 0) return p;
-    const int64_t rem = items % ncu;
-    const int cand = (int)((rem + hb - 1) / hb);        // query blocks per (batch, head) moved to the tail launch
-    if (cand >= nqb) return p;
-    const int64_t tail_items = hb * cand, main_items = hb * (nqb - cand);
-    int nsplit = (int)std::min<int64_t>(std::min<int64_t>(ncu / tail_items, nkv / 8), 16);
-    if (nsplit < 2) return p;
-    const int tps = (nkv + nsplit - 1) / nsplit;
-    nsplit = (nkv + tps - 1) / tps;                     // no empty split
-    const double before = (double)((items + ncu - 1) / ncu);
-    const double after = (double)((main_items + ncu - 1) / ncu) + 1.0 / nsplit + 0.05;
-    if (nsplit < 2 || after > before - 0.2) return p;
-    p.tq = cand; p.nsplit = nsplit; p.tiles_per_split = tps; p.main_qb = nqb - cand;
-    p.rows_tail = Lq - p.main_qb * kQPerWG;
-    p.ws_bytes = (int64_t)batch * nsplit * num_heads * p.rows_tail * (kD + 2) * (int64_t)sizeof(float);
-    return p;
-}
-
-}  // namespace
-
-namespace {
 // Contract check behind the `debug_checks` switch: the V^T pad columns [Lk, roundup(Lk, 64)) of every row are read by
 // the last KV tile with probability 0, and 0 * NaN is NaN in the MFMA, so they must be finite.  One pass over the pad
 // columns, a device flag, a stream synchronise (developer / bring-up use only; the product path never synchronises).
@@ -1300,16 +1244,56 @@ __global__ void vt_pad_check_kernel(const bf16_t* vt, int64_t ldvt, int64_t vt_b
     if (bad) atomicOr(flag, 1);
 }
 
-wan_status_t check_vt_padding(const AttnArgs& a, int batch, int64_t lk_pad, hipStream_t st) {
-    if (lk_pad == a.Lk) return WAN_OK;
+// ---- the instantiations, written ONCE: the LDS reservation and the run-time -> template dispatch both walk this list, so a form
+// cannot be launched without having been reserved, and each is reserved with the size it is launched with.
+constexpr int attn_form_id(int variant, bool split, int ref, bool fix = false, bool qk8 = false, bool persist = false) {
+    return variant | (split ? 2 : 0) | ref << 2 | (fix ? 16 : 0) | (qk8 ? 32 : 0) | (persist ? 64 : 0);
+}
+constexpr int kAttnFormF8 = 128;        // attn_fwd_f8_kernel
+template <auto KERNEL, int ID, int LDS_BYTES>
+struct AttnForm { static constexpr auto kernel = KERNEL; static constexpr int id = ID, lds = LDS_BYTES; };
+template <int VARIANT, bool SPLIT, int REF, bool FIX = false, bool QK8 = false, bool PERSIST = false>
+using W4Form = AttnForm<&attn_fwd_w4_kernel<VARIANT, SPLIT, REF, FIX, QK8, PERSIST>, attn_form_id(VARIANT, SPLIT, REF, FIX, QK8, PERSIST), kLdsBytesW4>;
+using F8Form = AttnForm<&attn_fwd_f8_kernel, kAttnFormF8, kLdsBytesF8>;
+// f(form) for every form until one answers true; false if none did
+template <class F>
+bool any_attn_form(F&& f) {
+    return f(W4Form<0, false, 0>{}) || f(W4Form<1, false, 0>{})                                     // max-free attempt: self, cross
+        || f(W4Form<0, false, 1>{}) || f(W4Form<1, false, 1>{})                                     // lazy reference in the accumulator
+        || f(W4Form<0, false, 2>{}) || f(W4Form<1, false, 2>{})                                     // lazy reference, packed shift
+        || f(W4Form<0, false, 1, true>{}) || f(W4Form<1, false, 1, true>{})                         // fix-up behind the max-free attempt
+        || f(W4Form<0, true, 1>{}) || f(W4Form<0, true, 2>{})                                       // split-KV tail round
+        || f(W4Form<1, false, 1, false, false, true>{}) || f(W4Form<1, false, 2, false, false, true>{})     // persistent cross-attention
+        || f(W4Form<0, false, 1, false, true>{}) || f(W4Form<0, true, 1, false, true>{})            // fp8 QK^T: main, tail
+        || f(W4Form<0, false, 1, true, true>{})                                                     // fp8 QK^T fix-up behind the all-fp8 attempt
+        || f(F8Form{});                                                                             // fp8 QK^T and fp8 P.V, checked max-free
+}
+
+wan_status_t launch_form(int id, dim3 grid, hipStream_t st, const AttnArgs& a) {
+    const bool held = any_attn_form([&](auto form) {
+        using Form = decltype(form);
+        if (Form::id != id) return false;
+        hipLaunchKernelGGL(Form::kernel, grid, dim3(kW4Threads), Form::lds, st, a);
+        return true;
+    });
+    WAN_REQUIRE(held, WAN_ERR_UNSUPPORTED, "wan_attention_fwd: no kernel instantiation for form 0x%x", id);
+    return WAN_OK;
+}
+#define WAN_LAUNCH_FORM(id, grid) do { if (const wan_status_t ls__ = launch_form(id, grid, st, a); ls__ != WAN_OK) return ls__; } while (0)
+
+}  // namespace
+
+wan_status_t wan_attn_check_vt_padding(const WanAttnCall& c, hipStream_t st) {
+    const int64_t lk_pad = ((int64_t)c.Lk + kKV - 1) / kKV * kKV;
+    if (lk_pad == c.Lk) return WAN_OK;
     int* flag = nullptr;
     if (hipMalloc(&flag, sizeof(int)) != hipSuccess || hipMemsetAsync(flag, 0, sizeof(int), st) != hipSuccess) {
         wan_set_error("wan_attention_fwd: debug check could not allocate its flag");
         return WAN_ERR_LAUNCH;
     }
-    const int rows = a.H * kD;
-    hipLaunchKernelGGL(vt_pad_check_kernel, dim3((unsigned)((rows + 255) / 256), (unsigned)batch), dim3(256), 0, st,
-                       a.vt, a.ldvt, a.vt_bs, rows, a.Lk, (int)lk_pad, flag);
+    const int rows = c.num_heads * kD;
+    hipLaunchKernelGGL(vt_pad_check_kernel, dim3((unsigned)((rows + 255) / 256), (unsigned)c.batch), dim3(256), 0, st,
+                       (const bf16_t*)c.vt, c.ldvt, c.vt_bs, rows, c.Lk, (int)lk_pad, flag);
     int host = 0;
     hipError_t e = hipMemcpyAsync(&host, flag, sizeof(int), hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
@@ -1320,299 +1304,69 @@ wan_status_t check_vt_padding(const AttnArgs& a, int batch, int64_t lk_pad, hipS
     }
     WAN_REQUIRE(host == 0, WAN_ERR_INVALID,
                 "wan_attention_fwd: V^T pad columns [%d, %lld) hold Inf/NaN (the caller must keep them finite, e.g. zero)",
-                a.Lk, (long long)lk_pad);
+                c.Lk, (long long)lk_pad);
     return WAN_OK;
 }
 
-// scratch layout: [16-byte header + one int per workgroup of the un-split grid, rounded up to 256 B][partials of the
-// split tail round].  The header must be zero when the scratch is first used (it carries the sticky switch).
-int64_t flag_bytes(int batch, int Lq, int num_heads) {
-    const int64_t wgs = (int64_t)((Lq + kQPerWG - 1) / kQPerWG) * num_heads * batch;
-    return (16 + wgs * (int64_t)sizeof(int) + 255) / 256 * 256;      // 16-byte header + one int per workgroup
-}
-}  // namespace
-
-namespace {
-// The dispatch decision of wan_attention_fwd as host arithmetic (shared by the launcher and wan_attention_plan).
-struct AttnPlan { TailPlan tail; bool fast = false, ref2 = false, xcd = false; int variant = 0; };
-
-AttnPlan plan_attention(int batch, int Lq, int Lk, int num_heads, bool pre, int64_t workspace_bytes, bool qk8 = false, bool pv8 = false) {
-    AttnPlan p;
-    const bool self = Lk > 1024;
-    const int nqb_all = (Lq + kQPerWG - 1) / kQPerWG;
-    // plain q always takes the packed-shift form (it applies softmax_scale exactly, in the same fma); pre-scaled q the
-    // accumulator form unless the developer switch asks for the other
-    p.ref2 = !pre || wan_tune(WAN_TUNE_ATTN_REF) == 2;
-    const int64_t fb = flag_bytes(batch, Lq, num_heads);
-    if (workspace_bytes >= fb) {
-        // the attempt is worth its second launch (~5-15 us of workgroups that exit at once) only on long launches: self-attention
-        // over >= 4 rounds of workgroups, or -- round 6 -- fewer rounds of LONG key streams (rounds x KV tiles >= 1024, i.e. >= ~1.5 ms of
-        // launch at ~1.5 us per tile: the 2- and 3-head launches of an 8-way Ulysses rank at L = 67 080 are 2.05 / 3.08 rounds of 1 049
-        // tiles and sat on the lazy form until `bench.py --emulate-sp 8` showed it); short launches (cross-attention's 8 KV tiles,
-        // small grids) take the one-launch lazy form.  attn_fast = 2 forces the attempt whenever there is scratch (tests)
-        const int fast_mode = wan_tune(WAN_TUNE_ATTN_FAST);
-        const int64_t nwg_all = (int64_t)nqb_all * num_heads * batch, cus = wan_cu_count();
-        const int64_t rounds = (nwg_all + cus - 1) / cus, kv_tiles = (Lk + kKV - 1) / kKV;
-        const bool long_launch = self && (nwg_all >= 4 * cus || rounds * kv_tiles >= 1024);
-        p.fast = pre && !qk8 && (fast_mode == 2 || (fast_mode == 1 && long_launch));
-        p.tail = plan_tail(batch, Lq, Lk, num_heads);
-        if (p.tail.tq > 0 && workspace_bytes - fb < p.tail.ws_bytes) p.tail = TailPlan();
-    }
-    // heads pinned to XCDs: only worth it (and only balanced) when the (batch, head) pairs split evenly over the 8 XCDs
-    p.xcd = wan_tune(WAN_TUNE_ATTN_XCD_MAP) != 0 && self && (num_heads * batch) % 8 == 0;
-    if (qk8) p.ref2 = false;
-    p.variant = (qk8 && pv8 && workspace_bytes >= fb) ? WAN_ATTN_VARIANT_W4_F8 : qk8 ? WAN_ATTN_VARIANT_W4_LAZY_QK8
-                    : (p.fast ? WAN_ATTN_VARIANT_W4_MAXFREE : WAN_ATTN_VARIANT_W4_LAZY);
-    if (p.xcd) p.variant |= WAN_ATTN_VARIANT_XCD_PINNED;
-    if (p.tail.tq > 0) p.variant |= WAN_ATTN_VARIANT_SPLIT_TAIL;
-    return p;
-}
-}  // namespace
-
-extern "C" int wan_attention_plan(int batch, int Lq, int Lk, int num_heads, int head_dim, int flags, int64_t workspace_bytes) {
-    if (batch <= 0 || Lq <= 0 || Lk <= 0 || num_heads <= 0 || head_dim != kD) return 0;
-    return plan_attention(batch, Lq, Lk, num_heads, (flags & WAN_ATTN_Q_PRESCALED) != 0, workspace_bytes, (flags & WAN_ATTN_QK_FP8) != 0,
-                          (flags & WAN_ATTN_PV_FP8) != 0).variant;
-}
-
-extern "C" int64_t wan_attention_workspace_bytes(int batch, int Lq, int Lk, int num_heads, int head_dim) {
-    if (batch <= 0 || Lq <= 0 || Lk <= 0 || num_heads <= 0 || head_dim != kD) return 0;
-    return flag_bytes(batch, Lq, num_heads) + plan_tail(batch, Lq, Lk, num_heads).ws_bytes;
-}
-
-namespace {
-struct Qk8Operands {            // q8 = e4m3(q * softmax_scale * log2(e) * 2^q_exp), k8 = e4m3(k * 2^k_exp)
-    int q_exp, k_exp;
-    // fp8 P.V as well (wan_attention_fwd_f8): the MX e4m3 V^T of wan_vt_quantize_mx; v8 = NULL: bf16 P.V
-    const void* v8; int64_t ldv8, v8_bs; const void* vs8;
-};
-int64_t vt_mx_scale_bytes_per_head(int Lk) { return (int64_t)((Lk + kKV - 1) / kKV) * 256; }
-}
-
-// q / k are bf16 tensors, or -- with `qk8` -- e4m3 tensors whose strides count BYTES
-static wan_status_t attention_fwd_impl(const void* q, int64_t ldq, int64_t q_bstride,
-                                       const void* k, int64_t ldk, int64_t k_bstride,
-                                       const void* vt, int64_t ldvt, int64_t vt_bstride,
-                                       void* out, int64_t ldo, int64_t o_bstride,
-                                       int batch, int Lq, int Lk, int num_heads, int head_dim,
-                                       float softmax_scale, int flags, void* workspace, int64_t workspace_bytes,
-                                       void* stream, const Qk8Operands* qk8, const int* klens = nullptr) {
-    WAN_REQUIRE(q && k && vt && out, WAN_ERR_INVALID, "wan_attention_fwd: null tensor");
-    WAN_REQUIRE((flags & ~WAN_ATTN_Q_PRESCALED) == 0, WAN_ERR_INVALID, "wan_attention_fwd: unknown flags 0x%x", flags);
-    WAN_REQUIRE(head_dim == kD, WAN_ERR_UNSUPPORTED, "wan_attention_fwd: head_dim=%d (only 128 is built)", head_dim);
-    WAN_REQUIRE(batch > 0 && Lq >= 0 && Lk > 0 && num_heads > 0, WAN_ERR_INVALID,
-                "wan_attention_fwd: batch=%d Lq=%d Lk=%d heads=%d", batch, Lq, Lk, num_heads);
-    const int64_t C = (int64_t)num_heads * kD;
-    WAN_REQUIRE(ldq >= C && ldk >= C && ldo >= C && ldq % 8 == 0 && ldk % 8 == 0 && ldo % 4 == 0, WAN_ERR_INVALID,
-                "wan_attention_fwd: row strides (%lld,%lld,%lld) too small/misaligned for %d heads",
-                (long long)ldq, (long long)ldk, (long long)ldo, num_heads);
-    if (qk8) {
-        WAN_REQUIRE(ldq % 16 == 0 && ldk % 16 == 0 && ((uintptr_t)q & 15) == 0 && ((uintptr_t)k & 15) == 0 && q_bstride % 16 == 0 &&
-                        k_bstride % 16 == 0, WAN_ERR_INVALID, "wan_attention_fwd_qk8: e4m3 rows must be 16-byte aligned");
-        WAN_REQUIRE(qk8->q_exp >= -100 && qk8->q_exp <= 100 && qk8->k_exp >= -100 && qk8->k_exp <= 100, WAN_ERR_INVALID,
-                    "wan_attention_fwd_qk8: scale exponents (%d, %d) out of range", qk8->q_exp, qk8->k_exp);
-    }
-    const int64_t lk_pad = ((int64_t)Lk + kKV - 1) / kKV * kKV;
-    WAN_REQUIRE(ldvt >= lk_pad && ldvt % 8 == 0, WAN_ERR_INVALID,
-                "wan_attention_fwd: ldvt=%lld must be >= roundup(Lk,64)=%lld and a multiple of 8",
-                (long long)ldvt, (long long)lk_pad);
-    if (qk8 && qk8->v8) {
-        WAN_REQUIRE(qk8->vs8 != nullptr && qk8->ldv8 >= lk_pad && qk8->ldv8 % 16 == 0 && qk8->v8_bs % 16 == 0 && ((uintptr_t)qk8->v8 & 15) == 0 &&
-                        ((uintptr_t)qk8->vs8 & 3) == 0, WAN_ERR_INVALID,
-                    "wan_attention_fwd_f8: v8 rows must be 16-byte aligned with ldv8=%lld >= roundup(Lk,64)=%lld, scales 4-byte aligned",
-                    (long long)qk8->ldv8, (long long)lk_pad);
-        WAN_REQUIRE(workspace != nullptr && workspace_bytes >= flag_bytes(batch, Lq, num_heads), WAN_ERR_INVALID,
-                    "wan_attention_fwd_f8: needs the scratch of wan_attention_workspace_bytes (its softmax is the checked max-free form)");
-    }
-    if (Lq == 0) return WAN_OK;
+// Fills AttnArgs from the call and launches what the plan says -- main, fix-up, tail, combine -- with no decision of its own.
+wan_status_t wan_attn_launch(const WanAttnCall& c, const WanAttnPlan& plan, hipStream_t st) {
     static std::atomic<uint64_t> attr_done{0};
     const wan_status_t ast = wan_once_per_device(attr_done, +[]() -> wan_status_t {
-        const void* fns[] = {reinterpret_cast<const void*>(&attn_fwd_w4_kernel<0, false, 0>), reinterpret_cast<const void*>(&attn_fwd_w4_kernel<1, false, 0>),
-                             reinterpret_cast<const void*>(&attn_fwd_w4_kernel<0, false, 1>), reinterpret_cast<const void*>(&attn_fwd_w4_kernel<1, false, 1>),
-                             reinterpret_cast<const void*>(&attn_fwd_w4_kernel<0, false, 1, true>), reinterpret_cast<const void*>(&attn_fwd_w4_kernel<1, false, 1, true>),
-                             reinterpret_cast<const void*>(&attn_fwd_w4_kernel<0, true, 1>),
-                             reinterpret_cast<const void*>(&attn_fwd_w4_kernel<0, false, 2>), reinterpret_cast<const void*>(&attn_fwd_w4_kernel<1, false, 2>),
-                             reinterpret_cast<const void*>(&attn_fwd_w4_kernel<0, true, 2>),
-                             reinterpret_cast<const void*>(&attn_fwd_w4_kernel<0, false, 1, false, true>),
-                             reinterpret_cast<const void*>(&attn_fwd_w4_kernel<0, true, 1, false, true>),
-                             reinterpret_cast<const void*>(&attn_fwd_w4_kernel<0, false, 1, true, true>),
-                             reinterpret_cast<const void*>(&attn_fwd_f8_kernel)};
-        for (size_t i = 0; i < sizeof(fns) / sizeof(fns[0]); ++i) {
-            hipError_t e = hipFuncSetAttribute(fns[i], hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytesW4);
-            if (e != hipSuccess) {
-                wan_set_error("wan_attention_fwd: cannot reserve LDS: %s", hipGetErrorString(e));
-                return WAN_ERR_LAUNCH;
-            }
-        }
+        // every form at once: a graph capture warmed up on one shape must not meet an attribute call for another form
+        const bool failed = any_attn_form([](auto form) {
+            using Form = decltype(form);
+            return hipFuncSetAttribute(reinterpret_cast<const void*>(Form::kernel), hipFuncAttributeMaxDynamicSharedMemorySize, Form::lds) != hipSuccess;
+        });
+        WAN_REQUIRE(!failed, WAN_ERR_LAUNCH, "wan_attention_fwd: cannot reserve LDS: %s", hipGetErrorString(hipGetLastError()));
         return WAN_OK;
     });
     if (ast != WAN_OK) return ast;
-    AttnArgs a;
-    a.q = (const bf16_t*)q; a.ldq = ldq; a.q_bs = q_bstride;
-    a.k = (const bf16_t*)k; a.ldk = ldk; a.k_bs = k_bstride;
-    a.q8 = nullptr; a.k8 = nullptr; a.ldq8 = a.ldk8 = a.q8_bs = a.k8_bs = 0; a.q8_scale = a.k8_scale = 0x7f7f7f7fu;
-    if (qk8) {
-        a.q8 = (const unsigned char*)q; a.ldq8 = ldq; a.q8_bs = q_bstride;
-        a.k8 = (const unsigned char*)k; a.ldk8 = ldk; a.k8_bs = k_bstride;
-        a.q8_scale = 0x01010101u * (unsigned)(127 - qk8->q_exp);
-        a.k8_scale = 0x01010101u * (unsigned)(127 - qk8->k_exp);
+    const WanAttnTail& tp = plan.tail;
+    const int batch = c.batch, num_heads = c.num_heads;
+    AttnArgs a = {};             // what a form does not read stays null / 0
+    a.q = (const bf16_t*)c.q; a.ldq = c.ldq; a.q_bs = c.q_bs;
+    a.k = (const bf16_t*)c.k; a.ldk = c.ldk; a.k_bs = c.k_bs;
+    a.q8_scale = a.k8_scale = 0x7f7f7f7fu;
+    if (c.qk8) {
+        a.q8 = (const unsigned char*)c.q; a.ldq8 = c.ldq; a.q8_bs = c.q_bs;
+        a.k8 = (const unsigned char*)c.k; a.ldk8 = c.ldk; a.k8_bs = c.k_bs;
+        a.q8_scale = 0x01010101u * (unsigned)(127 - c.q_exp);
+        a.k8_scale = 0x01010101u * (unsigned)(127 - c.k_exp);
     }
-    a.v8 = nullptr; a.vs8 = nullptr; a.ldv8 = a.v8_bs = a.vs8_hs = 0;
-    const bool pv8 = qk8 != nullptr && qk8->v8 != nullptr;
-    if (pv8) {
-        a.v8 = (const unsigned char*)qk8->v8; a.ldv8 = qk8->ldv8; a.v8_bs = qk8->v8_bs;
-        a.vs8 = (const unsigned char*)qk8->vs8; a.vs8_hs = vt_mx_scale_bytes_per_head(Lk);
+    if (c.v8) {
+        a.v8 = (const unsigned char*)c.v8; a.ldv8 = c.ldv8; a.v8_bs = c.v8_bs;
+        a.vs8 = (const unsigned char*)c.vs8; a.vs8_hs = wan_vt_mx_scale_bytes_per_head(c.Lk);
     }
-    a.vt = (const bf16_t*)vt; a.ldvt = ldvt; a.vt_bs = vt_bstride;
-    a.o = (bf16_t*)out; a.ldo = ldo; a.o_bs = o_bstride;
-    a.Lq = Lq; a.Lk = Lk; a.H = num_heads; a.klens = klens;
-    const bool pre = (flags & WAN_ATTN_Q_PRESCALED) != 0;
-    WAN_REQUIRE(pre || (softmax_scale > 0.f && softmax_scale < 1e30f), WAN_ERR_INVALID,
-                "wan_attention_fwd: softmax_scale=%g must be positive and finite", (double)softmax_scale);
-    a.scale_log2e = pre ? 1.0f : softmax_scale * 1.4426950408889634f;
-    a.qblk0 = 0; a.nsplit = 1; a.tiles_per_split = 0; a.row0 = 0; a.rows_tail = 0; a.ws_o = nullptr; a.ws_ml = nullptr; a.flags = nullptr;
-    const int nqb_all = (Lq + kQPerWG - 1) / kQPerWG;
-    hipStream_t st = (hipStream_t)stream;
-    const bool self = Lk > 1024;
-    if (wan_tune(WAN_TUNE_DEBUG_CHECKS) != 0 && klens == nullptr) {       // synchronising contract check, developer builds / bring-up only
-        const wan_status_t cs = check_vt_padding(a, batch, lk_pad, st);
-        if (cs != WAN_OK) return cs;
-    }
-    // With scratch memory: (1) pre-scaled q first runs the max-free form, followed by the FIX launch of the lazy-reference form
-    // on the flagged workgroups only; (2) the last partial round of a long launch is split over the keys (plan_tail).
-    // Without scratch (or attn_fast = 0): ONE launch of the lazy-reference form.
-    // attn_fast / attn_tail (wan_set_tuning, or WAN_ATTN_FAST / WAN_ATTN_TAIL read once at load) are developer A/B switches.
-    char* ws_tail = nullptr;
-    int64_t ws_usable = 0;
-    if (workspace != nullptr) {
-        WAN_REQUIRE(((uintptr_t)workspace & 15) == 0, WAN_ERR_INVALID, "wan_attention_fwd: workspace must be 16-byte aligned");
-        const int64_t fb = flag_bytes(batch, Lq, num_heads);
-        if (workspace_bytes >= fb) {
-            ws_usable = workspace_bytes;
-            a.flags = (int*)workspace + 4;
-            ws_tail = (char*)workspace + fb;
-        }
-    }
-    AttnPlan plan = plan_attention(batch, Lq, Lk, num_heads, pre, ws_usable, qk8 != nullptr, qk8 != nullptr && qk8->v8 != nullptr);
-    if (klens != nullptr && plan.tail.tq > 0) {        // ragged batches: the split-KV tail round divides ONE key count; every workgroup walks its own
-        plan.tail = TailPlan();
-        plan.variant &= ~WAN_ATTN_VARIANT_SPLIT_TAIL;
-    }
-    const TailPlan& tp = plan.tail;
-    const bool fast = plan.fast;
-    a.nqb = tp.tq > 0 ? tp.main_qb : nqb_all;
-    a.nbh = num_heads * batch;
+    a.vt = (const bf16_t*)c.vt; a.ldvt = c.ldvt; a.vt_bs = c.vt_bs;
+    a.o = (bf16_t*)c.out; a.ldo = c.ldo; a.o_bs = c.o_bs;
+    a.Lq = c.Lq; a.Lk = c.Lk; a.H = num_heads; a.klens = c.k_lens;
+    a.scale_log2e = (c.flags & WAN_ATTN_Q_PRESCALED) != 0 ? 1.0f : c.softmax_scale * 1.4426950408889634f;
+    a.nsplit = 1;
+    if (plan.scratch) a.flags = (int*)c.workspace + 4;
+    a.nbh = num_heads * batch; a.nqb = (int)(plan.nwg / a.nbh); a.nwg = (int)plan.nwg;
     a.xcd_map = plan.xcd ? 1 : 0;
-    const int64_t nwg = (int64_t)a.nqb * a.nbh;
-    WAN_REQUIRE(nwg < (int64_t)1 << 31, WAN_ERR_UNSUPPORTED, "wan_attention_fwd: grid too large");
-    a.nwg = (int)nwg;
-    dim3 grid((unsigned)nwg);
-    const bool ref2 = plan.ref2;
-    const dim3 block4(kW4Threads);
-    int variant;
-    if (pv8) {                       // fp8 QK^T and fp8 P.V (opt-in, lossy): checked max-free form, flagged workgroups redone by the fp8-QK^T lazy kernel
-        variant = WAN_ATTN_VARIANT_W4_F8;
-        hipLaunchKernelGGL(attn_fwd_f8_kernel, grid, block4, kLdsBytesF8, st, a);
-        WAN_CHECK_LAUNCH("wan_attention_fwd_f8");
-        hipLaunchKernelGGL((attn_fwd_w4_kernel<0, false, 1, true, true>), grid, block4, kLdsBytesW4, st, a);
-    } else if (qk8) {                // fp8 QK^T (opt-in, lossy): the lazy-reference kernel with its S product on the fp8 pipe
-        variant = WAN_ATTN_VARIANT_W4_LAZY_QK8;
-        hipLaunchKernelGGL((attn_fwd_w4_kernel<0, false, 1, false, true>), grid, block4, kLdsBytesW4, st, a);
-    } else if (!fast) {               // lazy-reference 4-wave kernel, one launch: any q form, scratch or not, no input-dependent path
-        variant = WAN_ATTN_VARIANT_W4_LAZY;
-        // short KV streams (cross-attention: 8 tiles per query block): ONE resident workgroup per CU walks the blocks (PERSIST, see the
-        // kernel); the grid stays a multiple of 8 so that w & 7 -- the XCD a head is pinned to -- is the same for every block of a workgroup
-        // (wan_resident_cus: the CUs tuning key "sp_reserve_cus" leaves to communication kernels are not occupied)
-        const int pcus = wan_resident_cus() & ~7;
-        const bool persist = !self && wan_tune(WAN_TUNE_ATTN_PERSIST) != 0 && nwg > pcus && pcus >= 8;
-        const dim3 pgrid(persist ? (unsigned)pcus : (unsigned)nwg);
-        if (ref2) {
-            if (self) hipLaunchKernelGGL((attn_fwd_w4_kernel<0, false, 2>), grid, block4, kLdsBytesW4, st, a);
-            else if (persist) hipLaunchKernelGGL((attn_fwd_w4_kernel<1, false, 2, false, false, true>), pgrid, block4, kLdsBytesW4, st, a);
-            else hipLaunchKernelGGL((attn_fwd_w4_kernel<1, false, 2>), grid, block4, kLdsBytesW4, st, a);
-        } else {
-            if (self) hipLaunchKernelGGL((attn_fwd_w4_kernel<0, false, 1>), grid, block4, kLdsBytesW4, st, a);
-            else if (persist) hipLaunchKernelGGL((attn_fwd_w4_kernel<1, false, 1, false, false, true>), pgrid, block4, kLdsBytesW4, st, a);
-            else hipLaunchKernelGGL((attn_fwd_w4_kernel<1, false, 1>), grid, block4, kLdsBytesW4, st, a);
-        }
-    } else {                         // max-free attempt (2 % faster), then the lazy-reference kernel on the flagged workgroups only
-        variant = WAN_ATTN_VARIANT_W4_MAXFREE;
-        if (self) hipLaunchKernelGGL((attn_fwd_w4_kernel<0, false, 0>), grid, block4, kLdsBytesW4, st, a);
-        else hipLaunchKernelGGL((attn_fwd_w4_kernel<1, false, 0>), grid, block4, kLdsBytesW4, st, a);
-        WAN_CHECK_LAUNCH("wan_attention_fwd");
-        if (self) hipLaunchKernelGGL((attn_fwd_w4_kernel<0, false, 1, true>), grid, block4, kLdsBytesW4, st, a);
-        else hipLaunchKernelGGL((attn_fwd_w4_kernel<1, false, 1, true>), grid, block4, kLdsBytesW4, st, a);
-    }
-    if (a.xcd_map) variant |= WAN_ATTN_VARIANT_XCD_PINNED;
+    const dim3 grid((unsigned)plan.nwg);
+    // the checked attempt of the two-launch families, then the lazy kernel: as their fix-up (accumulator form) on the same grid, or alone
+    const bool f8 = plan.family == WAN_ATTN_VARIANT_W4_F8, maxfree = plan.family == WAN_ATTN_VARIANT_W4_MAXFREE, fix = f8 || maxfree;
+    const bool q8 = f8 || plan.family == WAN_ATTN_VARIANT_W4_LAZY_QK8;           // the fp8 QK^T kernels are attn_self instantiations
+    const int v = plan.self || q8 ? 0 : 1, lazy_ref = plan.ref2 ? 2 : 1;
+    if (f8) { WAN_LAUNCH_FORM(kAttnFormF8, grid); WAN_CHECK_LAUNCH("wan_attention_fwd_f8"); }
+    if (maxfree) { WAN_LAUNCH_FORM(attn_form_id(v, false, 0), grid); WAN_CHECK_LAUNCH("wan_attention_fwd"); }
+    WAN_LAUNCH_FORM(attn_form_id(v, false, fix ? 1 : lazy_ref, fix, q8, plan.persist), plan.persist ? dim3((unsigned)plan.persist_grid) : grid);
     if (tp.tq > 0) {
         WAN_CHECK_LAUNCH("wan_attention_fwd");
-        variant |= WAN_ATTN_VARIANT_SPLIT_TAIL;
         a.qblk0 = tp.main_qb; a.nsplit = tp.nsplit; a.tiles_per_split = tp.tiles_per_split;
         a.row0 = tp.main_qb * kQPerWG; a.rows_tail = tp.rows_tail;
-        a.ws_o = (float*)ws_tail;
+        a.ws_o = (float*)((char*)c.workspace + plan.flag_bytes);
         a.ws_ml = a.ws_o + (int64_t)batch * tp.nsplit * num_heads * tp.rows_tail * kD;
         a.nqb = tp.tq; a.nbh = num_heads * batch * tp.nsplit; a.xcd_map = 0;
-        dim3 tgrid((unsigned)((int64_t)a.nqb * a.nbh));
-        if (qk8) hipLaunchKernelGGL((attn_fwd_w4_kernel<0, true, 1, false, true>), tgrid, block4, kLdsBytesW4, st, a);
-        else if (ref2) hipLaunchKernelGGL((attn_fwd_w4_kernel<0, true, 2>), tgrid, block4, kLdsBytesW4, st, a);
-        else hipLaunchKernelGGL((attn_fwd_w4_kernel<0, true, 1>), tgrid, block4, kLdsBytesW4, st, a);
+        WAN_LAUNCH_FORM(attn_form_id(0, true, lazy_ref, false, c.qk8), dim3((unsigned)((int64_t)a.nqb * a.nbh)));
         WAN_CHECK_LAUNCH("wan_attention_fwd (tail)");
         hipLaunchKernelGGL(attn_combine_kernel, dim3((unsigned)tp.rows_tail, (unsigned)num_heads, (unsigned)batch), dim3(kD), 0, st, a);
     }
-    wan_note_attn_variant(variant);
+    wan_note_attn_variant(plan.variant);
     WAN_CHECK_LAUNCH("wan_attention_fwd");
     return WAN_OK;
-}
-
-extern "C" wan_status_t wan_attention_fwd(const void* q, int64_t ldq, int64_t q_bstride,
-                                          const void* k, int64_t ldk, int64_t k_bstride,
-                                          const void* vt, int64_t ldvt, int64_t vt_bstride,
-                                          void* out, int64_t ldo, int64_t o_bstride,
-                                          int batch, int Lq, int Lk, int num_heads, int head_dim,
-                                          float softmax_scale, int flags, void* workspace, int64_t workspace_bytes,
-                                          void* stream) {
-    return attention_fwd_impl(q, ldq, q_bstride, k, ldk, k_bstride, vt, ldvt, vt_bstride, out, ldo, o_bstride, batch, Lq, Lk, num_heads,
-                              head_dim, softmax_scale, flags, workspace, workspace_bytes, stream, nullptr);
-}
-
-extern "C" wan_status_t wan_attention_fwd_varlen(const void* q, int64_t ldq, int64_t q_bstride,
-                                                 const void* k, int64_t ldk, int64_t k_bstride,
-                                                 const void* vt, int64_t ldvt, int64_t vt_bstride,
-                                                 void* out, int64_t ldo, int64_t o_bstride,
-                                                 int batch, int Lq, int Lk, const int32_t* k_lens, int num_heads, int head_dim,
-                                                 float softmax_scale, int flags, void* workspace, int64_t workspace_bytes,
-                                                 void* stream) {
-    WAN_REQUIRE(k_lens != nullptr && ((uintptr_t)k_lens & 3) == 0, WAN_ERR_INVALID, "wan_attention_fwd_varlen: k_lens must be a device array of batch int32");
-    return attention_fwd_impl(q, ldq, q_bstride, k, ldk, k_bstride, vt, ldvt, vt_bstride, out, ldo, o_bstride, batch, Lq, Lk, num_heads,
-                              head_dim, softmax_scale, flags, workspace, workspace_bytes, stream, nullptr, k_lens);
-}
-
-extern "C" wan_status_t wan_attention_fwd_qk8(const void* q8, int64_t ldq8, int64_t q8_bstride, int q_exp,
-                                              const void* k8, int64_t ldk8, int64_t k8_bstride, int k_exp,
-                                              const void* vt, int64_t ldvt, int64_t vt_bstride,
-                                              void* out, int64_t ldo, int64_t o_bstride,
-                                              int batch, int Lq, int Lk, int num_heads, int head_dim,
-                                              void* workspace, int64_t workspace_bytes, void* stream) {
-    const Qk8Operands ops = {q_exp, k_exp, nullptr, 0, 0, nullptr};
-    return attention_fwd_impl(q8, ldq8, q8_bstride, k8, ldk8, k8_bstride, vt, ldvt, vt_bstride, out, ldo, o_bstride, batch, Lq, Lk,
-                              num_heads, head_dim, 1.0f, WAN_ATTN_Q_PRESCALED, workspace, workspace_bytes, stream, &ops);
-}
-
-extern "C" wan_status_t wan_attention_fwd_f8(const void* q8, int64_t ldq8, int64_t q8_bstride, int q_exp,
-                                             const void* k8, int64_t ldk8, int64_t k8_bstride, int k_exp,
-                                             const void* v8, int64_t ldv8, int64_t v8_bstride, const void* v8_scales,
-                                             const void* vt, int64_t ldvt, int64_t vt_bstride,
-                                             void* out, int64_t ldo, int64_t o_bstride,
-                                             int batch, int Lq, int Lk, int num_heads, int head_dim,
-                                             void* workspace, int64_t workspace_bytes, void* stream) {
-    WAN_REQUIRE(v8 && v8_scales, WAN_ERR_INVALID, "wan_attention_fwd_f8: null tensor");
-    const Qk8Operands ops = {q_exp, k_exp, v8, ldv8, v8_bstride, v8_scales};
-    return attention_fwd_impl(q8, ldq8, q8_bstride, k8, ldk8, k8_bstride, vt, ldvt, vt_bstride, out, ldo, o_bstride, batch, Lq, Lk,
-                              num_heads, head_dim, 1.0f, WAN_ATTN_Q_PRESCALED, workspace, workspace_bytes, stream, &ops);
-}
-
-extern "C" int64_t wan_vt_mx_scale_bytes(int batch, int num_heads, int Lk) {
-    return batch > 0 && num_heads > 0 && Lk > 0 ? (int64_t)batch * num_heads * vt_mx_scale_bytes_per_head(Lk) : 0;
 }
 
 extern "C" wan_status_t wan_vt_quantize_mx(const void* vt_bf16, int64_t ldvt, int64_t vt_bstride, int batch, int num_heads, int Lk,
@@ -1626,20 +1380,18 @@ extern "C" wan_status_t wan_vt_quantize_mx(const void* vt_bf16, int64_t ldvt, in
     const int ntiles = (int)(lk_pad / kKV), C = num_heads * kD;
     hipLaunchKernelGGL(vt_quantize_mx_kernel, dim3((unsigned)((ntiles + 7) / 8), (unsigned)C, (unsigned)batch), dim3(64), 0, (hipStream_t)stream,
                        (const bf16_t*)vt_bf16, ldvt, vt_bstride, C, num_heads, ntiles, (unsigned char*)v8, ldv8, v8_bstride,
-                       (unsigned char*)v8_scales, vt_mx_scale_bytes_per_head(Lk));
+                       (unsigned char*)v8_scales, wan_vt_mx_scale_bytes_per_head(Lk));
     WAN_CHECK_LAUNCH("wan_vt_quantize_mx");
     return WAN_OK;
 }
 
-extern "C" wan_status_t wan_transpose_bf16(const void* in, int64_t ld, void* out_t, int64_t ldt,
-                                           int64_t rows, int cols, void* stream) {
+extern "C" wan_status_t wan_transpose_bf16(const void* in, int64_t ld, void* out_t, int64_t ldt, int64_t rows, int cols, void* stream) {
     WAN_REQUIRE(in && out_t, WAN_ERR_INVALID, "wan_transpose_bf16: null tensor");
     WAN_REQUIRE(rows >= 0 && cols > 0 && ld >= cols && ldt >= rows, WAN_ERR_INVALID,
                 "wan_transpose_bf16: rows=%lld cols=%d ld=%lld ldt=%lld", (long long)rows, cols, (long long)ld, (long long)ldt);
     if (ldt == 0) return WAN_OK;
     dim3 grid((unsigned)((ldt + 63) / 64), (unsigned)((cols + 63) / 64)), block(256);
-    hipLaunchKernelGGL(transpose_bf16_kernel, grid, block, 0, (hipStream_t)stream, (const bf16_t*)in, ld,
-                       (bf16_t*)out_t, ldt, rows, cols);
+    hipLaunchKernelGGL(transpose_bf16_kernel, grid, block, 0, (hipStream_t)stream, (const bf16_t*)in, ld, (bf16_t*)out_t, ldt, rows, cols);
     WAN_CHECK_LAUNCH("wan_transpose_bf16");
     return WAN_OK;
 }
