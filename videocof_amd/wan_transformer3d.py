@@ -22,6 +22,7 @@ There is no eager fallback: CPU tensors raise.
 """
 from __future__ import annotations
 
+import ctypes
 import glob
 import json
 import math
@@ -34,7 +35,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from ._lib import RopeParams
+from ._lib import BlockWeights, BlockWorkspace, DitWeights, DitWorkspace, RopeParams, check, load
 from .dist import get_sp_group
 
 __all__ = ["WanTransformer3DModel", "sinusoidal_embedding_1d", "rope_params"]
@@ -88,6 +89,20 @@ class _Block:
     __slots__ = ("w_qk", "b_qk", "w_v", "b_v", "w_o", "b_o", "nq", "nk",
                  "w_cq", "b_cq", "w_ck", "b_ck", "w_cv", "b_cv", "w_co", "b_co", "ncq", "nck",
                  "n3w", "n3b", "w1", "b1", "w2", "b2", "modulation", "f8", "_cw", "spw")
+
+
+# Linear of a block -> its (weight, bias) on _Block; blk.f8 holds the e4m3 copy (weight, per-output-channel scales) under the same key
+_LINEARS = {"qk": ("w_qk", "b_qk"), "v": ("w_v", "b_v"), "o": ("w_o", "b_o"), "cq": ("w_cq", "b_cq"), "co": ("w_co", "b_co"),
+            "w1": ("w1", "b1"), "w2": ("w2", "b2")}
+# ... and what stands in for (Linear, half of q | k) under Ulysses with padded heads: (weight, bias or None = the block's) on blk.spw
+_SPW_LINEARS = {("qk", 0): ("w_q", "b_q"), ("qk", 1): ("w_k", "b_k"), ("v", None): ("w_v", "b_v"), ("o", None): ("w_o", None)}
+# Linear fed by a bf16 activation -> the workspace's (e4m3 rows, row scales) its row-quantising pass writes
+_ROW_QUANT = {"o": ("attq", "atts"), "co": ("attq", "atts"), "w2": ("ffq", "ffs")}
+
+
+def _e4m3_exponent(amax: float) -> int:
+    """The power of two, within 2^-8 .. 2^8, that brings a magnitude of `amax` one bit below the e4m3 clamp (+-448)."""
+    return int(max(-8, min(8, math.floor(math.log2(448.0 / max(amax, 1e-30))) - 1)))
 
 
 def cfg_skip_active(batch: int, cfg_skip_ratio, current_steps, num_inference_steps) -> bool:
@@ -768,31 +783,6 @@ class WanTransformer3DModel(nn.Module):
         self._ctx_cache = (list(context), vers, kv, {})      # {}: tail views handed to cfg_skip steps, by sample count
         return kv
 
-    def _last_block_suffix(self, blk, em, xs, h, qk, vt, att, cq, ff, ctx_kv, rp, r0, L):
-        """The last WanAttentionBlock for B = 1 when only rows >= r0 feed the output: K / V^T are built
-        from every token, everything per-query (q, attention, o, cross-attention, FFN) only for the suffix."""
-        C, H, Ll = self.dim, self.num_heads, xs.shape[0]
-        ops.ln_modulate(xs, em[1], em[0], True, Ll, self.eps, out=h)
-        ops.gemm(h, blk.w_qk[C:], blk.b_qk[C:], ops.EPI_BF16, out=qk[:, C:])            # k for all tokens
-        ops.gemm(h[r0:], blk.w_qk[:C], blk.b_qk[:C], ops.EPI_BF16, out=qk[r0:, :C])      # q for the suffix
-        ops.rmsnorm_rope_(qk[:r0, C:], blk.nk, None, None, self.d, self.eps, self._rope_dev, rp)
-        rp2 = type(rp)(rp.F, rp.Hp, rp.Wp, rp.mode, rp.f_src, rp.ground_end, r0, Ll - r0, rp.max_pos)
-        ops.rmsnorm_rope_(qk[r0:, :C], blk.nq, qk[r0:, C:], blk.nk, self.d, self.eps, self._rope_dev, rp2, x0_scale=self._qs)
-        ops.gemm(h[:L], blk.w_v, blk.b_v, ops.EPI_BF16_T, out=vt[0])
-        n = Ll - r0
-        ops.attention_fwd(qk[r0:, :C].unsqueeze(0), qk[:, C:].unsqueeze(0), vt, H, k_len=L, out=att[r0:].unsqueeze(0), q_prescaled=True,
-                          workspace=self._ws_self_sfx)
-        ops.gemm(att[r0:], blk.w_o, blk.b_o, ops.EPI_RESID_F32, out=xs[r0:], gate=em[2], rows_per_batch=n)
-        ops.ln_modulate(xs[r0:], blk.n3w, blk.n3b, False, n, self.eps, out=h[r0:])
-        ops.gemm(h[r0:], blk.w_cq, blk.b_cq, ops.EPI_BF16, out=cq[r0:])
-        ops.rmsnorm_rope_(cq[r0:], blk.ncq, None, None, self.d, self.eps, x0_scale=self._qs)
-        ck, cvt = ctx_kv
-        ops.attention_fwd(cq[r0:].unsqueeze(0), ck, cvt, H, out=att[r0:].unsqueeze(0), q_prescaled=True, workspace=self._ws_cross_sfx)
-        ops.gemm(att[r0:], blk.w_co, blk.b_co, ops.EPI_RESID_F32, out=xs[r0:])
-        ops.ln_modulate(xs[r0:], em[4], em[3], True, n, self.eps, out=h[r0:])
-        ops.gemm(h[r0:], blk.w1, blk.b1, ops.EPI_GELU_BF16, out=ff[r0:])
-        ops.gemm(ff[r0:], blk.w2, blk.b2, ops.EPI_RESID_F32, out=xs[r0:], gate=em[5], rows_per_batch=n)
-
     def _event_pair(self):
         if self._attn_events is None:
             return None
@@ -889,7 +879,6 @@ class WanTransformer3DModel(nn.Module):
                 b.q8 = torch.empty(M, C, device=dev, dtype=ops.FP8)
                 b.k8 = torch.empty(M, C, device=dev, dtype=ops.FP8)
                 b.kmean = torch.empty(B, C, device=dev, dtype=torch.float32)
-                from ._lib import load
                 b.kmean_ws = torch.empty(int(load().wan_col_mean_workspace_bytes(B, C)) // 4, device=dev, dtype=torch.float32)
                 if "attn_pv" in self._fp8:
                     b.v8 = torch.empty_like(b.vt_full if self._usp else b.vt, dtype=ops.FP8)
@@ -919,265 +908,277 @@ class WanTransformer3DModel(nn.Module):
         # may still replay from it -- `ops.release_gemm_workspaces(include_capture=True)` is for a caller who knows every graph is gone.
         ops.release_gemm_workspaces(include_capture=False)
 
+    # ------------------------------------------------------------------ one WanAttentionBlock
+    def _linear(self, blk: _Block, key, a, epilogue, out, half=None, spw=None, **kw):
+        """Linear `key` of the block (_LINEARS) on the operand `a`: a bf16 tensor runs ops.gemm on the bf16 weight, a pair (e4m3 rows, their
+        row scales) -- what `_ln_operand` / `_row_operand` hand out when blk.f8 holds that Linear -- runs ops.gemm_fp8 on the e4m3 copy.
+        `half` (0: q, 1: k) takes that half of the fused q | k output rows (weight, scales and bias alike).  `spw`: the padded-head
+        copies of the Ulysses branch, which stand in for the entries of the table they hold (_SPW_LINEARS; bf16 only)."""
+        wn, bn = _LINEARS[key]
+        w, bias = getattr(blk, wn), getattr(blk, bn)
+        if spw is not None and (key, half) in _SPW_LINEARS:
+            wn, bn = _SPW_LINEARS[key, half]
+            w, bias, half = getattr(spw, wn), (getattr(spw, bn) if bn else bias), None
+        rows = None if half is None else slice(half * self.dim, (half + 1) * self.dim)
+        if isinstance(a, tuple):
+            w8, ws8 = blk.f8[key]
+            if rows is not None:    # the e4m3 copy and its per-output-channel scales split by rows like the bf16 weight
+                w8, ws8, bias = w8[rows], ws8[rows], bias[rows]
+            return ops.gemm_fp8(a[0], a[1], w8, ws8, bias, epilogue, out=out, **kw)
+        if rows is not None:
+            w, bias = w[rows], bias[rows]
+        return ops.gemm(a, w, bias, epilogue, out=out, **kw)
+
+    @staticmethod
+    def _rows(a, lo, hi):           # token rows [lo, hi) of a Linear's operand (either form)
+        return (a[0][lo:hi], a[1][lo:hi]) if isinstance(a, tuple) else a[lo:hi]
+
+    def _ln_operand(self, blk: _Block, key, x, scale, shift, add_one, rows, bufs, h=None, bf16=False):
+        """LayerNorm + modulation of x into the operand Linear `key` wants: e4m3 rows with their scales (quantised inside the kernel)
+        when blk.f8 holds that Linear, else bf16 in `h` (default bufs.h).  `bf16`: the caller runs on the bf16 weights regardless."""
+        if not bf16 and blk.f8 and key in blk.f8:
+            ops.ln_modulate_fp8(x, scale, shift, add_one, rows, self.eps, out=bufs.hq, out_scale=bufs.rs)
+            return bufs.hq, bufs.rs
+        h = bufs.h if h is None else h
+        ops.ln_modulate(x, scale, shift, add_one, rows, self.eps, out=h)
+        return h
+
+    def _row_operand(self, blk: _Block, key, a, bufs, bf16=False):
+        """The bf16 activation `a` (an attention output, the GELU output) as the operand Linear `key` wants: one row-quantising pass
+        when blk.f8 holds that Linear, else `a` itself."""
+        if not bf16 and blk.f8 and key in blk.f8:
+            q, s = (getattr(bufs, name) for name in _ROW_QUANT[key])
+            ops.quantize_rows_fp8(a, out=q, out_scale=s)
+            return q, s
+        return a
+
+    def _o_projection(self, blk: _Block, em, x, att, bufs, n, spw=None, bf16=False):        # x += gate * o(att) (:499), n rows per sample
+        self._linear(blk, "o", self._row_operand(blk, "o", att, bufs, bf16), ops.EPI_RESID_F32, x, spw=spw, gate=em[2], rows_per_batch=n)
+
+    def _norm_rope(self, blk: _Block, bufs, rp, B, Ll, L):
+        """RMSNorm + RoPE of the fused q | k projection in place and, with "attn" in blk.f8 (QK^T on the fp8 matrix pipe), the e4m3
+        operands bufs.q8 / bufs.k8.  Returns the exponents (qe, ke) those were written with."""
+        C, f8 = self.dim, blk.f8 or {}
+        q, k = bufs.qk[:, :C], bufs.qk[:, C:]
+        qe, ke = f8.get("attn_exp") or self.fp8_attn_exponents
+        if "attn" in f8 and not self.fp8_attn_smooth_k:       # the norm+rope kernel writes e4m3 q / k instead of bf16
+            ops.rmsnorm_rope_fp8(q, blk.nq, k, blk.nk, self.d, self.eps, self._rope_dev, rp, bufs.q8, bufs.k8,
+                                 x0_scale=self._qs * 2.0 ** qe, x1_scale=2.0 ** ke)
+            return qe, ke
+        ops.rmsnorm_rope_(q, blk.nq, k, blk.nk, self.d, self.eps, self._rope_dev, rp, x0_scale=self._qs)
+        if "attn" in f8:
+            # K smoothing (sageattn's smooth_k): the bf16 norm + rope as usual, the per-sample token mean of k, then e4m3 q and k - mean
+            ops.col_mean(k, Ll, L, B, out=bufs.kmean, workspace=bufs.kmean_ws)
+            qe, ke = self._calibrate(f8, q, k, bufs.kmean, B, Ll, L)
+            ops.qk_quantize_fp8(q, k, Ll, bufs.kmean, 2.0 ** qe, 2.0 ** ke, bufs.q8, bufs.k8)
+        return qe, ke
+
+    def _calibrate(self, f8, q_bf16, k_bf16, mean, B, rows_per_batch, L):
+        """Per-layer exponents from this call's operands (first forward after enable_fp8_linear; one host sync per layer, once).
+        Returns the pair in force."""
+        if self.fp8_attn_calibrate and "attn_exp" not in f8 and not torch.cuda.is_current_stream_capturing():
+            # over the L valid rows of every sample only (pad rows [L, Ll) are never attended; the sequence-parallel path
+            # measures the same rows, so both paths pick the exponents of the same operands)
+            kc = k_bf16.float().view(B, rows_per_batch, -1)[:, :L] - mean[:, None, :].float()
+            aq, ak = float(q_bf16.float().view(B, rows_per_batch, -1)[:, :L].abs().max()), float(kc.abs().max())
+            f8["attn_exp"] = (_e4m3_exponent(aq), _e4m3_exponent(ak))
+        return f8.get("attn_exp") or self.fp8_attn_exponents
+
+    def _self_attention(self, blk: _Block, em, xs, bufs, rp, B, Ll, L):
+        """Self-attention (:495-499) on one device up to its output bufs.att (the o projection follows in _run_block)."""
+        C, H, f8 = self.dim, self.num_heads, blk.f8 or {}
+        vt, att = bufs.vt, bufs.att.view(B, Ll, C)
+        a = self._ln_operand(blk, "qk", xs, em[1], em[0], True, Ll, bufs)
+        self._linear(blk, "qk", a, ops.EPI_BF16, bufs.qk)
+        qe, ke = self._norm_rope(blk, bufs, rp, B, Ll, L)
+        for b in range(B):
+            self._linear(blk, "v", self._rows(a, b * Ll, b * Ll + L), ops.EPI_BF16_T, vt[b])
+        ev = self._event_pair()
+        if "attn_pv" in f8:
+            ops.vt_quantize_mx(vt, H, L, v8=bufs.v8, scales=bufs.v8s)
+            ops.attention_fwd_f8(bufs.q8.view(B, Ll, C), bufs.k8.view(B, Ll, C), bufs.v8, bufs.v8s, vt, H, qe, ke, k_len=L, out=att,
+                                 workspace=self._ws_self)
+        elif "attn" in f8:
+            ops.attention_fwd_qk8(bufs.q8.view(B, Ll, C), bufs.k8.view(B, Ll, C), vt, H, qe, ke, k_len=L, out=att, workspace=self._ws_self)
+        else:
+            ops.attention_fwd(bufs.qk3[:, :, :C], bufs.qk3[:, :, C:], vt, H, k_len=L, out=att, q_prescaled=True, workspace=self._ws_self)
+        self._event_done(ev, B * Ll)
+        return bufs.att
+
+    def _self_attention_ulysses(self, blk: _Block, em, xs, bufs, rp, B, Ll, L, seq_len):
+        """Self-attention (:495-499) under Ulysses: returns its gathered output and the padded-head weight copies for the o projection (or None).
+        Every projection writes its result straight into the send layout of its own exchange (k, q: the RMSNorm+RoPE kernel's wire
+        output; V^T: the transposed GEMM epilogue with ldo = B * Ll) and is followed at once by that exchange (async, on RCCL's stream):
+        the k exchange runs under the V projection, the V^T exchange under the q projection, only the q exchange is exposed.  The
+        arrived q / k buffers ARE the attention operands ([P*Ll][B][C/P], uniform strides), the attention output IS the send buffer of
+        the inverse exchange; the only re-layout passes per layer are wan_sp_unpack_vt and wan_sp_unpack_heads (2 x M*C bf16 each way).
+        Padded heads (num_heads % P != 0, _pad_heads_for_ulysses): the attention side runs on Ca = C_pad channels / Ha = H_pad heads
+        with the wire-ordered, zero-padded weight copies; otherwise Ca = C and everything below is the model's own tensors."""
+        P, sp, f8, pad = self.sp_world_size, self._sp, blk.f8 or {}, self._sp_pad
+        spw = blk.spw if pad is not None else None
+        Ca, Ha, eps_a = (pad.C, pad.H, pad.eps) if pad is not None else (self.dim, self.num_heads, self.eps)
+        nq_a, nk_a, qk_a, att_a = (spw.nq, spw.nk, bufs.qk_a, bufs.att_a) if pad is not None else (blk.nq, blk.nk, bufs.qk, bufs.att)
+        Cl, Lt = Ca // P, P * Ll
+        a = self._ln_operand(blk, "qk", xs, em[1], em[0], True, Ll, bufs)
+        self._linear(blk, "qk", a, ops.EPI_BF16, qk_a[:, Ca:], half=1, spw=spw)
+        ops.rmsnorm_rope_sp(qk_a[:, Ca:], nk_a, None, None, self.d, eps_a, self._rope_dev, rp, bufs.kw_s, None, P, B)
+        wait_k = sp.exchange(bufs.kw_r, bufs.kw_s, async_op=True)
+        vsend = bufs.vw_s.view(Ca, B, Ll)
+        for b in range(B):
+            self._linear(blk, "v", self._rows(a, b * Ll, (b + 1) * Ll), ops.EPI_BF16_T, vsend[:, b], spw=spw)
+        wait_v = sp.exchange(bufs.vw_r, bufs.vw_s, async_op=True)
+        self._linear(blk, "qk", a, ops.EPI_BF16, qk_a[:, :Ca], half=0, spw=spw)
+        # Head groups (q and o only; k and V^T are already under the projections).  The RMSNorm of q spans ALL heads of a token
+        # (wan_transformer3d.py:264-267: WanRMSNorm(dim)), so no head group of q exists before the whole projection does -- the
+        # pipeline is between the exchanges and the attention launches, not inside the projection: with groups g0 | g1 the
+        # exposed transfers per layer are q(g0) and o(g1), ONE exchange's worth instead of two.
+        Hl = Ha // P
+        h0 = Hl // 2 if (self.sp_head_groups >= 2 and Hl >= 2) else 0
+        split = h0 * self.d                                   # group 0: channels [0, split) of every slab
+        ops.rmsnorm_rope_sp(qk_a[:, :Ca], nq_a, None, None, self.d, eps_a, self._rope_dev, rp, bufs.qw_s, None, P, B,
+                            x0_scale=self._qs, split=split)
+        # The head groups of this rank: (first channel, channels, heads, its stretch of every wire buffer).  A group's wire buffer reads
+        # as [P*Ll][B][its channels]; k / V^T of a group are column / row slices of the whole arrived ones.
+        groups = [(c0, cg, hg, slice(Lt * B * c0, Lt * B * (c0 + cg)))
+                  for c0, cg, hg in ([(0, split, h0), (split, Cl - split, Hl - h0)] if h0 else [(0, Cl, Hl)])]
+        q_waits = [sp.exchange(bufs.qw_r[cut], bufs.qw_s[cut], async_op=True) for _, _, _, cut in groups]
+        cev = self._comm_pair("q_g0")       # exposed: whatever of the exchanges the projections did not cover (q: group 0 only)
+        wait_k()
+        wait_v()
+        ops.sp_unpack_vt(bufs.vw_r, bufs.vt_full, P, Ll)
+        k_all = bufs.kw_r.view(Lt, B, Cl).permute(1, 0, 2)
+        fp8 = self._ulysses_fp8_k(f8, bufs, groups, q_waits, B, Cl, Lt, L) if "attn" in f8 else None
+        wait_o = []
+        ev = self._event_pair()
+        for gi, (c0, cg, hg, cut) in enumerate(groups):
+            q_waits[gi]()                   # group 0: exposed; group 1 arrived under the attention of group 0
+            if gi == 0:
+                self._comm_done(cev)
+            o_g = bufs.ow_s[cut].view(Lt, B, cg).permute(1, 0, 2)     # [B, P*Ll, cg]: row stride B*cg, sample stride cg
+            if fp8 is not None:
+                self._ulysses_fp8_attention(f8, bufs, groups[gi], fp8, o_g, B, Lt, L)
+            else:
+                ops.attention_fwd(bufs.qw_r[cut].view(Lt, B, cg).permute(1, 0, 2), k_all[..., c0:c0 + cg], bufs.vt_full[:, c0:c0 + cg], hg,
+                                  k_len=L, out=o_g, q_prescaled=True, workspace=self._ws_self)
+            if gi + 1 < len(groups):        # ... the output of group 0 leaves under the attention of group 1
+                wait_o.append(sp.exchange(bufs.ow_r[cut], bufs.ow_s[cut], async_op=True))
+        self._event_done(ev, B * seq_len)
+        cev = self._comm_pair("o_g1")       # exposed: the inverse exchange sits between attention and the o projection (group 1 only)
+        sp.exchange(bufs.ow_r[cut], bufs.ow_s[cut])          # (cut: the last group's stretch)
+        for w_ in wait_o:
+            w_()
+        self._comm_done(cev)
+        # (padded heads: [B*Ll, Ca] in wire order; the o projection's padded weight has the matching columns)
+        ops.sp_unpack_heads(bufs.ow_r, att_a, P, Ll, B, split=split)
+        return att_a, spw
+
+    def _ulysses_fp8_k(self, f8, bufs, groups, q_waits, B, Cl, Lt, L):
+        """fp8 attention on the arrived operands (bf16 wires; every rank holds ALL tokens of its heads, so the K mean is local).
+        The token-major wire [P*Ll][B][Cl] is one [P*Ll, B*Cl] matrix: a column is one (sample, channel) pair, so one column
+        mean / one quantisation pass covers every sample of the CFG batch.  k is quantised once, when it has arrived (here); every
+        head group of q when ITS exchange completes (_ulysses_fp8_attention: group 1 still travels under the attention of group 0).
+        Returns (qe, ke, the e4m3 k as [B, P*Ll, Cl], MX scale bytes per (sample, head) of V^T or 0)."""
+        k2d = bufs.kw_r.view(Lt, B * Cl)
+        mean = (ops.col_mean(k2d, Lt, L, 1, out=bufs.kmean.view(-1)[:B * Cl].view(1, B * Cl), workspace=bufs.kmean_ws)
+                if self.fp8_attn_smooth_k else None)
+        # Whether to enter the collective below must be decided by state that is THE SAME ON EVERY RANK, or the ranks dead-lock:
+        # `fp8_attn_calibrate` (set by enable_fp8_linear, which every rank calls alike) and "attn_exp_agreed" (set only here,
+        # by the collective itself) -- not by a rank-local preset of "attn_exp" or by whether this rank happens to be capturing.
+        if self.fp8_attn_calibrate and not f8.get("attn_exp_agreed"):
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("fp8 attention under sequence parallelism calibrates its exponents on the first EAGER forward "
+                                   "(one all-reduce per layer); run one before capturing a graph")
+            # per-layer exponents, agreed by the ranks: each rank holds other heads, so the operands' maxima are reduced
+            # (max) over the group -- the pair every rank then uses is the one a single device would have measured
+            for w_ in q_waits:
+                w_()
+            kc = k2d[:L].float() if mean is None else k2d[:L].float() - mean.float()
+            q_amax = torch.stack([bufs.qw_r[cut.start:cut.start + L * B * cg].float().abs().max() for (_, cg, _, cut) in groups]).max()
+            amax = torch.stack([q_amax, kc.abs().max()])       # (over the L valid token rows of every sample)
+            if self.sp_world_size > 1:
+                amax = self._sp.all_reduce_max(amax)
+            aq, ak = (float(v) for v in amax.tolist())
+            if "attn_exp" not in f8:            # (a preset pair stays: exponents need not agree across ranks for correctness)
+                f8["attn_exp"] = (_e4m3_exponent(aq), _e4m3_exponent(ak))
+            f8["attn_exp_agreed"] = True
+        qe, ke = f8.get("attn_exp") or self.fp8_attn_exponents
+        k8w = bufs.k8.view(-1)[:Lt * B * Cl]
+        ops.qk_quantize_fp8(None, k2d, Lt, mean, 1.0, 2.0 ** ke, None, k8w)
+        return qe, ke, k8w.view(Lt, B, Cl).permute(1, 0, 2), int(load().wan_vt_mx_scale_bytes(1, 1, L)) if "attn_pv" in f8 else 0
+
+    def _ulysses_fp8_attention(self, f8, bufs, group, fp8, o_g, B, Lt, L):
+        """One head group of the fp8 attention under Ulysses: its arrived q quantised, then the QK^T-fp8 or the all-fp8 kernel."""
+        (c0, cg, hg, cut), (qe, ke, k8_all, hs) = group, fp8
+        q8g = bufs.q8.view(-1)[cut]
+        ops.qk_quantize_fp8(bufs.qw_r[cut].view(Lt, B * cg), None, Lt, None, 2.0 ** qe, 1.0, q8g, None)
+        q8v = q8g.view(Lt, B, cg).permute(1, 0, 2)
+        vt_g = bufs.vt_full[:, c0:c0 + cg]
+        if "attn_pv" in f8:
+            # a group's V^T is quantised on its own (rows [c0, c0 + cg) of every sample; its scales are a [B][hg] block)
+            v8g, s8g = bufs.v8[:, c0:c0 + cg], bufs.v8s[B * (c0 // self.d) * hs:B * (c0 // self.d + hg) * hs]
+            ops.vt_quantize_mx(vt_g, hg, L, v8=v8g, scales=s8g)
+            ops.attention_fwd_f8(q8v, k8_all[..., c0:c0 + cg], v8g, s8g, vt_g, hg, qe, ke, k_len=L, out=o_g, workspace=self._ws_self)
+        else:
+            ops.attention_fwd_qk8(q8v, k8_all[..., c0:c0 + cg], vt_g, hg, qe, ke, k_len=L, out=o_g, workspace=self._ws_self)
+
+    def _block_tail(self, blk: _Block, em, xs, bufs, ctx_kv, B, n, ws_cross, r0=0, bf16=False):
+        """The token-local rest of the block -- norm3, cross-attention, FFN (:504-511) -- on rows [r0:] of the stream, n rows per sample
+        (r0 > 0: the suffix of a single sample).  `ws_cross`: the call site's attention scratch.  `bf16`: on the bf16 weights whatever blk.f8 holds."""
+        C = self.dim
+        x, h, cq, att, ff = xs, bufs.h, bufs.cq, bufs.att, bufs.ff
+        if r0:
+            x, h, cq, att, ff = x[r0:], h[r0:], cq[r0:], att[r0:], ff[r0:]
+        # ---- cross attention (:504), text rows are NOT masked (context_lens=None, :936)
+        a = self._ln_operand(blk, "cq", x, blk.n3w, blk.n3b, False, B * n, bufs, h, bf16)
+        self._linear(blk, "cq", a, ops.EPI_BF16, cq)
+        ops.rmsnorm_rope_(cq, blk.ncq, None, None, self.d, self.eps, x0_scale=self._qs)
+        ops.attention_fwd(cq.view(B, n, C), *ctx_kv, self.num_heads, out=att.view(B, n, C), q_prescaled=True, workspace=ws_cross)
+        self._linear(blk, "co", self._row_operand(blk, "co", att, bufs, bf16), ops.EPI_RESID_F32, x)
+        # ---- FFN (:507-511)
+        a = self._ln_operand(blk, "w1", x, em[4], em[3], True, n, bufs, h, bf16)
+        self._linear(blk, "w1", a, ops.EPI_GELU_BF16, ff)
+        self._linear(blk, "w2", self._row_operand(blk, "w2", ff, bufs, bf16), ops.EPI_RESID_F32, x, gate=em[5], rows_per_batch=n)
+
     def _run_block(self, blk: _Block, em, xs, bufs, ctx_kv, rp, B, Ll, L, seq_len):
         """One WanAttentionBlock (:464-515) in place on the fp32 residual stream xs [B*Ll, C].
         em: [6, B, C] = modulation + e0 (:495); ctx_kv: (k [B,512,C], v^T [B,C,512]) of the text tokens."""
-        C, H, P, M = self.dim, self.num_heads, self.sp_world_size, B * Ll
-        h, qk, att, cq, ff, vt, qk3 = bufs.h, bufs.qk, bufs.att, bufs.cq, bufs.ff, bufs.vt, bufs.qk3
-        usp = self._usp
-        f8 = blk.f8 or {}                                       # fp8 Linears (every projection below has both forms, Ulysses included)
-        a8_sp = usp and "attn" in f8                            # the fp8 attention products also run on the arrived Ulysses operands
-        if not usp and not f8 and self._attn_events is None and self.use_block_composite:
+        composite = not blk.f8 and self._attn_events is None and self.use_block_composite
+        if composite and not self._usp:
             # the same launch sequence as below, enqueued by ONE C call (wan_dit_block_forward): 1 FFI crossing instead of 15
             self._block_composite(blk, em, xs, bufs, ctx_kv, rp, B, Ll, L)
             return
-        # ---- self attention (:495-499)
-        if "qk" in f8:
-            ops.ln_modulate_fp8(xs, em[1], em[0], True, Ll, self.eps, out=bufs.hq, out_scale=bufs.rs)
+        e = em.unbind(0)                    # the six [B, C] rows of em (one call instead of six selects of the same views)
+        if self._usp:
+            att, spw = self._self_attention_ulysses(blk, e, xs, bufs, rp, B, Ll, L, seq_len)
         else:
-            ops.ln_modulate(xs, em[1], em[0], True, Ll, self.eps, out=h)
-        a8 = "attn" in f8                 # QK^T on the fp8 matrix pipe: the norm+rope kernel writes e4m3 q / k instead of bf16
-        qe, ke = f8.get("attn_exp") or self.fp8_attn_exponents
-
-        def calibrate(q_bf16, k_bf16, mean, rows_per_batch):
-            """Per-layer exponents from this call's operands (first forward after enable_fp8_linear; one host sync per layer, once)."""
-            nonlocal qe, ke
-            if not (self.fp8_attn_calibrate and "attn_exp" not in f8) or torch.cuda.is_current_stream_capturing():
-                return
-            # over the L valid rows of every sample only (pad rows [L, Ll) are never attended; the sequence-parallel path below
-            # measures the same rows, so both paths pick the exponents of the same operands)
-            kc = k_bf16.float().view(B, rows_per_batch, -1)[:, :L]
-            if mean is not None:
-                kc = kc - mean[:, None, :].float()
-            aq, ak = float(q_bf16.float().view(B, rows_per_batch, -1)[:, :L].abs().max()), float(kc.abs().max())
-            pick = lambda a: int(max(-8, min(8, math.floor(math.log2(448.0 / max(a, 1e-30))) - 1)))
-            qe, ke = pick(aq), pick(ak)
-            f8["attn_exp"] = (qe, ke)
-
-        def norm_rope():
-            if a8 and self.fp8_attn_smooth_k:
-                # K smoothing (sageattn's smooth_k): the bf16 norm + rope as usual, the per-sample token mean of k, then e4m3 q and k - mean
-                ops.rmsnorm_rope_(qk[:, :C], blk.nq, qk[:, C:], blk.nk, self.d, self.eps, self._rope_dev, rp, x0_scale=self._qs)
-                ops.col_mean(qk[:, C:], Ll, L, B, out=bufs.kmean, workspace=bufs.kmean_ws)
-                calibrate(qk[:, :C], qk[:, C:], bufs.kmean, Ll)
-                ops.qk_quantize_fp8(qk[:, :C], qk[:, C:], Ll, bufs.kmean, 2.0 ** qe, 2.0 ** ke, bufs.q8, bufs.k8)
-            elif a8:
-                ops.rmsnorm_rope_fp8(qk[:, :C], blk.nq, qk[:, C:], blk.nk, self.d, self.eps, self._rope_dev, rp, bufs.q8, bufs.k8,
-                                     x0_scale=self._qs * 2.0 ** qe, x1_scale=2.0 ** ke)
-            else:
-                ops.rmsnorm_rope_(qk[:, :C], blk.nq, qk[:, C:], blk.nk, self.d, self.eps, self._rope_dev, rp, x0_scale=self._qs)
-
-        if not usp and "qk" in f8:
-            ops.gemm_fp8(bufs.hq, bufs.rs, *f8["qk"], blk.b_qk, ops.EPI_BF16, out=qk)
-            norm_rope()
-            for b in range(B):
-                ops.gemm_fp8(bufs.hq[b * Ll:(b + 1) * Ll][:L], bufs.rs[b * Ll:(b + 1) * Ll][:L], *f8["v"], blk.b_v,
-                             ops.EPI_BF16_T, out=vt[b])
-        elif not usp:
-            ops.gemm(h, blk.w_qk, blk.b_qk, ops.EPI_BF16, out=qk)
-            norm_rope()
-            for b in range(B):
-                ops.gemm(h[b * Ll:(b + 1) * Ll][:L], blk.w_v, blk.b_v, ops.EPI_BF16_T, out=vt[b])
-        if not usp:
-            ev = self._event_pair()
-            if a8 and "attn_pv" in f8:
-                ops.vt_quantize_mx(vt, H, L, v8=bufs.v8, scales=bufs.v8s)
-                ops.attention_fwd_f8(bufs.q8.view(B, Ll, C), bufs.k8.view(B, Ll, C), bufs.v8, bufs.v8s, vt, H, qe, ke, k_len=L,
-                                     out=att.view(B, Ll, C), workspace=self._ws_self)
-            elif a8:
-                ops.attention_fwd_qk8(bufs.q8.view(B, Ll, C), bufs.k8.view(B, Ll, C), vt, H, qe, ke, k_len=L, out=att.view(B, Ll, C),
-                                      workspace=self._ws_self)
-            else:
-                ops.attention_fwd(qk3[:, :, :C], qk3[:, :, C:], vt, H, k_len=L, out=att.view(B, Ll, C), q_prescaled=True,
-                                  workspace=self._ws_self)
-            self._event_done(ev, B * Ll)
-            o_in = att
-        else:
-            # Ulysses.  Every projection writes its result straight into the send layout of its own exchange (k, q: the
-            # RMSNorm+RoPE kernel's wire output; V^T: the transposed GEMM epilogue with ldo = B * Ll) and is followed at once
-            # by that exchange (async, on RCCL's stream): the k exchange runs under the V projection, the V^T exchange under
-            # the q projection, only the q exchange is exposed.  The arrived q / k buffers ARE the attention operands
-            # ([P*Ll][B][C/P], uniform strides), the attention output IS the send buffer of the inverse exchange; the only
-            # re-layout passes per layer are wan_sp_unpack_vt and wan_sp_unpack_heads (2 x M*C bf16 each way).
-            # Padded heads (num_heads % P != 0, _pad_heads_for_ulysses): the attention side runs on Ca = C_pad channels / Ha = H_pad heads
-            # with the wire-ordered, zero-padded weight copies; otherwise Ca = C and everything below is the model's own tensors.
-            pad = self._sp_pad
-            Ca, Ha = (pad.C, pad.H) if pad is not None else (C, H)
-            eps_a = pad.eps if pad is not None else self.eps
-            spw = blk.spw if pad is not None else None
-            nq_a, nk_a = (spw.nq, spw.nk) if pad is not None else (blk.nq, blk.nk)
-            qk_a = bufs.qk_a if pad is not None else qk
-            sp, Cl, Lt = self._sp, Ca // P, P * Ll
-            if "qk" in f8:          # e4m3 operands: the q | k weight copy and its per-output-channel scales split by rows like the bf16 one
-                w8, ws8 = f8["qk"]
-                proj = lambda rows, bias, out: ops.gemm_fp8(bufs.hq, bufs.rs, w8[rows], ws8[rows], bias, ops.EPI_BF16, out=out)
-                proj_vt = lambda b, out: ops.gemm_fp8(bufs.hq[b * Ll:(b + 1) * Ll], bufs.rs[b * Ll:(b + 1) * Ll], *f8["v"], blk.b_v,
-                                                      ops.EPI_BF16_T, out=out)
-            elif pad is not None:
-                proj = lambda rows, bias, out: ops.gemm(h, spw.w_k if rows.start else spw.w_q, spw.b_k if rows.start else spw.b_q,
-                                                        ops.EPI_BF16, out=out)
-                proj_vt = lambda b, out: ops.gemm(h[b * Ll:(b + 1) * Ll], spw.w_v, spw.b_v, ops.EPI_BF16_T, out=out)
-            else:
-                proj = lambda rows, bias, out: ops.gemm(h, blk.w_qk[rows], bias, ops.EPI_BF16, out=out)
-                proj_vt = lambda b, out: ops.gemm(h[b * Ll:(b + 1) * Ll], blk.w_v, blk.b_v, ops.EPI_BF16_T, out=out)
-            proj(slice(Ca, 2 * Ca), blk.b_qk[C:], qk_a[:, Ca:])
-            ops.rmsnorm_rope_sp(qk_a[:, Ca:], nk_a, None, None, self.d, eps_a, self._rope_dev, rp, bufs.kw_s, None, P, B)
-            wait_k = sp.exchange(bufs.kw_r, bufs.kw_s, async_op=True)
-            vsend = bufs.vw_s.view(Ca, B, Ll)
-            for b in range(B):
-                proj_vt(b, vsend[:, b])
-            wait_v = sp.exchange(bufs.vw_r, bufs.vw_s, async_op=True)
-            proj(slice(0, Ca), blk.b_qk[:C], qk_a[:, :Ca])
-            # Head groups (q and o only; k and V^T are already under the projections).  The RMSNorm of q spans ALL heads of a token
-            # (wan_transformer3d.py:264-267: WanRMSNorm(dim)), so no head group of q exists before the whole projection does -- the
-            # pipeline is between the exchanges and the attention launches, not inside the projection: with groups g0 | g1 the
-            # exposed transfers per layer are q(g0) and o(g1), ONE exchange's worth instead of two.
-            Hl = Ha // P
-            h0 = Hl // 2 if (self.sp_head_groups >= 2 and Hl >= 2) else 0
-            split, n0 = h0 * self.d, Lt * B * h0 * self.d        # group 0: channels [0, split) of every slab, n0 elements of wire
-            ops.rmsnorm_rope_sp(qk_a[:, :Ca], nq_a, None, None, self.d, eps_a, self._rope_dev, rp, bufs.qw_s, None, P, B,
-                                x0_scale=self._qs, split=split)
-            if h0:
-                wait_q = sp.exchange(bufs.qw_r[:n0], bufs.qw_s[:n0], async_op=True)
-                wait_q1 = sp.exchange(bufs.qw_r[n0:], bufs.qw_s[n0:], async_op=True)
-            else:
-                wait_q = sp.exchange(bufs.qw_r, bufs.qw_s, async_op=True)
-            cev = self._comm_pair("q_g0")       # exposed: whatever of the exchanges the projections did not cover (q: group 0 only)
-            wait_k()
-            wait_v()
-            ops.sp_unpack_vt(bufs.vw_r, bufs.vt_full, P, Ll)
-            # The head groups of this rank: (first channel, channels, heads, wire elements before it).  A group's wire buffer reads as
-            # [P*Ll][B][its channels]; k / V^T of a group are column / row slices of the whole arrived ones.
-            groups = [(0, split, h0, 0), (split, Cl - split, Hl - h0, n0)] if h0 else [(0, Cl, Hl, 0)]
-            q_waits = [wait_q, wait_q1] if h0 else [wait_q]
-            wire_g = lambda w, c0, cg, off: w[off:off + Lt * B * cg].view(Lt, B, cg).permute(1, 0, 2)     # [B, P*Ll, cg]: row stride B*cg, sample stride cg
-            k_all = bufs.kw_r.view(Lt, B, Cl).permute(1, 0, 2)
-            if a8_sp:
-                # fp8 attention on the arrived operands (bf16 wires; every rank holds ALL tokens of its heads, so the K mean is local).
-                # The token-major wire [P*Ll][B][Cl] is one [P*Ll, B*Cl] matrix: a column is one (sample, channel) pair, so one column
-                # mean / one quantisation pass covers every sample of the CFG batch.  k is quantised once, when it has arrived; every
-                # head group of q when ITS exchange completes (so group 1 still travels under the attention of group 0).
-                from ._lib import load
-                k2d = bufs.kw_r.view(Lt, B * Cl)
-                mean = None
-                if self.fp8_attn_smooth_k:
-                    mean = ops.col_mean(k2d, Lt, L, 1, out=bufs.kmean.view(-1)[:B * Cl].view(1, B * Cl), workspace=bufs.kmean_ws)
-                # Whether to enter the collective below must be decided by state that is THE SAME ON EVERY RANK, or the ranks dead-lock:
-                # `fp8_attn_calibrate` (set by enable_fp8_linear, which every rank calls alike) and "attn_exp_agreed" (set only here,
-                # by the collective itself) -- not by a rank-local preset of "attn_exp" or by whether this rank happens to be capturing.
-                if self.fp8_attn_calibrate and not f8.get("attn_exp_agreed"):
-                    if torch.cuda.is_current_stream_capturing():
-                        raise RuntimeError("fp8 attention under sequence parallelism calibrates its exponents on the first EAGER forward "
-                                           "(one all-reduce per layer); run one before capturing a graph")
-                    # per-layer exponents, agreed by the ranks: each rank holds other heads, so the operands' maxima are reduced
-                    # (max) over the group -- the pair every rank then uses is the one a single device would have measured
-                    for w_ in q_waits:
-                        w_()
-                    kc = k2d[:L].float() if mean is None else k2d[:L].float() - mean.float()
-                    q_amax = torch.stack([bufs.qw_r[off:off + L * B * cg].float().abs().max() for (_, cg, _, off) in groups]).max()
-                    amax = torch.stack([q_amax, kc.abs().max()])       # (over the L valid token rows of every sample)
-                    if self.sp_world_size > 1:
-                        amax = sp.all_reduce_max(amax)
-                    aq, ak = (float(v) for v in amax.tolist())
-                    pick = lambda a_: int(max(-8, min(8, math.floor(math.log2(448.0 / max(a_, 1e-30))) - 1)))
-                    if "attn_exp" not in f8:            # (a preset pair stays: exponents need not agree across ranks for correctness)
-                        qe, ke = pick(aq), pick(ak)
-                        f8["attn_exp"] = (qe, ke)
-                    f8["attn_exp_agreed"] = True
-                k8w = bufs.k8.view(-1)[:Lt * B * Cl]
-                ops.qk_quantize_fp8(None, k2d, Lt, mean, 1.0, 2.0 ** ke, None, k8w)
-                k8_all = k8w.view(Lt, B, Cl).permute(1, 0, 2)
-                pv8 = "attn_pv" in f8
-                hs = int(load().wan_vt_mx_scale_bytes(1, 1, L)) if pv8 else 0          # scale bytes per (sample, head)
-            wait_o = []
-            ev = self._event_pair()
-            for gi, (c0, cg, hg, off) in enumerate(groups):
-                q_waits[gi]()                   # group 0: exposed; group 1 arrived under the attention of group 0
-                if gi == 0:
-                    self._comm_done(cev)
-                o_g = wire_g(bufs.ow_s, c0, cg, off)
-                if a8_sp:
-                    q8g = bufs.q8.view(-1)[off:off + Lt * B * cg]
-                    ops.qk_quantize_fp8(bufs.qw_r[off:off + Lt * B * cg].view(Lt, B * cg), None, Lt, None, 2.0 ** qe, 1.0, q8g, None)
-                    q8v = q8g.view(Lt, B, cg).permute(1, 0, 2)
-                    vt_g = bufs.vt_full[:, c0:c0 + cg]
-                    if pv8:
-                        # a group's V^T is quantised on its own (rows [c0, c0 + cg) of every sample; its scales are a [B][hg] block)
-                        v8g, s8g = bufs.v8[:, c0:c0 + cg], bufs.v8s[B * (c0 // self.d) * hs:B * (c0 // self.d + hg) * hs]
-                        ops.vt_quantize_mx(vt_g, hg, L, v8=v8g, scales=s8g)
-                        ops.attention_fwd_f8(q8v, k8_all[..., c0:c0 + cg], v8g, s8g, vt_g, hg, qe, ke, k_len=L, out=o_g,
-                                             workspace=self._ws_self)
-                    else:
-                        ops.attention_fwd_qk8(q8v, k8_all[..., c0:c0 + cg], vt_g, hg, qe, ke, k_len=L, out=o_g, workspace=self._ws_self)
-                else:
-                    ops.attention_fwd(wire_g(bufs.qw_r, c0, cg, off), k_all[..., c0:c0 + cg], bufs.vt_full[:, c0:c0 + cg], hg, k_len=L,
-                                      out=o_g, q_prescaled=True, workspace=self._ws_self)
-                if gi + 1 < len(groups):        # ... the output of group 0 leaves under the attention of group 1
-                    wait_o.append(sp.exchange(bufs.ow_r[off:off + Lt * B * cg], bufs.ow_s[off:off + Lt * B * cg], async_op=True))
-            self._event_done(ev, B * seq_len)
-            cev = self._comm_pair("o_g1")       # exposed: the inverse exchange sits between attention and the o projection (group 1 only)
-            c0, cg, hg, off = groups[-1]
-            sp.exchange(bufs.ow_r[off:off + Lt * B * cg], bufs.ow_s[off:off + Lt * B * cg])
-            for w_ in wait_o:
-                w_()
-            self._comm_done(cev)
-            if pad is not None:                 # [B*Ll, Ca] in wire order; the o projection's padded weight has the matching columns
-                ops.sp_unpack_heads(bufs.ow_r, bufs.att_a, P, Ll, B, split=split)
-                ops.gemm(bufs.att_a, spw.w_o, blk.b_o, ops.EPI_RESID_F32, out=xs, gate=em[2], rows_per_batch=Ll)
-                o_in = None
-            else:
-                ops.sp_unpack_heads(bufs.ow_r, att, P, Ll, B, split=split)
-                o_in = att
-        if o_in is None:
-            pass
-        elif "o" in f8:
-            ops.quantize_rows_fp8(o_in, out=bufs.attq, out_scale=bufs.atts)
-            ops.gemm_fp8(bufs.attq, bufs.atts, *f8["o"], blk.b_o, ops.EPI_RESID_F32, out=xs, gate=em[2], rows_per_batch=Ll)
-        else:
-            ops.gemm(o_in, blk.w_o, blk.b_o, ops.EPI_RESID_F32, out=xs, gate=em[2], rows_per_batch=Ll)
-        if usp and not f8 and self._attn_events is None and self.use_block_composite:
+            att, spw = self._self_attention(blk, e, xs, bufs, rp, B, Ll, L), None
+        self._o_projection(blk, e, xs, att, bufs, Ll, spw)
+        if composite:
             # the token-local two thirds of the layer (norm3 -> cross-attention -> FFN) as ONE C call (wan_dit_block_tail_forward):
-            # the same launches as below, bit for bit
-            from ._lib import check, load
-            import ctypes
-            self._block_cw(blk)
-            self._block_cws(bufs, bufs, B, Ll, L)
-            ck, cvt = ctx_kv
-            check(load().wan_dit_block_tail_forward(ctypes.c_void_p(xs.data_ptr()), ctypes.c_void_p(em.data_ptr()),
-                                                    ctypes.c_void_p(ck.data_ptr()), ctypes.c_void_p(cvt.data_ptr()),
-                                                    ctypes.byref(blk._cw), ctypes.byref(bufs.cws), B, Ll, ops._stream()),
-                  "wan_dit_block_tail_forward")
+            # the same launches as _block_tail, bit for bit
+            self._block_composite(blk, em, xs, bufs, ctx_kv, None, B, Ll, L)
             return
-        # ---- cross attention (:504), text rows are NOT masked (context_lens=None, :936)
-        if "cq" in f8:
-            ops.ln_modulate_fp8(xs, blk.n3w, blk.n3b, False, M, self.eps, out=bufs.hq, out_scale=bufs.rs)
-            ops.gemm_fp8(bufs.hq, bufs.rs, *f8["cq"], blk.b_cq, ops.EPI_BF16, out=cq)
-        else:
-            ops.ln_modulate(xs, blk.n3w, blk.n3b, False, M, self.eps, out=h)
-            ops.gemm(h, blk.w_cq, blk.b_cq, ops.EPI_BF16, out=cq)
-        ops.rmsnorm_rope_(cq, blk.ncq, None, None, self.d, self.eps, x0_scale=self._qs)
-        ck, cvt = ctx_kv
-        ops.attention_fwd(cq.view(B, Ll, C), ck, cvt, H, out=att.view(B, Ll, C), q_prescaled=True, workspace=self._ws_cross)
-        if "co" in f8:
-            ops.quantize_rows_fp8(att, out=bufs.attq, out_scale=bufs.atts)
-            ops.gemm_fp8(bufs.attq, bufs.atts, *f8["co"], blk.b_co, ops.EPI_RESID_F32, out=xs)
-        else:
-            ops.gemm(att, blk.w_co, blk.b_co, ops.EPI_RESID_F32, out=xs)
-        # ---- FFN (:507-511)
-        if "w1" in f8:
-            ops.ln_modulate_fp8(xs, em[4], em[3], True, Ll, self.eps, out=bufs.hq, out_scale=bufs.rs)
-            ops.gemm_fp8(bufs.hq, bufs.rs, *f8["w1"], blk.b1, ops.EPI_GELU_BF16, out=ff)
-            ops.quantize_rows_fp8(ff, out=bufs.ffq, out_scale=bufs.ffs)
-            ops.gemm_fp8(bufs.ffq, bufs.ffs, *f8["w2"], blk.b2, ops.EPI_RESID_F32, out=xs, gate=em[5], rows_per_batch=Ll)
-        else:
-            ops.ln_modulate(xs, em[4], em[3], True, Ll, self.eps, out=h)
-            ops.gemm(h, blk.w1, blk.b1, ops.EPI_GELU_BF16, out=ff)
-            ops.gemm(ff, blk.w2, blk.b2, ops.EPI_RESID_F32, out=xs, gate=em[5], rows_per_batch=Ll)
+        self._block_tail(blk, e, xs, bufs, ctx_kv, B, Ll, self._ws_cross)
+
+    def _last_block_suffix(self, blk: _Block, em, xs, bufs, ctx_kv, rp, r0, L):
+        """The last WanAttentionBlock for B = 1 when only rows >= r0 feed the output: K / V^T are built
+        from every token, everything per-query (q, attention, o, cross-attention, FFN) only for the suffix.  On the bf16 weights."""
+        C, Ll, em = self.dim, xs.shape[0], em.unbind(0)
+        qk, att, n = bufs.qk, bufs.att, Ll - r0
+        h = self._ln_operand(blk, "qk", xs, em[1], em[0], True, Ll, bufs, bf16=True)
+        self._linear(blk, "qk", h, ops.EPI_BF16, qk[:, C:], half=1)                  # k for all tokens
+        self._linear(blk, "qk", h[r0:], ops.EPI_BF16, qk[r0:, :C], half=0)           # q for the suffix
+        ops.rmsnorm_rope_(qk[:r0, C:], blk.nk, None, None, self.d, self.eps, self._rope_dev, rp)
+        rp2 = RopeParams(rp.F, rp.Hp, rp.Wp, rp.mode, rp.f_src, rp.ground_end, r0, n, rp.max_pos)
+        ops.rmsnorm_rope_(qk[r0:, :C], blk.nq, qk[r0:, C:], blk.nk, self.d, self.eps, self._rope_dev, rp2, x0_scale=self._qs)
+        self._linear(blk, "v", h[:L], ops.EPI_BF16_T, bufs.vt[0])
+        ops.attention_fwd(qk[r0:, :C].unsqueeze(0), qk[:, C:].unsqueeze(0), bufs.vt, self.num_heads, k_len=L, out=att[r0:].unsqueeze(0),
+                          q_prescaled=True, workspace=self._ws_self_sfx)
+        self._o_projection(blk, em, xs[r0:], att[r0:], bufs, n, bf16=True)
+        self._block_tail(blk, em, xs, bufs, ctx_kv, 1, n, self._ws_cross_sfx, r0=r0, bf16=True)
 
     def _block_cw(self, blk: _Block):
         """The block's weights as a ``wan_block_weights`` (built once; the tensors it points at live as long as the block)."""
-        from ._lib import BlockWeights
-        import ctypes
         if getattr(blk, "_cw", None) is None:
             p = lambda t: ctypes.c_void_p(t.data_ptr())
             blk._cw = BlockWeights(self.dim, self.ffn_dim, self.num_heads, self.text_len, float(self.eps),
@@ -1188,8 +1189,6 @@ class WanTransformer3DModel(nn.Module):
 
     def _block_cws(self, bufs, holder, B, Ll, L):
         """``wan_block_workspace`` over the cached activation buffers, kept on `holder.cws`."""
-        from ._lib import BlockWorkspace, load
-        import ctypes
         if getattr(holder, "cws", None) is None:
             lib = load()
             p = lambda t: ctypes.c_void_p(t.data_ptr())
@@ -1222,8 +1221,6 @@ class WanTransformer3DModel(nn.Module):
     def _forward_composite(self, x, emod, ehead, kvs, rp, bufs, B, Ll, L, out_dtype, rep=1):
         """The token path of forward as ONE C call (wan_dit_forward, include/wan_hip.h a11'): used when nothing hooks into
         the block loop (no TeaCache, probes, fp8 projections, suffix-only last block, kernel events) on a single device."""
-        from ._lib import BlockWeights, DitWeights, DitWorkspace, check, load
-        import ctypes
         lib, w, n = load(), self._w, self.num_layers
         p = lambda t: ctypes.c_void_p(t.data_ptr())
         pt, ph, pw = self.patch_size
@@ -1253,17 +1250,18 @@ class WanTransformer3DModel(nn.Module):
         return out
 
     def _block_composite(self, blk: _Block, em, xs, bufs, ctx_kv, rp, B, Ll, L):
-        from ._lib import check, load
-        import ctypes
-        lib = load()
+        """One block as ONE C call: wan_dit_block_forward, or with rp = None its token-local part after the o projection
+        (wan_dit_block_tail_forward: what follows the Ulysses self-attention)."""
+        p = ctypes.c_void_p
         self._block_cw(blk)
         self._block_cws(bufs, bufs, B, Ll, L)
         ck, cvt = ctx_kv
-        check(lib.wan_dit_block_forward(ctypes.c_void_p(xs.data_ptr()), ctypes.c_void_p(em.data_ptr()),
-                                        ctypes.c_void_p(ck.data_ptr()), ctypes.c_void_p(cvt.data_ptr()),
-                                        ctypes.byref(blk._cw), ctypes.byref(bufs.cws), ctypes.c_void_p(self._rope_dev[0].data_ptr()),
-                                        ctypes.c_void_p(self._rope_dev[1].data_ptr()), ctypes.byref(rp), B, Ll, L,
-                                        ops._stream()), "wan_dit_block_forward")
+        args = (p(xs.data_ptr()), p(em.data_ptr()), p(ck.data_ptr()), p(cvt.data_ptr()), ctypes.byref(blk._cw), ctypes.byref(bufs.cws))
+        if rp is None:
+            check(load().wan_dit_block_tail_forward(*args, B, Ll, ops._stream()), "wan_dit_block_tail_forward")
+        else:
+            check(load().wan_dit_block_forward(*args, p(self._rope_dev[0].data_ptr()), p(self._rope_dev[1].data_ptr()), ctypes.byref(rp),
+                                               B, Ll, L, ops._stream()), "wan_dit_block_forward")
 
     @torch.no_grad()
     def head_forward(self, x: torch.Tensor, e: torch.Tensor) -> torch.Tensor:
@@ -1426,7 +1424,7 @@ class WanTransformer3DModel(nn.Module):
             if self._probe_layer == li:
                 self._probe = xs.clone()
             if r0 and li == self.num_layers - 1:
-                self._last_block_suffix(blk, emod[li], xs, bufs.h, bufs.qk, bufs.vt, bufs.att, bufs.cq, bufs.ff, kv, rp, r0, L)
+                self._last_block_suffix(blk, emod[li], xs, bufs, kv, rp, r0, L)
                 break
             self._run_block(blk, emod[li], xs, bufs, kv, rp, B, Ll, L, seq_len)
         if ori_x is not None:
