@@ -693,6 +693,47 @@ wan_status_t wan_frames_u8_compose(const wan_compose_src* srcs, int n_src, void*
  * comparisons with a NaN are false: no rescale).  Zeroes the word and enqueues one kernel on `stream`; never synchronises. */
 wan_status_t wan_video_range_flag(const void* x, int kind, int64_t n, int* flag, void* stream);
 
+/* 8-bit YCbCr planes <-> uint8 [T, H, W, 3] RGB frames: what a decoder yields (an ffmpeg pipe, an NV12 surface, a .y4m file) and what
+ * an encoder takes, converted on the device -- 1.5 bytes per pixel cross the host link instead of 3, the host does no pixel arithmetic.
+ * replaces: nothing in the reference, whose reader (imageio) converts to RGB on the host before load_video_frames sees a frame.
+ * Planes (wan_yuv_planes): a base pointer each, `*_extent` = the bytes addressable from that base (the geometry is checked against
+ * it and no load leaves it), strides in bytes.  Luma is H rows of W bytes; chroma is Ch x Cw samples, Cw = ceil(W / 2) if sub_x else
+ * W, Ch = ceil(H / 2) if sub_y else H, `c_step` bytes from one sample of a plane to the next (1 planar; 2 for NV12-style interleaved
+ * CbCr, where cr = cb + 1, or cb = cr + 1 for NV21).  cb = cr = NULL: mono (reading only; Cb = Cr = 128).  Any base alignment, any
+ * row stride >= the row, any frame stride (writing: >= a frame).
+ * Integer arithmetic only, all shifts arithmetic, every sum fits an int32 (videocof_amd/video_io.py: yuv_matrix builds the tables in
+ * float64, reference_yuv_to_frames / reference_frames_to_yuv restate this in numpy and equal the kernels byte for byte):
+ *   in   chroma up: per axis two samples with weights in quarters, indices clamped to the plane --
+ *            not subsampled (c[i], 4);  centred: even i (c[i/2 - 1], 1), (c[i/2], 3), odd i (c[i/2], 3), (c[i/2 + 1], 1);
+ *            left co-sited: even i (c[i/2], 4), odd i (c[i/2], 2), (c[i/2 + 1], 2)
+ *        C = (sum over the 2 x 2 taps of wy * wx * c + 8) >> 4, one rounding; vertical always centred, horizontal by `cosited`;
+ *        rgb[c] = clamp((k[3c] * (Y - yo) + k[3c + 1] * (Cb - 128) + k[3c + 2] * (Cr - 128) + 2^15) >> 16, 0, 255)
+ *   out  (Y, Cb, Cr)[c] = clamp((k[3c] * R + k[3c + 1] * G + k[3c + 2] * B + (off[c] << 16) + 2^15) >> 16, 0, 255), off = (yo, 128, 128);
+ *        4:2:0 (sub_x = sub_y = 1): (a + b + c + d + 2) >> 2 over each 2 x 2 block of those 8-bit chroma values, the last column / row
+ *        repeated when W / H is odd (centre siting; `cosited` is not read); 4:4:4 (sub_x = sub_y = 0): the per-pixel values.  Other
+ *        subsamplings are not written -> WAN_ERR_UNSUPPORTED.
+ * wan_yuv_coef: the nine 16-bit fixed-point coefficients (|k| < 2^23) and the luma offset, by value from HOST memory.
+ * A thread moves 16 pixels: 48 RGB bytes, 16 luma bytes, 8 or 16 chroma bytes per plane, each as dwordx4 / dwordx2 where its address
+ * allows, as aligned dwords shifted with v_alignbyte_b32 elsewhere, byte by byte at the end of a row; no byte outside the described
+ * rows is written.  T <= 65535 -> else WAN_ERR_UNSUPPORTED.  A geometry that leaves an extent, planes that overlap on the way out or
+ * a null argument is WAN_ERR_INVALID before anything is enqueued.  Enqueues one kernel on `stream`; never synchronises. */
+typedef struct {
+    void* y;
+    void* cb;
+    void* cr;
+    int64_t y_extent, cb_extent, cr_extent;
+    int64_t y_row, y_frame, c_row, c_frame;
+    int c_step, sub_x, sub_y, cosited;
+} wan_yuv_planes;
+typedef struct {
+    int k[9];
+    int yo;
+} wan_yuv_coef;
+wan_status_t wan_yuv_to_frames_u8(const wan_yuv_planes* planes, const wan_yuv_coef* inverse, void* frames_u8, int T, int H, int W,
+                                  void* stream);
+wan_status_t wan_frames_u8_to_yuv(const void* frames_u8, const wan_yuv_planes* planes, const wan_yuv_coef* forward, int T, int H, int W,
+                                  void* stream);
+
 /* ===========================================================================
  * the umT5 text encoder (videox_fun/models/wan_text_encoder.py:256-304), the step
  * before the denoising path.  Its Linear layers are wan_gemm_bf16; the rest:

@@ -65,6 +65,18 @@ COMPOSE_U8, COMPOSE_F32, COMPOSE_BF16 = 0, 1, 2                                 
 COMPOSE_COPY, COMPOSE_LOADER_ROUNDTRIP, COMPOSE_WRITER, COMPOSE_NORMALIZE = 0, 1, 2, 3  # wan_compose_src.mode
 
 
+class YuvPlanes(Structure):
+    """``wan_yuv_planes`` of include/wan_hip.h."""
+    _fields_ = ([(n, c_void_p) for n in ("y", "cb", "cr")] +
+                [(n, c_int64) for n in ("y_extent", "cb_extent", "cr_extent", "y_row", "y_frame", "c_row", "c_frame")] +
+                [(n, c_int) for n in ("c_step", "sub_x", "sub_y", "cosited")])
+
+
+class YuvCoef(Structure):
+    """``wan_yuv_coef`` of include/wan_hip.h."""
+    _fields_ = [("k", c_int * 9), ("yo", c_int)]
+
+
 class ConvParams(Structure):
     """``wan_conv_params`` of include/wan_hip.h."""
     _fields_ = [(n, c_int) for n in ("T_in", "H_in", "W_in", "Cin", "T_out", "H_out", "W_out", "Cout",
@@ -221,6 +233,8 @@ SIGNATURES = {
                                        c_void_p]),
     "wan_frames_u8_compose": (c_int, [POINTER(ComposeSrc), c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "wan_video_range_flag": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_void_p]),
+    "wan_yuv_to_frames_u8": (c_int, [POINTER(YuvPlanes), POINTER(YuvCoef), c_void_p, c_int, c_int, c_int, c_void_p]),
+    "wan_frames_u8_to_yuv": (c_int, [c_void_p, POINTER(YuvPlanes), POINTER(YuvCoef), c_int, c_int, c_int, c_void_p]),
 }
 
 _lib = None

@@ -1066,6 +1066,83 @@ def frames_u8_compose(canvas: torch.Tensor, sources, pad: int = 0) -> torch.Tens
     return canvas
 
 
+def _yuv_planes(y: torch.Tensor, cb: Optional[torch.Tensor], cr: Optional[torch.Tensor], sub_x: bool, sub_y: bool, cosited: bool,
+                what: str) -> "_lib.YuvPlanes":
+    """``wan_yuv_planes`` of three strided uint8 views: luma ``[T, H, W]`` (unit column stride), chroma ``[T, Ch, Cw]`` with a column
+    stride of 1 (planar) or 2 (interleaved CbCr), both chroma planes with the same strides, or both ``None`` (mono)."""
+    _need(y, torch.uint8, what + ".y")
+    if y.dim() != 3:
+        raise ValueError(f"{what}.y: expected [T, H, W], got {tuple(y.shape)}")
+    T, H, W = (int(v) for v in y.shape)
+    p = _lib.YuvPlanes()
+    p.y, p.y_extent, p.y_frame, p.y_row = y.data_ptr(), _avail(y), y.stride(0), max(y.stride(1), W)
+    p.sub_x, p.sub_y, p.cosited, p.c_step = int(bool(sub_x)), int(bool(sub_y)), int(bool(cosited)), 1
+    if (cb is None) != (cr is None):
+        raise ValueError(f"{what}: pass both chroma planes or neither (mono)")
+    if cb is not None:
+        ch, cw = ((H + 1) // 2 if sub_y else H), ((W + 1) // 2 if sub_x else W)
+        for name, t in (("cb", cb), ("cr", cr)):
+            if not t.is_cuda:
+                raise RuntimeError(f"{what}.{name}: tensor is on {t.device}; the HIP path has no CPU fallback")
+            if t.dtype != torch.uint8 or t.device != y.device or tuple(t.shape) != (T, ch, cw):
+                raise ValueError(f"{what}.{name}: expected uint8 [{T}, {ch}, {cw}] on {y.device}, got {t.dtype} {tuple(t.shape)} on "
+                                 f"{t.device}")
+        step = cb.stride(2) if cw > 1 else 1
+        if step not in (1, 2) or (cw > 1 and cr.stride(2) != step) or cb.stride()[:2] != cr.stride()[:2]:
+            raise ValueError(f"{what}: chroma strides {cb.stride()} / {cr.stride()}: expected the same for both planes and a column "
+                             "stride of 1 (planar) or 2 (interleaved CbCr)")
+        p.cb, p.cr, p.cb_extent, p.cr_extent = cb.data_ptr(), cr.data_ptr(), _avail(cb), _avail(cr)
+        p.c_frame, p.c_row, p.c_step = cb.stride(0), max(cb.stride(1), (cw - 1) * step + 1), step
+    return p
+
+
+def _yuv_coef(k, yo: int) -> "_lib.YuvCoef":
+    k = [int(v) for v in k]
+    if len(k) != 9:
+        raise ValueError(f"expected the 9 coefficients of a 3 x 3 matrix, got {len(k)}")
+    return _lib.YuvCoef((ctypes.c_int * 9)(*k), int(yo))
+
+
+@_on_tensor_device
+def yuv_to_frames_u8(y: torch.Tensor, cb: Optional[torch.Tensor], cr: Optional[torch.Tensor], sub_x: bool, sub_y: bool, cosited: bool,
+                     inverse, yo: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """8-bit YCbCr planes -> uint8 [T,H,W,3] RGB frames (``wan_yuv_to_frames_u8``, include/wan_hip.h).  ``y`` [T,H,W], ``cb`` / ``cr``
+    [T,Ch,Cw] (or None: mono): strided views of any alignment.  ``inverse``: the 9 fixed-point coefficients, row-major; ``yo``: the luma
+    offset.  ``out``: a contiguous uint8 [T,H,W,3] device tensor that receives the frames (returned as given)."""
+    planes = _yuv_planes(y, cb, cr, sub_x, sub_y, cosited, "yuv_to_frames_u8")
+    T, H, W = (int(v) for v in y.shape)
+    if out is None:
+        out = torch.empty(T, H, W, 3, device=y.device, dtype=torch.uint8)
+    else:
+        _need(out, torch.uint8, "yuv_to_frames_u8.out")
+        if tuple(out.shape) != (T, H, W, 3) or not out.is_contiguous() or out.device != y.device:
+            raise ValueError(f"yuv_to_frames_u8.out: expected a contiguous [{T}, {H}, {W}, 3] on {y.device}, got {tuple(out.shape)} on "
+                             f"{out.device}")
+    coef = _yuv_coef(inverse, yo)
+    _lib.check(_lib.load().wan_yuv_to_frames_u8(ctypes.byref(planes), ctypes.byref(coef), _p(out), T, H, W, _stream()),
+               "wan_yuv_to_frames_u8")
+    return out
+
+
+@_on_tensor_device
+def frames_u8_to_yuv(frames: torch.Tensor, y: torch.Tensor, cb: torch.Tensor, cr: torch.Tensor, subsampled: bool, forward,
+                     yo: int) -> None:
+    """uint8 [T,H,W,3] RGB frames -> 8-bit YCbCr written into the strided views ``y`` [T,H,W], ``cb`` / ``cr`` [T,Ch,Cw]
+    (``wan_frames_u8_to_yuv``): 4:2:0 with ``subsampled``, else 4:4:4.  No byte outside the views' rows is written."""
+    _need(frames, torch.uint8, "frames_u8_to_yuv.frames")
+    if frames.dim() != 4 or frames.shape[-1] != 3:
+        raise ValueError(f"frames_u8_to_yuv.frames: expected [T, H, W, 3], got {tuple(frames.shape)}")
+    frames = frames.contiguous()
+    T, H, W, _ = (int(v) for v in frames.shape)
+    if tuple(y.shape) != (T, H, W) or y.device != frames.device or cb is None or cr is None:
+        raise ValueError(f"frames_u8_to_yuv.y: expected [{T}, {H}, {W}] on {frames.device} and both chroma planes, got "
+                         f"{tuple(y.shape)} on {y.device}")
+    planes = _yuv_planes(y, cb, cr, subsampled, subsampled, False, "frames_u8_to_yuv")
+    coef = _yuv_coef(forward, yo)
+    _lib.check(_lib.load().wan_frames_u8_to_yuv(_p(frames), ctypes.byref(planes), ctypes.byref(coef), T, H, W, _stream()),
+               "wan_frames_u8_to_yuv")
+
+
 @_on_tensor_device
 def lincomb(terms, out_dtype: torch.dtype) -> torch.Tensor:
     """sum_i c_i * x_i over <= 4 same-shape CUDA tensors in one pass (fp32 accumulate); `terms` is a list

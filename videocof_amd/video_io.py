@@ -33,7 +33,9 @@ from __future__ import annotations
 
 import functools
 import math
+import os
 from dataclasses import dataclass
+from fractions import Fraction
 from typing import Optional, Tuple, Union
 
 import numpy as np
@@ -43,7 +45,9 @@ from . import ops
 
 __all__ = ["frames_to_video", "video_to_frames", "load_video_frames", "reference_frames_to_video", "reference_video_to_frames",
            "fit_size", "fit_plan", "FitPlan", "fit_frames", "restore_frames", "reference_fit_frames",
-           "grid_layout", "grid_frames", "compare_frames", "reference_grid_frames", "reference_compare_frames"]
+           "grid_layout", "grid_frames", "compare_frames", "reference_grid_frames", "reference_compare_frames",
+           "select_frame_indices", "yuv_matrix", "chroma_shape", "yuv_to_frames", "frames_to_yuv", "reference_yuv_to_frames",
+           "reference_frames_to_yuv", "YuvClip", "read_y4m", "load_y4m_frames", "write_y4m"]
 
 COEF_BITS = 22                  # fixed-point bits of a filter coefficient: 8 + 22 bits of product and a sum of weights of 1 fit 32 bits
 MAX_TAPS = 24                   # WAN_RESAMPLE_MAX_TAPS of include/wan_hip.h: an 11x downscale
@@ -80,6 +84,20 @@ def reference_video_to_frames(video: torch.Tensor) -> torch.Tensor:
     return (x * 255).to(torch.uint8).contiguous()
 
 
+def select_frame_indices(total: int, source_frames: int, generator: Optional[torch.Generator] = None) -> list:
+    """The frames fast_infer.py:60-80 picks of a clip of ``total`` frames: ``stride = max(1, total // source_frames)``, the start
+    frame one draw of ``torch.randint`` (the global generator unless ``generator`` is given), ``start + i * stride`` while they
+    exist, the last one repeated up to ``source_frames``; ``[]`` for an empty clip.  The one rule ``load_video_frames`` and
+    ``load_y4m_frames`` share: the same seed picks the same frames."""
+    total, source_frames = int(total), int(source_frames)
+    stride = max(1, total // source_frames)
+    start = int(torch.randint(0, max(1, total - stride * source_frames), (1,), generator=generator)[0].item())
+    idx = [start + i * stride for i in range(source_frames) if start + i * stride < total]
+    if idx:
+        idx += [idx[-1]] * (source_frames - len(idx))
+    return idx
+
+
 def load_video_frames(video: Union[str, np.ndarray, torch.Tensor], source_frames: int,
                       generator: Optional[torch.Generator] = None) -> Tuple[torch.Tensor, int, int]:
     """fast_infer.py:43-92 without the float conversion: ``source_frames`` frames of a clip as uint8 ``[T, H, W, 3]``.
@@ -107,13 +125,9 @@ def load_video_frames(video: Union[str, np.ndarray, torch.Tensor], source_frames
     frames = torch.as_tensor(video)
     if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
         raise ValueError(f"load_video_frames: expected uint8 [N, H, W, 3] frames, got {frames.dtype} {tuple(frames.shape)}")
-    total = int(frames.shape[0])
-    stride = max(1, total // source_frames)
-    start = int(torch.randint(0, max(1, total - stride * source_frames), (1,), generator=generator)[0].item())
-    idx = [start + i * stride for i in range(source_frames) if start + i * stride < total]
+    idx = select_frame_indices(int(frames.shape[0]), source_frames, generator)
     if not idx:
         return torch.zeros(source_frames, 480, 832, 3, dtype=torch.uint8), 480, 832
-    idx += [idx[-1]] * (source_frames - len(idx))
     out = frames[torch.as_tensor(idx, device=frames.device)].contiguous()
     return out, int(out.shape[1]), int(out.shape[2])
 
@@ -455,3 +469,364 @@ def reference_compare_frames(source: torch.Tensor, edit: torch.Tensor) -> torch.
     a = _reference_writer_bytes(a[:, :, :T, :H, :W])                           # the writer is element-wise: bytes before the cat
     b = b[:, :, :T, :H, :W] if eu8 else _reference_writer_bytes(b[:, :, :T, :H, :W])
     return torch.cat([a, b], dim=4).permute(0, 2, 3, 4, 1).contiguous()
+
+
+# ---------------------------------------------------------------------------------------------- YCbCr planes in and out, .y4m files
+YUV_BITS = 16                   # fixed-point bits of a matrix coefficient
+YUV_MATRICES = {"bt601": (0.299, 0.114), "bt709": (0.2126, 0.0722)}           # (Kr, Kb)
+# chroma layout -> (subsampled horizontally, subsampled vertically, horizontally left co-sited); None: no chroma planes
+CHROMA_LAYOUTS = {"420jpeg": (True, True, False), "420mpeg2": (True, True, True), "422": (True, False, True),
+                  "444": (False, False, False), "mono": None}
+_Y4M_CHROMA_TAGS = {"420jpeg": "420jpeg", "420mpeg2": "420mpeg2", "420": "420jpeg", "422": "422", "444": "444", "mono": "mono"}
+_Y4M_MAGIC = b"YUV4MPEG2"
+_Y4M_FRAME = b"FRAME\n"
+
+
+def _yuv_range(full_range: bool) -> Tuple[int, int, int]:
+    """(luma span, chroma span, luma offset)."""
+    return (255, 255, 0) if full_range else (219, 224, 16)
+
+
+@functools.lru_cache(maxsize=None)
+def _yuv_tables(matrix: str, full_range: bool):
+    if matrix not in YUV_MATRICES:
+        raise ValueError(f"yuv_matrix: matrix {matrix!r}; expected one of {sorted(YUV_MATRICES)}")
+    kr, kb = YUV_MATRICES[matrix]
+    kg = 1.0 - kr - kb
+    ys, cs, _ = _yuv_range(bool(full_range))
+    one = float(1 << YUV_BITS)
+    m = np.array([[kr, kg, kb],
+                  [-kr / (2 * (1 - kb)), -kg / (2 * (1 - kb)), (1 - kb) / (2 * (1 - kb))],
+                  [(1 - kr) / (2 * (1 - kr)), -kg / (2 * (1 - kr)), -kb / (2 * (1 - kr))]], dtype=np.float64)
+    m *= np.array([[ys / 255.0], [cs / 255.0], [cs / 255.0]])
+    fwd = np.rint(m * one).astype(np.int64)
+    for row, target in enumerate((int(np.rint(ys / 255.0 * one)), 0, 0)):
+        fwd[row, int(np.argmax(np.abs(fwd[row])))] += target - int(fwd[row].sum())
+    ky, kc = 255.0 / ys, 255.0 / cs
+    inv = np.array([[ky, 0.0, 2 * (1 - kr) * kc],
+                    [ky, -2 * (1 - kb) * kb / kg * kc, -2 * (1 - kr) * kr / kg * kc],
+                    [ky, 2 * (1 - kb) * kc, 0.0]], dtype=np.float64)
+    inv = np.rint(inv * one).astype(np.int64)
+    fwd.setflags(write=False)
+    inv.setflags(write=False)
+    return fwd, inv
+
+
+def yuv_matrix(matrix: str = "bt601", full_range: bool = False) -> Tuple[np.ndarray, np.ndarray]:
+    """The two integer tables of the YCbCr definition (include/wan_hip.h) as int64 ``[3, 3]``:
+    ``forward`` (rows Y, Cb, Cr over R, G, B) and ``inverse`` (rows R, G, B over Y - yo, Cb - 128, Cr - 128), in 16-bit fixed point,
+    rounded from float64.  Each forward row is adjusted in its largest entry to sum to exactly ``rint(ys / 255 * 2**16)``, 0, 0, so a
+    grey pixel has Cb = Cr = 128 exactly.  ``matrix``: ``"bt601"`` | ``"bt709"``; limited range is Y in [16, 235], chroma in [16, 240]."""
+    return _yuv_tables(str(matrix), bool(full_range))
+
+
+def _chroma_layout(chroma: str, what: str):
+    if chroma not in _Y4M_CHROMA_TAGS:
+        raise ValueError(f"{what}: chroma layout {chroma!r}; expected one of {sorted(_Y4M_CHROMA_TAGS)}")
+    name = _Y4M_CHROMA_TAGS[chroma]
+    return name, CHROMA_LAYOUTS[name]
+
+
+def chroma_shape(height: int, width: int, chroma: str) -> Tuple[int, int]:
+    """Rows and columns of a chroma plane of a ``height`` x ``width`` frame: halves are rounded up; ``(0, 0)`` for mono."""
+    _, lay = _chroma_layout(chroma, "chroma_shape")
+    if lay is None:
+        return 0, 0
+    return ((height + 1) // 2 if lay[1] else height), ((width + 1) // 2 if lay[0] else width)
+
+
+def _up_taps(n_out: int, n_in: int, sub: bool, cosited: bool):
+    """Per output index the two source indices (clamped to the plane) and their weights in quarters."""
+    i = np.arange(n_out, dtype=np.int64)
+    if not sub:
+        return i, np.full(n_out, 4, np.int64), i, np.zeros(n_out, np.int64)
+    h, odd = i // 2, (i & 1).astype(bool)
+    if cosited:
+        i0, w0, i1, w1 = h, np.where(odd, 2, 4), np.where(odd, h + 1, h), np.where(odd, 2, 0)
+    else:
+        i0, w0, i1, w1 = np.where(odd, h, h - 1), np.where(odd, 3, 1), np.where(odd, h + 1, h), np.where(odd, 1, 3)
+    return np.clip(i0, 0, n_in - 1), w0.astype(np.int64), np.clip(i1, 0, n_in - 1), w1.astype(np.int64)
+
+
+def _as_plane(x, what: str) -> np.ndarray:
+    a = x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
+    if a.dtype != np.uint8 or a.ndim != 3:
+        raise ValueError(f"{what}: expected uint8 [T, rows, columns], got {a.dtype} {a.shape}")
+    return a
+
+
+def reference_yuv_to_frames(y, cb=None, cr=None, *, chroma: str = "420jpeg", matrix: str = "bt601",
+                            full_range: bool = False) -> torch.Tensor:
+    """The definition of the way in, in numpy int64 on the host: planes ``[T, H, W]`` / ``[T, Ch, Cw]`` -> uint8 ``[T, H, W, 3]``.
+    What ``yuv_to_frames`` equals byte for byte; never called by the product path."""
+    name, lay = _chroma_layout(chroma, "reference_yuv_to_frames")
+    yy = _as_plane(y, "reference_yuv_to_frames.y").astype(np.int64)
+    T, H, W = yy.shape
+    _, inv = yuv_matrix(matrix, full_range)
+    yo = _yuv_range(full_range)[2]
+    if lay is None:
+        u = v = np.full_like(yy, 128)
+    else:
+        ch, cw = chroma_shape(H, W, name)
+        iy0, wy0, iy1, wy1 = _up_taps(H, ch, lay[1], False)                   # the vertical axis is always centred
+        ix0, wx0, ix1, wx1 = _up_taps(W, cw, lay[0], lay[2])
+        planes = []
+        for nm, c in (("cb", cb), ("cr", cr)):
+            c = _as_plane(c, f"reference_yuv_to_frames.{nm}").astype(np.int64)
+            if c.shape != (T, ch, cw):
+                raise ValueError(f"reference_yuv_to_frames.{nm}: expected [{T}, {ch}, {cw}] for {name}, got {c.shape}")
+            r0, r1 = c[:, iy0] * wy0[None, :, None], c[:, iy1] * wy1[None, :, None]
+            s = (r0[:, :, ix0] + r1[:, :, ix0]) * wx0 + (r0[:, :, ix1] + r1[:, :, ix1]) * wx1
+            planes.append((s + 8) >> 4)
+        u, v = planes
+    src = np.stack([yy - yo, u - 128, v - 128], axis=-1)                       # [T, H, W, 3]
+    rgb = (src @ inv.T + (1 << (YUV_BITS - 1))) >> YUV_BITS
+    return torch.from_numpy(np.clip(rgb, 0, 255).astype(np.uint8))
+
+
+def reference_frames_to_yuv(frames_u8, *, chroma: str = "420jpeg", matrix: str = "bt601", full_range: bool = False):
+    """The definition of the way out, in numpy int64 on the host: uint8 ``[T, H, W, 3]`` -> ``(y, cb, cr)`` uint8 tensors
+    ``[T, H, W]`` / ``[T, Ch, Cw]``, ``chroma`` = ``"420jpeg"`` (centre siting) or ``"444"``.  Never called by the product path."""
+    name, lay = _chroma_layout(chroma, "reference_frames_to_yuv")
+    if name not in ("420jpeg", "444"):
+        raise ValueError(f"reference_frames_to_yuv: writes 420jpeg or 444, not {chroma!r}")
+    x = torch.as_tensor(frames_u8)
+    if x.dtype != torch.uint8 or x.dim() != 4 or x.shape[-1] != 3:
+        raise ValueError(f"reference_frames_to_yuv: expected uint8 [T, H, W, 3], got {x.dtype} {tuple(x.shape)}")
+    rgb = x.cpu().numpy().astype(np.int64)
+    fwd, _ = yuv_matrix(matrix, full_range)
+    off = np.array([_yuv_range(full_range)[2], 128, 128], dtype=np.int64)
+    ycc = np.clip((rgb @ fwd.T + (off << YUV_BITS) + (1 << (YUV_BITS - 1))) >> YUV_BITS, 0, 255)
+    out = [ycc[..., 0]]
+    for c in (ycc[..., 1], ycc[..., 2]):
+        if lay[0]:
+            c = np.pad(c, ((0, 0), (0, c.shape[1] & 1), (0, c.shape[2] & 1)), mode="edge")
+            c = (c[:, 0::2, 0::2] + c[:, 0::2, 1::2] + c[:, 1::2, 0::2] + c[:, 1::2, 1::2] + 2) >> 2
+        out.append(c)
+    return tuple(torch.from_numpy(np.ascontiguousarray(p.astype(np.uint8))) for p in out)
+
+
+def _default_matrix(height: int) -> str:
+    """The format carries no matrix tag: HD material is BT.709, everything smaller BT.601 (what players assume)."""
+    return "bt709" if int(height) >= 720 else "bt601"
+
+
+def yuv_to_frames(y: torch.Tensor, cb: Optional[torch.Tensor] = None, cr: Optional[torch.Tensor] = None, *, chroma: str = "420jpeg",
+                  matrix: str = "bt601", full_range: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """8-bit YCbCr planes on the device -> uint8 ``[T, H, W, 3]`` RGB frames on the device, one launch of ``wan_yuv_to_frames_u8``.
+    ``y``: uint8 ``[T, H, W]``; ``cb`` / ``cr``: uint8 ``[T, Ch, Cw]`` (``chroma_shape``), strided views of any alignment -- the planes
+    inside an uploaded ``.y4m`` file, padded decoder surfaces, or the two halves of an NV12 ``CbCr`` plane (``uv[..., 0]``,
+    ``uv[..., 1]``).  ``chroma``: a key of ``CHROMA_LAYOUTS`` (``"420"`` = ``"420jpeg"``); ``"mono"`` takes no chroma planes.  CPU
+    tensors raise, like every op.  ``out``: a contiguous uint8 ``[T, H, W, 3]`` device tensor to fill."""
+    name, lay = _chroma_layout(chroma, "yuv_to_frames")
+    if (lay is None) != (cb is None and cr is None):
+        raise ValueError(f"yuv_to_frames: chroma={chroma!r} with{'out' if cb is None else ''} chroma planes")
+    _, inv = yuv_matrix(matrix, full_range)
+    sub_x, sub_y, cosited = lay if lay is not None else (False, False, False)
+    return ops.yuv_to_frames_u8(y, cb, cr, sub_x, sub_y, cosited, inv.ravel().tolist(), _yuv_range(full_range)[2], out)
+
+
+def _plane_views(buf: torch.Tensor, height: int, width: int, chroma: str, prefix: int = 0):
+    """The ``[T, H, W]`` / ``[T, Ch, Cw]`` views of a uint8 ``[T, prefix + frame_bytes]`` buffer in the ``.y4m`` frame layout (Y, Cb, Cr
+    one after the other, rows packed); ``(y, None, None)`` for mono."""
+    T, pitch = int(buf.shape[0]), int(buf.stride(0)) if buf.shape[0] > 1 else int(buf.shape[1])
+    ch, cw = chroma_shape(height, width, chroma)
+    base = buf.storage_offset() + prefix
+
+    def view(off, rows, cols):
+        return torch.as_strided(buf, (T, rows, cols), (pitch, cols, 1), base + off)
+    y = view(0, height, width)
+    if ch == 0:
+        return y, None, None
+    return y, view(height * width, ch, cw), view(height * width + ch * cw, ch, cw)
+
+
+def y4m_frame_bytes(height: int, width: int, chroma: str) -> int:
+    ch, cw = chroma_shape(height, width, chroma)
+    return int(height) * int(width) + 2 * ch * cw
+
+
+def frames_to_yuv(frames_u8: torch.Tensor, *, chroma: str = "420", matrix: str = "bt601", full_range: bool = False,
+                  frame_prefix: bytes = b""):
+    """uint8 ``[T, H, W, 3]`` RGB frames on the device -> 8-bit YCbCr on the device, one launch of ``wan_frames_u8_to_yuv``.  Returns
+    ``(buffer, (y, cb, cr))``: one uint8 ``[T, frame_bytes]`` buffer in the ``.y4m`` frame layout and the three plane views into it.
+    ``chroma``: ``"420"`` / ``"420jpeg"`` (centre siting) or ``"444"``.  ``frame_prefix``: bytes put in front of every frame (the file's
+    ``FRAME`` line; the buffer is then ``[T, len(frame_prefix) + frame_bytes]``).  CPU tensors raise, like every op."""
+    name, lay = _chroma_layout(chroma, "frames_to_yuv")
+    if name not in ("420jpeg", "444"):
+        raise ValueError(f"frames_to_yuv: writes 420jpeg or 444, not {chroma!r}")
+    if not torch.is_tensor(frames_u8) or frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[-1] != 3:
+        raise ValueError(f"frames_to_yuv: expected uint8 [T, H, W, 3] frames, got {getattr(frames_u8, 'dtype', type(frames_u8))} "
+                         f"{tuple(getattr(frames_u8, 'shape', ()))}")
+    T, H, W, _ = (int(v) for v in frames_u8.shape)
+    fwd, _ = yuv_matrix(matrix, full_range)
+    npre = len(frame_prefix)
+    buf = torch.empty(T, npre + y4m_frame_bytes(H, W, name), device=frames_u8.device, dtype=torch.uint8)
+    if npre:
+        buf[:, :npre] = torch.frombuffer(bytearray(frame_prefix), dtype=torch.uint8).to(buf.device)
+    y, cb, cr = _plane_views(buf, H, W, name, npre)
+    ops.frames_u8_to_yuv(frames_u8, y, cb, cr, lay[0], fwd.ravel().tolist(), _yuv_range(full_range)[2])
+    return buf, (y, cb, cr)
+
+
+@dataclass(frozen=True)
+class YuvClip:
+    """A ``.y4m`` file as ``read_y4m`` maps it: nothing is copied, ``data`` is a read-only ``numpy.memmap`` of the whole file and
+    ``offsets[i]`` the byte at which frame ``i``'s planes start (``frame_bytes`` each: Y, Cb, Cr)."""
+    path: str
+    width: int
+    height: int
+    fps: Optional[Fraction]
+    chroma: str                     # a key of CHROMA_LAYOUTS
+    full_range: Optional[bool]      # XCOLORRANGE of the header; None when the file has no such tag
+    frames: int
+    frame_bytes: int
+    offsets: np.ndarray
+    data: np.ndarray
+    aspect: Optional[str] = None
+
+    def planes(self, index: int):
+        """``(y, cb, cr)`` of frame ``index`` as numpy views of the map (``cb`` = ``cr`` = None for mono)."""
+        if not 0 <= index < self.frames:
+            raise IndexError(f"frame {index} of {self.frames}")
+        o, n = int(self.offsets[index]), self.height * self.width
+        ch, cw = chroma_shape(self.height, self.width, self.chroma)
+        y = self.data[o:o + n].reshape(self.height, self.width)
+        if ch == 0:
+            return y, None, None
+        return y, self.data[o + n:o + n + ch * cw].reshape(ch, cw), self.data[o + n + ch * cw:o + n + 2 * ch * cw].reshape(ch, cw)
+
+
+def read_y4m(path) -> YuvClip:
+    """Map a YUV4MPEG2 file: the header's ``W H F I A C X`` tags and the place of every frame.  8-bit progressive ``C420jpeg``,
+    ``C420mpeg2``, ``C420`` (the format's default, read as 420jpeg), ``C422``, ``C444`` and ``Cmono`` are accepted, ``XCOLORRANGE=FULL``
+    is honoured; interlaced clips, more than 8 bits, ``C411`` and ``C420paldv`` raise ``ValueError`` with the tag in the message.
+    ``FRAME`` lines may carry parameters, so frames are found by parsing (at once when every marker is the bare ``FRAME``)."""
+    path = os.fspath(path)
+    size = os.path.getsize(path)
+    if size < len(_Y4M_MAGIC) + 1:
+        raise ValueError(f"read_y4m: {path}: not a YUV4MPEG2 file ({size} bytes)")
+    data = np.memmap(path, dtype=np.uint8, mode="r")
+    head = bytes(data[:min(size, 65536)])
+    if not head.startswith(_Y4M_MAGIC) or head[len(_Y4M_MAGIC):len(_Y4M_MAGIC) + 1] not in (b" ", b"\n"):
+        raise ValueError(f"read_y4m: {path}: bad magic {head[:10]!r}; expected {_Y4M_MAGIC!r}")
+    end = head.find(b"\n")
+    if end < 0:
+        raise ValueError(f"read_y4m: {path}: no end of the header line in the first {len(head)} bytes")
+    width = height = None
+    fps = aspect = full_range = None
+    chroma = "420jpeg"
+    for tag in head[len(_Y4M_MAGIC):end].decode("ascii", errors="replace").split():
+        key, val = tag[0], tag[1:]
+        if key in "WH":
+            if not val.isdigit() or int(val) < 1:
+                raise ValueError(f"read_y4m: {path}: bad size tag {tag!r}")
+            width, height = (int(val), height) if key == "W" else (width, int(val))
+        elif key == "F":
+            num, _, den = val.partition(":")
+            if not (num.isdigit() and den.isdigit()):
+                raise ValueError(f"read_y4m: {path}: bad frame rate tag {tag!r}")
+            fps = Fraction(int(num), int(den)) if int(den) else None
+        elif key == "I":
+            if val not in ("p", "?"):
+                raise ValueError(f"read_y4m: {path}: interlaced clip ({tag!r}); only progressive frames are read")
+        elif key == "A":
+            aspect = val
+        elif key == "C":
+            if val not in _Y4M_CHROMA_TAGS:
+                why = "more than 8 bits per sample" if "p1" in val or val.startswith("mono1") else "not supported"
+                raise ValueError(f"read_y4m: {path}: chroma tag {tag!r}: {why}; accepted: "
+                                 + ", ".join("C" + k for k in _Y4M_CHROMA_TAGS))
+            chroma = _Y4M_CHROMA_TAGS[val]
+        elif key == "X":
+            if val.upper().startswith("COLORRANGE="):
+                full_range = val.upper().split("=", 1)[1] == "FULL"
+    if width is None or height is None:
+        raise ValueError(f"read_y4m: {path}: the header has no W / H tag")
+    fb = y4m_frame_bytes(height, width, chroma)
+    start, body = end + 1, size - (end + 1)
+    step = len(_Y4M_FRAME) + fb
+    offsets = None
+    if body % step == 0:                                                       # fast path: every marker the bare FRAME line
+        n = body // step
+        marks = np.lib.stride_tricks.as_strided(data[start:], (n, len(_Y4M_FRAME)), (step, 1)) if n else np.zeros((0, 6), np.uint8)
+        if bool((marks == np.frombuffer(_Y4M_FRAME, np.uint8)).all()):
+            offsets = start + np.arange(n, dtype=np.int64) * step + len(_Y4M_FRAME)
+    if offsets is None:
+        found, pos = [], start
+        while pos < size:
+            line = bytes(data[pos:min(size, pos + 4096)])
+            nl = line.find(b"\n")
+            if not line.startswith(b"FRAME") or nl < 0 or line[5:6] not in (b" ", b"\n"):
+                raise ValueError(f"read_y4m: {path}: no FRAME line at byte {pos} (frame {len(found)})")
+            pos += nl + 1
+            if pos + fb > size:
+                raise ValueError(f"read_y4m: {path}: frame {len(found)} is truncated: {size - pos} of {fb} bytes")
+            found.append(pos)
+            pos += fb
+        offsets = np.asarray(found, dtype=np.int64)
+    return YuvClip(path, width, height, fps, chroma, full_range, int(len(offsets)), fb, offsets, data, aspect)
+
+
+def _default_device() -> torch.device:
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def load_y4m_frames(path, source_frames: int, generator: Optional[torch.Generator] = None, matrix: Optional[str] = None,
+                    full_range: Optional[bool] = None) -> Tuple[torch.Tensor, int, int]:
+    """``load_video_frames`` for a ``.y4m`` file, with nothing but this package: the same frame selection
+    (``select_frame_indices``: the same seed picks the same frames), then ONLY the selected frames go through one page-locked staging
+    buffer and one copy to the device -- 1.5 bytes per pixel for 4:2:0 -- where ``yuv_to_frames`` makes the RGB frames.  Returns
+    ``(uint8 [source_frames, H, W, 3] on the device, H, W)``; hand the frames to ``fit_frames`` / ``WanPipeline.__call__``.
+    ``matrix=None``: ``"bt709"`` when ``H >= 720``, else ``"bt601"`` (the format has no matrix tag).  ``full_range=None``: the header's
+    ``XCOLORRANGE``, else limited.  An empty clip gives black 480 x 832 frames, as ``load_video_frames`` does."""
+    if source_frames is None or int(source_frames) < 1:
+        raise ValueError("load_y4m_frames: pass source_frames >= 1")
+    source_frames = int(source_frames)
+    clip = read_y4m(path)
+    idx = select_frame_indices(clip.frames, source_frames, generator)
+    dev = _default_device()
+    if not idx:
+        return torch.zeros(source_frames, 480, 832, 3, dtype=torch.uint8, device=dev), 480, 832
+    distinct = [i for k, i in enumerate(idx) if k == 0 or i != idx[k - 1]]      # the padding repeats the last frame: staged once
+    stage = torch.empty(len(distinct), clip.frame_bytes, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+    host = stage.numpy()
+    for k, i in enumerate(distinct):
+        o = int(clip.offsets[i])
+        host[k] = clip.data[o:o + clip.frame_bytes]
+    buf = stage.to(dev, non_blocking=True)
+    y, cb, cr = _plane_views(buf, clip.height, clip.width, clip.chroma)
+    full = bool(clip.full_range) if full_range is None else bool(full_range)
+    frames = yuv_to_frames(y, cb, cr, chroma=clip.chroma, matrix=matrix or _default_matrix(clip.height), full_range=full)
+    if len(distinct) < len(idx):
+        frames = torch.cat([frames, frames[-1:].expand(len(idx) - len(distinct), -1, -1, -1)]).contiguous()
+    return frames, clip.height, clip.width
+
+
+def write_y4m(path, frames_u8, fps=16, *, chroma: str = "420", matrix: Optional[str] = None, full_range: bool = False) -> None:
+    """Write uint8 ``[T, H, W, 3]`` RGB frames (device or host) as a YUV4MPEG2 file any ``ffmpeg`` reads: converted on the device
+    (``frames_to_yuv``), one copy into page-locked memory, then the header and the frames in one write each.  ``fps``: an int, a
+    ``Fraction`` or ``(num, den)``.  ``chroma``: ``"420"`` (tagged ``C420jpeg``) or ``"444"``.  ``matrix=None``: ``"bt709"`` when
+    ``H >= 720``, else ``"bt601"``.  Full range is tagged ``XCOLORRANGE=FULL``."""
+    x = torch.from_numpy(frames_u8) if isinstance(frames_u8, np.ndarray) else frames_u8
+    if not torch.is_tensor(x) or x.dtype != torch.uint8 or x.dim() != 4 or x.shape[-1] != 3 or x.shape[0] < 1:
+        raise ValueError(f"write_y4m: expected uint8 [T, H, W, 3] frames, got {getattr(x, 'dtype', type(x))} "
+                         f"{tuple(getattr(x, 'shape', ()))}")
+    name, _ = _chroma_layout(chroma, "write_y4m")
+    rate = Fraction(*fps) if isinstance(fps, (tuple, list)) else Fraction(fps)
+    if rate <= 0:
+        raise ValueError(f"write_y4m: fps={fps}")
+    if not x.is_cuda:
+        x = x.to(_default_device())                                            # bytes over the host link, as they are
+    T, H, W, _ = (int(v) for v in x.shape)
+    buf, _ = frames_to_yuv(x, chroma=name, matrix=matrix or _default_matrix(H), full_range=full_range, frame_prefix=_Y4M_FRAME)
+    host = torch.empty(buf.shape, dtype=torch.uint8, pin_memory=torch.cuda.is_available())
+    host.copy_(buf, non_blocking=True)
+    if buf.is_cuda:
+        torch.cuda.current_stream(buf.device).synchronize()
+    header = f"YUV4MPEG2 W{W} H{H} F{rate.numerator}:{rate.denominator} Ip A1:1 C{name}"
+    if full_range:
+        header += " XCOLORRANGE=FULL"
+    with open(os.fspath(path), "wb") as f:
+        f.write(header.encode("ascii") + b"\n")
+        f.write(memoryview(host.numpy()).cast("B"))
