@@ -570,7 +570,13 @@ wan_status_t wan_solver_step(void* x0_out, void* prev_out, int dtype, const void
  *               ResidualBlock's `x + h` (:224) through `resid`; all 1x1 convs (:203, 238-239, 509-510).
  *     x    bf16 [T_in, H_in, W_in, Cin], Cin % 8 == 0
  *     w    bf16 [Cout, ldw] with k = ((kt*KH + kh)*KW + kw)*Cin + ci, zero padded to ldw >= roundup(K, 64)
- *     out  bf16 [T_out*H_out*W_out, ldo]  (time_interleave: [2*T_out*H_out*W_out, ldo], Cout/2 channels) */
+ *     out  bf16 [T_out*H_out*W_out, ldo]  (time_interleave: [2*T_out*H_out*W_out, ldo], Cout/2 channels)
+ *          ldo: row stride in elements, ldo >= the channels of a row (Cout, or Cout/2 with time_interleave) and ldo % 4 == 0
+ *          (8-byte stores).  Pixels are dense: row (to*H_out + ho)*W_out + wo.  Columns [channels, ldo) of a row are never
+ *          written.  ldo % 8 == 0 with a 16-byte aligned out / resid is what the LDS-patch kernel's 16-byte stores need; any
+ *          other ldo runs the same convolution on the gather kernel.
+ *     resid bf16 or NULL: the layout of out, the SAME row stride ldo (read at the offsets out is written at)
+ *     bias fp32 [Cout] or NULL, 16-byte aligned */
 typedef struct {
     int T_in, H_in, W_in, Cin;
     int T_out, H_out, W_out, Cout;

@@ -8,7 +8,7 @@ Unit roundoffs (round to nearest even, p significand bits -> u = 2^-p):  bf16 p 
 A truncating conversion has 2 u; the bounds allow u for the output rounding, so truncation is rejected.
 
 Plain module: no fixtures, no pytest hooks.  tests/test_kernel_bounds_host.py checks it on the CPU (honest emulations inside,
-mutants outside); tests/test_gpu_kernel_elementwise.py uses it on the kernels.
+mutants outside); tests/test_gpu_kernel_elementwise.py and tests/test_gpu_vae_elementwise.py use it on the kernels.
 """
 import math
 
@@ -254,6 +254,144 @@ def rmsnorm_rope_bound(x, w, eps, post_scale=1.0, rotate=None, head_dim=128):
         cr, sr = cos[:, None, :], sin[:, None, :]
         ref = torch.stack([re * cr - im * sr, re * sr + im * cr], dim=-1).reshape(rows, dim)
     return ref, U_BF16 * ref.abs() + (dim + 16) * U_F32 * mag
+
+
+# ------------------------------------------------------------------------------------------------ VAE convolutions
+def conv_cl_im2col(x, hist, kernel, stride, pad, out_thw, upsample2x=False):
+    """The A matrix of wan_conv_cl as the ABI defines it (include/wan_hip.h), by plain tensor indexing -- no kernel, no torch conv:
+    A[(to, ho, wo), ((kt KH + kh) KW + kw) Cin + ci] = in[to st - pt + kt, ho sh - ph + kh, wo sw - pw + kw, ci], fp64 [M, ntaps Cin].
+    x [T, H, W, Cin]; hist [nh, H, W, Cin] or None.  A negative frame index counts back from the END of hist (-1 = its last frame);
+    frames before the start of hist and every spatial out-of-range tap are zero.  upsample2x: the tap addresses a virtual 2H x 2W
+    plane (the range test is against 2H, 2W) and reads source pixel (hi >> 1, wi >> 1)."""
+    x = _d(x)
+    T, H, W, C = x.shape
+    nh = 0 if hist is None else hist.shape[0]
+    frames = torch.cat([_d(hist), x]) if nh else x                       # frame index f = ti + nh
+    (KT, KH, KW), (st, sh, sw), (pt, ph, pw) = kernel, stride, pad
+    To, Ho, Wo = out_thw
+    Hl, Wl = (2 * H, 2 * W) if upsample2x else (H, W)
+    to = torch.arange(To).view(To, 1, 1).expand(To, Ho, Wo).reshape(-1)
+    ho = torch.arange(Ho).view(1, Ho, 1).expand(To, Ho, Wo).reshape(-1)
+    wo = torch.arange(Wo).view(1, 1, Wo).expand(To, Ho, Wo).reshape(-1)
+    cols = []
+    for kt in range(KT):
+        for kh in range(KH):
+            for kw in range(KW):
+                f, hi, wi = to * st - pt + kt + nh, ho * sh - ph + kh, wo * sw - pw + kw
+                ok = (f >= 0) & (f < nh + T) & (hi >= 0) & (hi < Hl) & (wi >= 0) & (wi < Wl)
+                hs, ws = (hi >> 1, wi >> 1) if upsample2x else (hi, wi)
+                v = frames[f.clamp(0, nh + T - 1), hs.clamp(0, H - 1), ws.clamp(0, W - 1)]          # [M, C]
+                cols.append(v * ok[:, None].double())
+    return torch.cat(cols, dim=1)
+
+
+def conv_geometry(mode, T, H, W):
+    """(kernel, stride, pad, out_thw, upsample2x, time_interleave) of a wan_conv_cl mode as videocof_amd/wan_vae.py calls it."""
+    if mode == "causal":
+        return (3, 3, 3), (1, 1, 1), (2, 1, 1), (T, H, W), False, False
+    if mode == "1x1":
+        return (1, 1, 1), (1, 1, 1), (0, 0, 0), (T, H, W), False, False
+    if mode == "down2d":          # ZeroPad2d((0, 1, 0, 1)) + stride 2: the bottom / right tap past the plane reads zero
+        return (1, 3, 3), (1, 2, 2), (0, 0, 0), (T, (H - 2) // 2 + 1, (W - 2) // 2 + 1), False, False
+    if mode == "up2d":
+        return (1, 3, 3), (1, 1, 1), (0, 1, 1), (T, 2 * H, 2 * W), True, False
+    if mode == "time":            # upsample3d's time_conv, channel -> time interleave in the store
+        return (3, 1, 1), (1, 1, 1), (2, 0, 0), (T, H, W), False, True
+    if mode == "down3d":
+        return (3, 1, 1), (2, 1, 1), (1, 0, 0), ((T + 1 - 3) // 2 + 1, H, W), False, False
+    raise ValueError(mode)
+
+
+def conv_operands(cin, cout, kernel, T, H, W, nh, seed, resid_shape=None):
+    """Operands of one wan_conv_cl test case on the CPU: unit-variance bf16 x [T, H, W, cin] and hist [nh, H, W, cin] (None for
+    nh = 0), bf16 weights of variance 1 / K packed [cout, Kpad] in the ABI's K order (kt, kh, kw, ci) with zeros in [K, Kpad), an
+    O(1) fp32 bias that differs per column, and a unit-variance bf16 residual of `resid_shape` (or None).  `wt` is the same
+    weight as [cout, cin, KT, KH, KW] for torch's convolutions."""
+    g = torch.Generator().manual_seed(seed)
+    KT, KH, KW = kernel
+    K = KT * KH * KW * cin
+    Kpad = (K + 63) // 64 * 64
+    x = torch.randn(T, H, W, cin, generator=g).to(torch.bfloat16)
+    hist = torch.randn(nh, H, W, cin, generator=g).to(torch.bfloat16) if nh else None
+    wt = (torch.randn(cout, cin, KT, KH, KW, generator=g) / math.sqrt(K)).to(torch.bfloat16)
+    w = torch.zeros(cout, Kpad, dtype=torch.bfloat16)
+    w[:, :K] = wt.permute(0, 2, 3, 4, 1).reshape(cout, K)
+    bias = torch.randn(cout, generator=g) + 0.37 * torch.arange(cout) / cout
+    resid = torch.randn(*resid_shape, generator=g).to(torch.bfloat16) if resid_shape is not None else None
+    return dict(x=x, hist=hist, w=w, wt=wt, bias=bias, resid=resid, K=K, Kpad=Kpad)
+
+
+def time_interleave(conv, out_thw):
+    """[M, Cout] conv result -> the time-interleaved rows the kernel stores: out[2 t + half, h, w, c] = conv[t, h, w, half Ch + c]."""
+    To, Ho, Wo = out_thw
+    Ch = conv.shape[1] // 2
+    return conv.view(To, Ho * Wo, 2, Ch).permute(0, 2, 1, 3).reshape(2 * To * Ho * Wo, Ch)
+
+
+def conv_bound(A, w, bias, resid, K):
+    """wan_conv_cl, all three kernels (conv_cl_kernel, conv3_patch_kernel, conv3_head_kernel in videocof_amd/csrc/vae_conv.hip):
+    out = bf16(acc + bias (+ resid)), A from conv_cl_im2col, w [Cout, >= K] (only columns < K are used: K padding multiplies exact
+    zeros).  Returns (ref, bound), [M, Cout], NOT interleaved (time_interleave() rearranges both):
+        u16 |ref| + acc (+ 2 u32 (|acc + bias| + |resid|)),   acc = gemm_acc_term with K = ntaps Cin additions.
+    * every kernel accumulates exact bf16 products in fp32 (MFMA chains over taps and channel chunks in three different orders:
+      any order is covered), adds the fp32 bias, then the residual -- widened from bf16, exact -- as ONE more fp32 addition, and
+      rounds ONCE to bf16, to nearest even: v_cvt_pk_bf16_f32 in the gather and the patch kernel (the patch kernel stages the fp32
+      accumulators through LDS unrounded), a __bf16 cast of `acc + bias` in the head kernel.  Read in all three epilogues: none differs."""
+    A, wd = _d(A), _d(w)[:, :K]
+    ref = gemm_ref(A, wd, bias)
+    term = gemm_acc_term(A, wd, bias, K)
+    if resid is not None:
+        r = _d(resid)
+        term = term + 2.0 * U_F32 * (ref.abs() + r.abs())
+        ref = ref + r
+    return ref, U_BF16 * ref.abs() + term
+
+
+# ------------------------------------------------------------------------------------------------ VAE row kernels
+SILU_SLOPE = 1.1           # max |d/da a sigmoid(a)| = 1.0998 (at a = 2.3994), rounded up
+
+
+def rmsnorm_silu_bound(x, gamma, silu):
+    """wan_rmsnorm_silu_cl: a = x sqrt(C) / max(||x||, 1e-12) gamma per row (F.normalize's eps on the NORM), out = bf16(a) or
+    bf16(a / (1 + e^-a)).  x bf16-valued [rows, C].  Returns (ref, bound):
+        plain:  u16 |a| + (C + 8) u32 |a|
+        SiLU:   u16 |g(a)| + 1.1 (C + 8) u32 |a| + u32 |g(a)| (6 + 2 |a|) + 2^-120
+    * the sum of C squares in fp32, per lane 8 fused terms then a shuffle tree: non-negative terms, any order, relative error
+      <= C u32, halved by the square root; sqrtf and the division are the correctly rounded expansions (gfx950 code of
+      rmsnorm_silu_cl_kernel: v_sqrt_f32 + fma refinement; v_div_scale / v_rcp_f32 / v_div_fmas / v_div_fixup), sqrtf(C) one more
+      rounding, two multiplies: (C / 2 + 5) u32, granted as (C + 8) u32 like rmsnorm_rope_bound's rstd;
+    * SiLU: the error of `a` through g, |g'| <= 1.0998; the evaluation, from the same code: e = v_exp_f32(-a * log2e) -- the
+      constant's and the multiply's rounding are 2 u32 of the argument, through 2^t a relative 2 u32 |a| of e, + 1 ulp = 2 u32 of
+      v_exp_f32 (CDNA ISA guide) -- 1 + e one rounding, the division correctly rounded (u32); e's share is damped by e / (1 + e) <= 1:
+      relative (2 |a| + 2 + 1 + 1) u32, the constant 4 taken as 6; the absolute floor covers e flushed below the normal range;
+    * one rounding to bf16, to nearest even (v_cvt_pk_bf16_f32)."""
+    x = _d(x)
+    C = x.shape[-1]
+    nrm = x.norm(dim=-1, keepdim=True).clamp_min(1e-12)
+    a = x * math.sqrt(C) / nrm * _d(gamma)
+    da = (C + 8) * U_F32 * a.abs()
+    if not silu:
+        return a, U_BF16 * a.abs() + da
+    g = a / (1.0 + torch.exp(-a))
+    return g, U_BF16 * g.abs() + SILU_SLOPE * da + U_F32 * g.abs() * (6.0 + 2.0 * a.abs()) + 2.0 ** -120
+
+
+def softmax_rows_bound(s, n, scale):
+    """wan_softmax_rows: p_i = e_i / sum_j e_j, e_i = __expf((s_i - mx) scale), i < n; s fp32 [rows, >= n].  Returns (ref, bound) [rows, n]:
+        u16 p_i + p_i u32 (4 x_i + 2 + sum_j p_j (4 x_j + 2) + n + 4) + 2^-120,    x_i = (mx - s_i) scale >= 0
+    * the exponent's argument: the subtraction, the multiply by scale, the multiply by the rounded log2(e) = 4 u32 relative on the
+      argument, seen through e^x as a relative 4 u32 x_i of e_i (as the attention bound's s_i sees its score error), + v_exp_f32's 1 ulp
+      = 2 u32; the max itself is exact;
+    * the row sum: n fp32 additions of non-negative terms in any order (256 strided partial sums, a shuffle tree, four wave sums):
+      n u32 relative, + the e_j's own errors weighted by their share p_j;
+    * 1 / sum (gfx950 code of softmax_rows_kernel: the correctly rounded division expansion; 2 u32 granted so that a bare v_rcp_f32
+      would pass as well), the multiply (u32), + 1 spare;  * one rounding to bf16, to nearest even;  * the floor: e_i flushed to zero."""
+    sd = _d(s)[:, :n]
+    x = (sd.max(dim=-1, keepdim=True).values - sd) * scale
+    p = torch.softmax(-x, dim=-1)
+    rel = 4.0 * x + 2.0
+    row = (p * rel).sum(dim=-1, keepdim=True)
+    return p, U_BF16 * p + p * U_F32 * (rel + row + n + 4.0) + 2.0 ** -120
 
 
 # ------------------------------------------------------------------------------------------------ comparison

@@ -983,7 +983,7 @@ extern "C" wan_status_t wan_conv_cl(const void* x, const void* hist, int hist_fr
                 "wan_conv_cl: kernel (%d,%d,%d) (extents must be 1 or 3)", p->KT, p->KH, p->KW);
     WAN_REQUIRE(p->T_in > 0 && p->H_in > 0 && p->W_in > 0 && p->T_out > 0 && p->H_out > 0 && p->W_out > 0, WAN_ERR_INVALID,
                 "wan_conv_cl: bad extents");
-    WAN_REQUIRE(p->st > 0 && p->sh > 0 && p->sw > 0 && p->pt >= 0 && p->ph >= 0 && p->pw >= 0 && p->pt < 4096 && p->ph < 4096,
+    WAN_REQUIRE(p->st > 0 && p->sh > 0 && p->sw > 0 && p->pt >= 0 && p->ph >= 0 && p->pw >= 0 && p->pt < 4096 && p->ph < 4096 && p->pw < 4096,
                 WAN_ERR_INVALID, "wan_conv_cl: bad stride/pad");
     WAN_REQUIRE(p->H_out * p->sh + 8 < 28000 && p->W_out * p->sw + 8 < 28000, WAN_ERR_UNSUPPORTED,
                 "wan_conv_cl: spatial extent too large for the packed coordinates");

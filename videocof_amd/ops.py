@@ -829,9 +829,13 @@ def _unpatchify_rep(tokens, grid, patch, cout, out_dtype, zero_frames, out, rep,
 @_on_tensor_device
 def conv_cl(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], cout: int, kernel, stride=(1, 1, 1),
             pad=(0, 0, 0), out_thw=None, hist: Optional[torch.Tensor] = None, upsample2x: bool = False,
-            time_interleave: bool = False, resid: Optional[torch.Tensor] = None) -> torch.Tensor:
+            time_interleave: bool = False, resid: Optional[torch.Tensor] = None,
+            out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """x bf16 [T,H,W,Cin]; w bf16 [Cout, Kpad] packed (kt,kh,kw,ci); hist bf16 [n<=2,H,W,Cin] or None.
-    Returns bf16 [T_out,H_out,W_out,Cout] (time_interleave: [2*T_out,H_out,W_out,Cout/2])."""
+    Returns bf16 [T_out,H_out,W_out,Cout] (time_interleave: [2*T_out,H_out,W_out,Cout/2]).
+    out: optional preallocated result of that shape whose pixels are dense rows of a [pixels, ldo] buffer -- channel stride 1, row
+    stride ldo >= channels, ldo % 4 == 0 (the ABI's rule); columns [channels, ldo) are not written.  resid then has out's strides
+    (the kernels read it at out's offsets)."""
     _need(x, torch.bfloat16, "conv_cl.x")
     _need(w, torch.bfloat16, "conv_cl.w")
     if x.dim() != 4 or not x.is_contiguous():
@@ -847,15 +851,27 @@ def conv_cl(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], cout
     if bias is not None:
         _need(bias, torch.float32, "conv_cl.bias")
     ch = cout // 2 if time_interleave else cout
-    out = torch.empty((2 * To if time_interleave else To), Ho, Wo, ch, device=x.device, dtype=torch.bfloat16)
+    shape = ((2 * To if time_interleave else To), Ho, Wo, ch)
+    ldo = ch
+    if out is None:
+        out = torch.empty(shape, device=x.device, dtype=torch.bfloat16)
+    else:
+        _need(out, torch.bfloat16, "conv_cl.out")
+        if tuple(out.shape) != shape:
+            raise ValueError(f"conv_cl.out must have shape {shape}, got {tuple(out.shape)}")
+        ldo = out.stride(2)
+        want = (Ho * Wo * ldo, Wo * ldo, ldo, 1)
+        if ldo < ch or ldo % 4 != 0 or any(n > 1 and a != b for n, a, b in zip(shape[:2], out.stride(), want)) or out.stride(3) != 1:
+            raise ValueError(f"conv_cl.out: pixels must be dense rows of a [pixels, ldo] buffer with ldo >= {ch} and ldo % 4 == 0, "
+                             f"got strides {tuple(out.stride())}")
     if resid is not None:
         _need(resid, torch.bfloat16, "conv_cl.resid")
-        if resid.shape != out.shape or not resid.is_contiguous():
-            raise ValueError("conv_cl.resid must match the output")
+        if resid.shape != out.shape or any(n > 1 and a != b for n, a, b in zip(out.shape, resid.stride(), out.stride())):
+            raise ValueError("conv_cl.resid must match the output (shape and strides)")
     p = _lib.ConvParams(T, H, W, Cin, To, Ho, Wo, cout, kernel[0], kernel[1], kernel[2], stride[0], stride[1], stride[2],
                         pad[0], pad[1], pad[2], int(upsample2x), int(time_interleave))
     lib = _lib.load()
-    _lib.check(lib.wan_conv_cl(_p(x), _p(hist), nh, _p(w), w.stride(0), _p(bias), _p(resid), _p(out), ch,
+    _lib.check(lib.wan_conv_cl(_p(x), _p(hist), nh, _p(w), w.stride(0), _p(bias), _p(resid), _p(out), ldo,
                                ctypes.byref(p), _stream()), "wan_conv_cl")
     return out
 
