@@ -740,6 +740,47 @@ wan_status_t wan_yuv_to_frames_u8(const wan_yuv_planes* planes, const wan_yuv_co
 wan_status_t wan_frames_u8_to_yuv(const void* frames_u8, const wan_yuv_planes* planes, const wan_yuv_coef* forward, int T, int H, int W,
                                   void* stream);
 
+/* Keep what the edit left alone: where did the edit change the frames the pipeline saw (a feathered uint8 mask), and the edit put back
+ * over the ORIGINAL clip under that mask, the original's bytes kept wherever nothing was edited or the fit cropped the frame away.
+ * replaces: nothing in the reference, which returns the whole clip as the VAE and the DiT left it; callers composite on the host in float.
+ * Integer arithmetic only (videocof_amd/video_io.py: reference_change_mask / reference_composite_frames restate this in numpy int64 and
+ * equal the kernels byte for byte).
+ *
+ * wan_change_mask: source, edit uint8 [B, T, H, W, 3] (any base alignment) -> alpha uint8 [B, T, H, W].  Per sample and frame:
+ *     d     = max_c |edit - source|
+ *     s     = (2 S + n) / (2 n),   S = sum of d over the (2 smooth + 1)^2 window with indices clamped to the frame, n = (2 smooth + 1)^2
+ *     b     = s > threshold
+ *     g     = max of b over the (2 grow + 1)^2 window and the frames t - grow_t .. t + grow_t; positions outside the frame or outside the
+ *             sample's T frames are ignored (the maximum never crosses from one sample of a batch into the next)
+ *     alpha = (2 * 255 * C + m) / (2 m),   C = count of g over the (2 feather + 1)^2 window with clamped indices, m = (2 feather + 1)^2
+ * all divisions floor.  feather <= grow is what makes b = 1 imply alpha = 255: every pixel of the feather window around it has g = 1.
+ * 0 <= threshold <= 254, smooth <= WAN_MASK_MAX_SMOOTH, grow <= WAN_MASK_MAX_GROW, grow_t <= WAN_MASK_MAX_GROW_T, feather <= grow, none
+ * negative -> else WAN_ERR_INVALID before anything is enqueued.  B * T <= 65535 -> else WAN_ERR_UNSUPPORTED.  `workspace`: device memory of
+ * wan_change_mask_workspace_bytes(B, T, H, W) bytes (the b and g planes).  Enqueues three kernels on `stream`; never synchronises. */
+#define WAN_MASK_MAX_SMOOTH 7
+#define WAN_MASK_MAX_GROW 32
+#define WAN_MASK_MAX_GROW_T 4
+int64_t wan_change_mask_workspace_bytes(int B, int T, int H, int W);
+wan_status_t wan_change_mask(const void* source_u8, const void* edit_u8, void* alpha_u8, int B, int T, int H, int W, int threshold,
+                             int smooth, int grow, int grow_t, int feather, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* wan_frames_u8_resample's two passes on one-channel planes (the alpha of wan_change_mask brought to the size of the source window):
+ * uint8 [N, H, W] -> uint8 [N, Ho, Wo], horizontal pass first into `tmp_u8` (N * H * Wo bytes, rounded to bytes), then the vertical pass;
+ * the same tables, the same arithmetic, the same limits on the tap counts.  Windows are clamped to the plane: a malformed table gives
+ * wrong bytes, never an access outside the tensors.  N <= 65535 and Ho <= 65535 -> else WAN_ERR_UNSUPPORTED.  Enqueues two kernels on
+ * `stream`; never synchronises. */
+wan_status_t wan_plane_u8_resample(const void* src_u8, void* tmp_u8, void* dst_u8, int N, int H, int W, int Ho, int Wo, const void* xtab,
+                                   int kx, const void* ytab, int ky, void* stream);
+
+/* original uint8 [N, Ho, Wo, 3], edit uint8 [N, wh, ww, 3], alpha uint8 [N, wh, ww] -> out uint8 [N, Ho, Wo, 3] (N = B * T frames):
+ *     inside the window rows [wy, wy + wh), columns [wx, wx + ww), per byte   out = (a * e + (255 - a) * o + 127) / 255   (floor, exact)
+ *     outside it                                                              out = o
+ * With the window the whole frame this is the same-size composite.  Any sizes and alignment: a thread moves 16 pixels, each of its runs
+ * as dwordx4 where its address allows.  A window that leaves the frame is WAN_ERR_INVALID; N <= 65535 -> else WAN_ERR_UNSUPPORTED.
+ * Enqueues one kernel on `stream`; never synchronises. */
+wan_status_t wan_frames_u8_composite(const void* original_u8, const void* edit_u8, const void* alpha_u8, void* out_u8, int N, int Ho,
+                                     int Wo, int wy, int wx, int wh, int ww, void* stream);
+
 /* ===========================================================================
  * the umT5 text encoder (videox_fun/models/wan_text_encoder.py:256-304), the step
  * before the denoising path.  Its Linear layers are wan_gemm_bf16; the rest:

@@ -235,6 +235,13 @@ SIGNATURES = {
     "wan_video_range_flag": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_void_p]),
     "wan_yuv_to_frames_u8": (c_int, [POINTER(YuvPlanes), POINTER(YuvCoef), c_void_p, c_int, c_int, c_int, c_void_p]),
     "wan_frames_u8_to_yuv": (c_int, [c_void_p, POINTER(YuvPlanes), POINTER(YuvCoef), c_int, c_int, c_int, c_void_p]),
+    "wan_change_mask_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
+    "wan_change_mask": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                c_int64, c_void_p]),
+    "wan_plane_u8_resample": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int,
+                                      c_void_p]),
+    "wan_frames_u8_composite": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                        c_void_p]),
 }
 
 _lib = None

@@ -16,6 +16,7 @@
 // Stores never touch a byte outside the run, so padding between rows, planes and frames keeps its contents.
 #include <algorithm>
 
+#include "byte_runs.hpp"
 #include "common.hpp"
 
 namespace {
@@ -34,101 +35,11 @@ struct yuv_args {
     int k[9], yo;                           // the 3 x 3 matrix in 16-bit fixed point, the luma offset
 };
 
-__device__ __forceinline__ unsigned int byte_of(const unsigned int* w, int i) { return (w[i >> 2] >> ((i & 3) * 8)) & 0xffu; }
 // clamp(s >> 16, 0, 255) of a 16-bit fixed-point sum, written as a clamp of the sum and a logical shift.  NOT min(max(s >> 16, 0), 255):
 // two of those packed side by side become one v_ashr_pk_u8_i32, whose result hipcc then ORs into the word as a whole dword although
 // the instruction writes 16 bits and leaves the upper half of its destination as it was (seen on gfx950 with ROCm 7: the byte
 // two places up came out ORed with the old register contents).  tests/test_gpu_yuv.py compares every byte.
 __device__ __forceinline__ unsigned int fixed_to_byte(int s) { return (unsigned int)min(max(s, 0), 0xffffff) >> 16; }
-
-// 4 * NW bytes from base + off (any alignment) into w.  Nothing outside [base, base + extent) is read.
-template <int NW>
-__device__ __forceinline__ void load_bytes(const uint8_t* base, int64_t extent, int64_t off, unsigned int (&w)[NW]) {
-    const uintptr_t addr = reinterpret_cast<uintptr_t>(base) + (uintptr_t)off;
-    const int a = (int)(addr & 3);
-    if (off - a >= 0 && off - a + 4 * (NW + (a ? 1 : 0)) <= extent) {
-        if constexpr (NW % 4 == 0) {
-            if ((addr & 15) == 0) {
-                const u32x4* p = reinterpret_cast<const u32x4*>(base + off);
-#pragma unroll
-                for (int q = 0; q < NW / 4; ++q) {
-                    const u32x4 v = p[q];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) w[4 * q + i] = v[i];
-                }
-                return;
-            }
-        }
-        if constexpr (NW == 2) {
-            if ((addr & 7) == 0) {
-                const u32x2 v = *reinterpret_cast<const u32x2*>(base + off);
-                w[0] = v[0]; w[1] = v[1];
-                return;
-            }
-        }
-        const unsigned int* p = reinterpret_cast<const unsigned int*>(base + (off - a));      // 4-byte aligned
-        if (a == 0) {
-#pragma unroll
-            for (int i = 0; i < NW; ++i) w[i] = p[i];
-        } else {
-            unsigned int v[NW + 1];
-#pragma unroll
-            for (int i = 0; i <= NW; ++i) v[i] = p[i];
-#pragma unroll
-            for (int i = 0; i < NW; ++i) w[i] = __builtin_amdgcn_alignbyte(v[i + 1], v[i], (unsigned int)a);
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < NW; ++i) w[i] = 0u;
-#pragma unroll
-        for (int b = 0; b < 4 * NW; ++b) {
-            const int64_t o = off + b;
-            if (o >= 0 && o < extent) w[b >> 2] |= (unsigned int)base[o] << ((b & 3) * 8);
-        }
-    }
-}
-
-// the first n <= 4 * NW bytes of w to dst (any alignment); no other byte is written
-template <int NW>
-__device__ __forceinline__ void store_span(uint8_t* dst, const unsigned int (&w)[NW], int n) {
-    if (n == 4 * NW) {
-        const uintptr_t addr = reinterpret_cast<uintptr_t>(dst);
-        if constexpr (NW % 4 == 0) {
-            if ((addr & 15) == 0) {
-#pragma unroll
-                for (int q = 0; q < NW / 4; ++q)
-                    reinterpret_cast<u32x4*>(dst)[q] = u32x4{w[4 * q], w[4 * q + 1], w[4 * q + 2], w[4 * q + 3]};
-                return;
-            }
-        }
-        if constexpr (NW == 2) {
-            if ((addr & 7) == 0) {
-                *reinterpret_cast<u32x2*>(dst) = u32x2{w[0], w[1]};
-                return;
-            }
-        }
-        const int a = (int)(addr & 3);
-        if (a == 0) {
-#pragma unroll
-            for (int i = 0; i < NW; ++i) reinterpret_cast<unsigned int*>(dst)[i] = w[i];
-            return;
-        }
-        const int head = 4 - a;                                    // bytes up to the next aligned dword
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-            if (j < head) dst[j] = (uint8_t)(w[0] >> (j * 8));
-        unsigned int* p = reinterpret_cast<unsigned int*>(dst + head);
-#pragma unroll
-        for (int i = 0; i + 1 < NW; ++i) p[i] = __builtin_amdgcn_alignbyte(w[i + 1], w[i], (unsigned int)head);
-#pragma unroll
-        for (int j = 0; j < 3; ++j)
-            if (j < a) dst[4 * NW - a + j] = (uint8_t)(w[NW - 1] >> ((head + j) * 8));
-    } else {
-#pragma unroll
-        for (int b = 0; b < 4 * NW; ++b)
-            if (b < n) dst[b] = (uint8_t)(w[b >> 2] >> ((b & 3) * 8));
-    }
-}
 
 // ---- in: one chroma row of a thread's 16 pixels
 // SUBX: NS = 10 samples [8 k - 1, 8 k + 8]: the 8 of the thread's own pairs as one run, the two neighbours as single bytes at indices

@@ -1160,6 +1160,73 @@ def frames_u8_to_yuv(frames: torch.Tensor, y: torch.Tensor, cb: torch.Tensor, cr
 
 
 @_on_tensor_device
+def change_mask(source: torch.Tensor, edit: torch.Tensor, threshold: int, smooth: int, grow: int, grow_t: int,
+                feather: int) -> torch.Tensor:
+    """uint8 [B,T,H,W,3] source and edit frames -> the feathered uint8 [B,T,H,W] mask of where they differ (``wan_change_mask``,
+    include/wan_hip.h: three launches, integer arithmetic).  The b / g planes live in a workspace allocated here."""
+    _need(source, torch.uint8, "change_mask.source")
+    _need(edit, torch.uint8, "change_mask.edit")
+    if source.dim() != 5 or source.shape[-1] != 3 or edit.shape != source.shape or edit.device != source.device:
+        raise ValueError(f"change_mask: expected two [B, T, H, W, 3] clips of one shape on one device, got {tuple(source.shape)} on "
+                         f"{source.device} and {tuple(edit.shape)} on {edit.device}")
+    source, edit = source.contiguous(), edit.contiguous()
+    B, T, H, W, _ = (int(v) for v in source.shape)
+    lib = _lib.load()
+    nws = int(lib.wan_change_mask_workspace_bytes(B, T, H, W))
+    ws = torch.empty(max(nws, 1), device=source.device, dtype=torch.uint8)
+    alpha = torch.empty(B, T, H, W, device=source.device, dtype=torch.uint8)
+    _lib.check(lib.wan_change_mask(_p(source), _p(edit), _p(alpha), B, T, H, W, int(threshold), int(smooth), int(grow), int(grow_t),
+                                   int(feather), _p(ws), nws, _stream()), "wan_change_mask")
+    return alpha
+
+
+@_on_tensor_device
+def plane_u8_resample(planes: torch.Tensor, out_height: int, out_width: int, xtab: torch.Tensor, kx: int, ytab: torch.Tensor,
+                      ky: int) -> torch.Tensor:
+    """uint8 [N,H,W] -> uint8 [N,out_height,out_width]: ``frames_u8_resample``'s two passes and tables on one-channel planes
+    (``wan_plane_u8_resample``); the horizontal pass' bytes go through a temporary allocated here."""
+    _need(planes, torch.uint8, "plane_u8_resample.planes")
+    if planes.dim() != 3:
+        raise ValueError(f"plane_u8_resample.planes: expected [N, H, W], got {tuple(planes.shape)}")
+    planes = planes.contiguous()
+    N, H, W = (int(v) for v in planes.shape)
+    lib = _lib.load()
+    for name, tab, n_out, k in (("xtab", xtab, out_width, kx), ("ytab", ytab, out_height, ky)):
+        _need(tab, torch.int32, f"plane_u8_resample.{name}")
+        if tab.device != planes.device or not tab.is_contiguous() or \
+                tab.numel() * 4 != lib.wan_frames_resample_table_bytes(int(n_out), int(k)):
+            raise ValueError(f"plane_u8_resample.{name}: expected {n_out} * (2 + {k}) contiguous int32 on {planes.device}, got "
+                             f"{tuple(tab.shape)} on {tab.device}")
+    tmp = torch.empty(N, H, int(out_width), device=planes.device, dtype=torch.uint8)
+    out = torch.empty(N, int(out_height), int(out_width), device=planes.device, dtype=torch.uint8)
+    _lib.check(lib.wan_plane_u8_resample(_p(planes), _p(tmp), _p(out), N, H, W, int(out_height), int(out_width), _p(xtab), int(kx),
+                                         _p(ytab), int(ky), _stream()), "wan_plane_u8_resample")
+    return out
+
+
+@_on_tensor_device
+def frames_u8_composite(original: torch.Tensor, edit: torch.Tensor, alpha: torch.Tensor, window: Tuple[int, int, int, int]) -> torch.Tensor:
+    """``(a * e + (255 - a) * o + 127) // 255`` per byte inside ``window`` = (y, x, h, w) of the original's frames, the original's
+    bytes outside it (``wan_frames_u8_composite``).  original uint8 [N,Ho,Wo,3], edit uint8 [N,h,w,3], alpha uint8 [N,h,w]."""
+    for name, t in (("original", original), ("edit", edit), ("alpha", alpha)):
+        _need(t, torch.uint8, f"frames_u8_composite.{name}")
+    wy, wx, wh, ww = (int(v) for v in window)
+    if original.dim() != 4 or original.shape[-1] != 3:
+        raise ValueError(f"frames_u8_composite.original: expected [N, H, W, 3], got {tuple(original.shape)}")
+    N, Ho, Wo, _ = (int(v) for v in original.shape)
+    if tuple(edit.shape) != (N, wh, ww, 3) or tuple(alpha.shape) != (N, wh, ww) or edit.device != original.device or \
+            alpha.device != original.device:
+        raise ValueError(f"frames_u8_composite: window {(wy, wx, wh, ww)} of {N} frames needs edit [{N}, {wh}, {ww}, 3] and alpha "
+                         f"[{N}, {wh}, {ww}] on {original.device}, got {tuple(edit.shape)} on {edit.device} and {tuple(alpha.shape)} on "
+                         f"{alpha.device}")
+    original, edit, alpha = original.contiguous(), edit.contiguous(), alpha.contiguous()
+    out = torch.empty_like(original)
+    _lib.check(_lib.load().wan_frames_u8_composite(_p(original), _p(edit), _p(alpha), _p(out), N, Ho, Wo, wy, wx, wh, ww, _stream()),
+               "wan_frames_u8_composite")
+    return out
+
+
+@_on_tensor_device
 def lincomb(terms, out_dtype: torch.dtype) -> torch.Tensor:
     """sum_i c_i * x_i over <= 4 same-shape CUDA tensors in one pass (fp32 accumulate); `terms` is a list
     of (coefficient, tensor).  Inputs are brought to `out_dtype` (fp32 or bf16) if they differ."""

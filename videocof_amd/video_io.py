@@ -21,6 +21,12 @@ centre crop, videox_fun/data/dataset_image_video.py:464-477), ``fit_frames`` run
 launch each).  The filter is the 8-bit antialiased triangle in integers; ``reference_fit_frames`` restates it
 in numpy and is what the kernel equals bit for bit.
 
+Keep what the edit left alone: an edit is local, but the whole clip comes back through the VAE and the DiT (and, after the fit,
+upscaled).  ``change_mask`` finds where the edit differs from the frames the pipeline saw, ``composite_frames`` puts the edit back
+into the ORIGINAL frames under that mask, ``keep_unedited`` does both (``wan_change_mask``, ``wan_plane_u8_resample``,
+``wan_frames_u8_composite``).  Nothing in the reference does this; the definition is ours, in integers:
+``reference_change_mask`` / ``reference_composite_frames`` state it in numpy and are what the kernels equal byte for byte.
+
 What the writer makes of more than one sample, and the compare clip: ``grid_frames`` is ``save_videos_grid`` up to the encoder
 (videox_fun/utils/utils.py:59-68: the ``make_grid(nrow=6)`` mosaic with its 2-pixel zero border, ``rescale``, the byte conversion)
 and ``compare_frames`` is ``save_side_by_side`` (fast_infer.py:183-206: ``_normalize_to_01`` of source and edit, the crop to the
@@ -45,6 +51,7 @@ from . import ops
 
 __all__ = ["frames_to_video", "video_to_frames", "load_video_frames", "reference_frames_to_video", "reference_video_to_frames",
            "fit_size", "fit_plan", "FitPlan", "fit_frames", "restore_frames", "reference_fit_frames",
+           "change_mask", "composite_frames", "keep_unedited", "reference_change_mask", "reference_composite_frames",
            "grid_layout", "grid_frames", "compare_frames", "reference_grid_frames", "reference_compare_frames",
            "select_frame_indices", "yuv_matrix", "chroma_shape", "yuv_to_frames", "frames_to_yuv", "reference_yuv_to_frames",
            "reference_frames_to_yuv", "YuvClip", "read_y4m", "load_y4m_frames", "write_y4m"]
@@ -322,6 +329,165 @@ def restore_frames(frames_u8, height: int, width: int, out: Optional[torch.Tenso
     out.copy_(res.contiguous(), non_blocking=True)
     torch.cuda.current_stream(res.device).synchronize()
     return out
+
+
+# ---------------------------------------------------------------------------------------------- keep what the edit left alone
+MASK_MAX_SMOOTH, MASK_MAX_GROW, MASK_MAX_GROW_T = 7, 32, 4          # WAN_MASK_MAX_* of include/wan_hip.h
+
+
+def _mask_args(what: str, threshold, smooth, grow, grow_t, feather) -> Tuple[int, int, int, int, int]:
+    v = tuple(int(x) for x in (threshold, smooth, grow, grow_t, feather))
+    threshold, smooth, grow, grow_t, feather = v
+    if not (0 <= threshold <= 254 and 0 <= smooth <= MASK_MAX_SMOOTH and 0 <= grow <= MASK_MAX_GROW and
+            0 <= grow_t <= MASK_MAX_GROW_T and 0 <= feather <= grow):
+        raise ValueError(f"{what}: threshold={threshold} (0..254) smooth={smooth} (0..{MASK_MAX_SMOOTH}) grow={grow} "
+                         f"(0..{MASK_MAX_GROW}) grow_t={grow_t} (0..{MASK_MAX_GROW_T}) feather={feather} (0..grow)")
+    return v
+
+
+def _box_sum(x: np.ndarray, radius: int, axes, clamp: bool) -> np.ndarray:
+    """The exact sum of an int64 array over the ``2 * radius + 1`` window along each of ``axes``, one pass per axis.  Positions outside
+    the array repeat its border (``clamp``: clamped indices) or count nothing."""
+    for ax in axes:
+        ax %= x.ndim
+        pad = [(0, 0)] * x.ndim
+        pad[ax] = (radius + 1, radius)
+        c = np.cumsum(np.pad(x, pad, mode="edge" if clamp else "constant"), axis=ax)      # the extra leading element is subtracted out
+        n = x.shape[ax]
+        lead = (slice(None),) * ax
+        x = c[lead + (slice(2 * radius + 1, 2 * radius + 1 + n),)] - c[lead + (slice(0, n),)]
+    return x
+
+
+def _mask_clips(source_u8, edit_u8, what: str):
+    s, e = (torch.as_tensor(v).cpu() for v in (source_u8, edit_u8))
+    for x in (s, e):
+        if x.dtype != torch.uint8 or x.dim() not in (4, 5) or x.shape[-1] != 3:
+            raise ValueError(f"{what}: expected uint8 [T, H, W, 3] or [B, T, H, W, 3] frames, got {x.dtype} {tuple(x.shape)}")
+    if s.shape != e.shape:
+        raise ValueError(f"{what}: source {tuple(s.shape)} and edit {tuple(e.shape)} differ in shape")
+    return s.numpy().astype(np.int64), e.numpy().astype(np.int64)
+
+
+def reference_change_mask(source_u8, edit_u8, *, threshold: int = 16, smooth: int = 2, grow: int = 12, grow_t: int = 1,
+                          feather: int = 8) -> torch.Tensor:
+    """The definition of ``change_mask`` in numpy int64 on the host: uint8 ``[T, H, W, 3]`` or
+    ``[B, T, H, W, 3]`` source and edit -> uint8 ``[T, H, W]`` / ``[B, T, H, W]``.  What the kernels equal byte for byte; never called
+    by the product path."""
+    threshold, smooth, grow, grow_t, feather = _mask_args("reference_change_mask", threshold, smooth, grow, grow_t, feather)
+    s, e = _mask_clips(source_u8, edit_u8, "reference_change_mask")
+    d = np.abs(e - s).max(-1)                                                   # 1. the largest channel difference
+    n = (2 * smooth + 1) ** 2
+    sm = (2 * _box_sum(d, smooth, (-1, -2), True) + n) // (2 * n)               # 2. its rounded mean over the window, indices clamped
+    b = (sm > threshold).astype(np.int64)                                       # 3.
+    g = (_box_sum(b, grow, (-1, -2), False) > 0).astype(np.int64)               # 4. the maximum over the window: nothing outside the
+    g = (_box_sum(g, grow_t, (-3,), False) > 0).astype(np.int64)                #    frame, nothing outside the sample's T frames
+    m = (2 * feather + 1) ** 2
+    alpha = (2 * 255 * _box_sum(g, feather, (-1, -2), True) + m) // (2 * m)     # 5. the rounded mean of 255 g, indices clamped
+    return torch.from_numpy(np.ascontiguousarray(alpha.astype(np.uint8)))
+
+
+def _check_composite(what: str, o_shape, e_shape, a_shape, plan: Optional[FitPlan]):
+    """-> the window (y, x, h, w) of the original that the edit lands in."""
+    o_shape, e_shape, a_shape = tuple(o_shape), tuple(e_shape), tuple(a_shape)
+    if len(o_shape) != len(e_shape) or o_shape[:-3] != e_shape[:-3] or a_shape != e_shape[:-1]:
+        raise ValueError(f"{what}: original {o_shape}, edit {e_shape}, alpha {a_shape}: expected the same leading sizes and an alpha of "
+                         "the edit's [.., T, H, W]")
+    if plan is None:
+        if o_shape != e_shape:
+            raise ValueError(f"{what}: original {o_shape} and edit {e_shape} differ in size; pass the FitPlan of fit_frames")
+        return (0, 0, e_shape[-3], e_shape[-2])
+    if o_shape[-3:-1] != (plan.height, plan.width) or e_shape[-3:-1] != (plan.out_height, plan.out_width):
+        raise ValueError(f"{what}: the plan fits {plan.height} x {plan.width} to {plan.out_height} x {plan.out_width}; got an original "
+                         f"of {o_shape[-3:-1]} and an edit of {e_shape[-3:-1]}")
+    return tuple(int(v) for v in plan.source_window)
+
+
+def reference_composite_frames(original_u8, edit_u8, alpha, plan: Optional[FitPlan] = None) -> torch.Tensor:
+    """The definition of ``composite_frames`` in numpy int64 on the host: per byte ``(a * e + (255 - a) * o + 127) // 255``.  With
+    ``plan`` (the ``FitPlan`` of ``fit_frames``) the edit and ``alpha`` first go to the size of ``plan.source_window`` -- the edit as
+    ``restore_frames`` defines it, ``alpha`` through the same two passes and tables, horizontal first, the intermediate rounded to a
+    byte -- and the bytes outside the window are the original's.  Never called by the product path."""
+    o, e, a = (torch.as_tensor(v).cpu() for v in (original_u8, edit_u8, alpha))
+    for x in (o, e, a):
+        if x.dtype != torch.uint8:
+            raise ValueError(f"reference_composite_frames: expected uint8 tensors, got {x.dtype}")
+    if e.dim() not in (4, 5) or e.shape[-1] != 3 or o.shape[-1] != 3:
+        raise ValueError(f"reference_composite_frames: expected [T, H, W, 3] or [B, T, H, W, 3] frames, got {tuple(o.shape)} and "
+                         f"{tuple(e.shape)}")
+    y, x, wh, ww = _check_composite("reference_composite_frames", o.shape, e.shape, a.shape, plan)
+    H, W = int(e.shape[-3]), int(e.shape[-2])
+    a = a.numpy().astype(np.int64)
+    if (wh, ww) != (H, W):
+        e = reference_fit_frames(e, wh, ww, _resize_plan(H, W, wh, ww))
+        a = _resample_axis(a, -1, resample_axis_table(W, ww))
+        a = _resample_axis(a, -2, resample_axis_table(H, wh))
+    out = o.numpy().astype(np.int64)
+    win = out[..., y:y + wh, x:x + ww, :]
+    a = a[..., None]
+    out[..., y:y + wh, x:x + ww, :] = (a * e.numpy().astype(np.int64) + (255 - a) * win + 127) // 255
+    return torch.from_numpy(np.ascontiguousarray(out.astype(np.uint8)))
+
+
+def change_mask(source_u8, edit_u8, *, threshold: int = 16, smooth: int = 2, grow: int = 12, grow_t: int = 1,
+                feather: int = 8) -> torch.Tensor:
+    """Where did the edit change the frames the pipeline saw: a feathered uint8 mask on the device, three launches of integer
+    arithmetic (``wan_change_mask``; the definition is ``reference_change_mask``).
+
+    ``source_u8``: the fitted frames handed to ``WanPipeline.__call__``; ``edit_u8``: ``out.edit_videos``; both uint8 ``[T, H, W, 3]``
+    or ``[B, T, H, W, 3]`` of one shape, host or device.  Returns ``alpha`` uint8 ``[T, H, W]`` / ``[B, T, H, W]`` on the device: 255
+    where the largest channel difference, averaged over ``(2 * smooth + 1)^2`` pixels, exceeds ``threshold``; that region grown by
+    ``grow`` pixels and ``grow_t`` frames (within a sample) and its edge softened over ``2 * feather + 1`` pixels; 0 elsewhere.
+    Limits: ``0 <= threshold <= 254``, ``smooth <= 7``, ``grow <= 32``, ``grow_t <= 4``, ``feather <= grow`` (so that a changed
+    pixel always has alpha 255), else ``ValueError``.
+
+    The defaults are guesses.  The right ``threshold`` sits just above what a VAE round trip alone does to an untouched pixel, which
+    depends on the checkpoint and has not been measured: no real weights have been run yet.  Measure it on yours
+    (``reference_change_mask`` steps 1-2 on a clip edited with an empty instruction) before relying on them."""
+    args = _mask_args("change_mask", threshold, smooth, grow, grow_t, feather)
+    s, e = _as_clip(source_u8, "change_mask.source"), _as_clip(edit_u8, "change_mask.edit")
+    if s.shape != e.shape:
+        raise ValueError(f"change_mask: source {tuple(s.shape)} and edit {tuple(e.shape)} differ in shape")
+    alpha = ops.change_mask(s if s.dim() == 5 else s.unsqueeze(0), e if e.dim() == 5 else e.unsqueeze(0), *args)
+    return alpha if s.dim() == 5 else alpha[0]
+
+
+def composite_frames(original_u8, edit_u8, alpha, plan: Optional[FitPlan] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The edit over the original under ``alpha``, on the device in bytes: ``(a * e + (255 - a) * o + 127) // 255``
+    (``wan_frames_u8_composite``; the definition is ``reference_composite_frames``).
+
+    Without ``plan`` the three share ``T, H, W``.  With ``plan`` -- the ``FitPlan`` ``fit_frames`` returned -- ``original_u8`` is the
+    clip BEFORE the fit (``[.., plan.height, plan.width, 3]``): inside ``plan.source_window`` the edit is ``restore_frames``' and
+    ``alpha`` goes through the same resample as one-channel planes (``wan_plane_u8_resample``); outside it, where the fit cropped the
+    frame away, the result is the original's bytes.  ``original_u8`` / ``edit_u8``: uint8 ``[T, H, W, 3]`` or ``[B, T, H, W, 3]``,
+    ``alpha``: uint8 ``[T, H, W]`` / ``[B, T, H, W]`` at the edit's size; host or device.  ``out``: a page-locked uint8 host tensor of
+    the original's shape, filled by one copy and returned, as in ``restore_frames``; without it the device frames are returned."""
+    o, e = _as_clip(original_u8, "composite_frames.original"), _as_clip(edit_u8, "composite_frames.edit")
+    a = torch.from_numpy(alpha) if isinstance(alpha, np.ndarray) else alpha
+    if not torch.is_tensor(a) or a.dtype != torch.uint8:
+        raise ValueError(f"composite_frames.alpha: expected a uint8 tensor, got {getattr(a, 'dtype', type(a))}")
+    if not a.is_cuda:
+        a = a.to(e.device)
+    y, x, wh, ww = _check_composite("composite_frames", o.shape, e.shape, a.shape, plan)
+    H, W = int(e.shape[-3]), int(e.shape[-2])
+    e, a = e.reshape(-1, H, W, 3), a.reshape(-1, H, W)
+    if (wh, ww) != (H, W):
+        rp, dev = _resize_plan(H, W, wh, ww), str(e.device)
+        xtab, kx = _device_table(rp.width, rp.new_width, 0, ww, dev)
+        ytab, ky = _device_table(rp.height, rp.new_height, 0, wh, dev)
+        e = ops.frames_u8_resample(e.unsqueeze(0), wh, ww, xtab, kx, ytab, ky)[0]
+        a = ops.plane_u8_resample(a, wh, ww, xtab, kx, ytab, ky)
+    res = ops.frames_u8_composite(o.reshape(-1, int(o.shape[-3]), int(o.shape[-2]), 3), e, a, (y, x, wh, ww)).view(o.shape)
+    return _to_host(res, out, "composite_frames")
+
+
+def keep_unedited(original_u8, source_u8, edit_u8, plan: Optional[FitPlan] = None, out: Optional[torch.Tensor] = None,
+                  **mask_args) -> torch.Tensor:
+    """``change_mask(source_u8, edit_u8, **mask_args)`` then ``composite_frames(original_u8, edit_u8, alpha, plan, out)``: the edit
+    put back into the original clip, the original's bytes wherever the edit changed nothing.  ``original_u8``: the clip as loaded;
+    ``source_u8``, ``plan``: what ``fit_frames`` made of it (``plan=None`` when the clip ran at its own size: then ``source_u8`` is
+    ``original_u8``); ``edit_u8``: ``out.edit_videos``."""
+    return composite_frames(original_u8, edit_u8, change_mask(source_u8, edit_u8, **mask_args), plan, out)
 
 
 # ---------------------------------------------------------------------------------------------- the writer's grid, the compare clip
