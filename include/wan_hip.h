@@ -781,6 +781,31 @@ wan_status_t wan_plane_u8_resample(const void* src_u8, void* tmp_u8, void* dst_u
 wan_status_t wan_frames_u8_composite(const void* original_u8, const void* edit_u8, const void* alpha_u8, void* out_u8, int N, int Ho,
                                      int Wo, int wy, int wx, int wh, int ww, void* stream);
 
+/* Clip statistics: how far is clip b from clip a, per frame, in exact integers, split by a mask.  a, b uint8 [N, H, W, 3] (N = B * T
+ * frames, any base alignment), alpha uint8 [N, H, W] or NULL -> stats int64 [N][2][WAN_CLIP_STATS_WORDS].  A pixel's region r is 1 where
+ * alpha != 0, else 0 (NULL: every pixel in region 0).  Per frame and region:
+ *     [0, 256)    the byte histogram: the number of bytes (all three channels) of the region's pixels with |a - b| == v
+ *     [256, 512)  the smoothed histogram: the number of the region's pixels with s == v, s of wan_change_mask above (d = max_c |a - b|,
+ *                 s = (2 S + n) / (2 n) over the (2 smooth + 1)^2 window with clamped indices), 0 <= smooth <= WAN_MASK_MAX_SMOOTH
+ *     [512]       the SSIM sum: the sum of q over the region's windows, signed
+ *     [513]       the number of those windows
+ * SSIM is the 8-bit form of x264 / ffmpeg's `ssim` filter on each colour plane by itself: h4 = H >> 2, w4 = W >> 2 (rows and columns from
+ * 4 h4 and 4 w4 on are not read for it); per 4 x 4 block the sums of a, of b, of a^2 + b^2 and of a b; a window is 2 x 2 neighbouring
+ * blocks (8 x 8 pixels at stride 4, (h4 - 1)(w4 - 1) of them per plane) with the blocks' sums added to s1, s2, ss, s12;
+ *     vars = 64 ss - s1^2 - s2^2,  covar = 64 s12 - s1 s2
+ *     q = rint((double)(2 s1 s2 + 416) * (double)(2 covar + 235963) / ((double)(s1^2 + s2^2 + 416) * (double)(vars + 235963)) * 2^20)
+ * two rounded products, one IEEE division, round half to even; identical windows give exactly 2^20.  A window is in region 1 if any of
+ * its 64 alpha bytes is non-zero.  h4 < 2 or w4 < 2: no windows, both words 0.
+ * Every word of stats is overwritten, nothing is accumulated into; counts are exact and independent of the order of execution (integer
+ * adds only; videocof_amd/video_io.py: reference_clip_stats restates this in numpy and equals the kernels word for word).  A null a, b or
+ * stats, a size below 1, smooth out of range or a workspace below wan_clip_stats_workspace_bytes(N, H, W) bytes -> WAN_ERR_INVALID;
+ * N > 65535 or a frame of 2 GiB or more -> WAN_ERR_UNSUPPORTED; both before anything is enqueued.  Enqueues four kernels on `stream`;
+ * never synchronises. */
+#define WAN_CLIP_STATS_WORDS 514          /* 256 + 256 + 2 */
+int64_t wan_clip_stats_workspace_bytes(int N, int H, int W);
+wan_status_t wan_clip_stats(const void* a_u8, const void* b_u8, const void* alpha_u8, void* stats_i64, int N, int H, int W, int smooth,
+                            void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ===========================================================================
  * the umT5 text encoder (videox_fun/models/wan_text_encoder.py:256-304), the step
  * before the denoising path.  Its Linear layers are wan_gemm_bf16; the rest:

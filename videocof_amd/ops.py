@@ -1226,6 +1226,41 @@ def frames_u8_composite(original: torch.Tensor, edit: torch.Tensor, alpha: torch
     return out
 
 
+CLIP_STATS_WORDS = 514             # WAN_CLIP_STATS_WORDS of include/wan_hip.h
+
+
+@_on_tensor_device
+def clip_stats(a: torch.Tensor, b: torch.Tensor, alpha: Optional[torch.Tensor], smooth: int,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Two uint8 [B,T,H,W,3] clips and an optional uint8 [B,T,H,W] mask -> int64 [B,T,2,514] on the device: per frame and region
+    (alpha == 0, alpha != 0) the histogram of byte differences, the histogram of the smoothed pixel difference and the SSIM sum and
+    window count (``wan_clip_stats``, include/wan_hip.h: four launches, exact integers).  ``out``: a contiguous int64 tensor of that
+    shape, every word of which is overwritten.  The workgroups' partial counts live in a workspace allocated here."""
+    _need(a, torch.uint8, "clip_stats.a")
+    _need(b, torch.uint8, "clip_stats.b")
+    if a.dim() != 5 or a.shape[-1] != 3 or b.shape != a.shape or b.device != a.device:
+        raise ValueError(f"clip_stats: expected two [B, T, H, W, 3] clips of one shape on one device, got {tuple(a.shape)} on "
+                         f"{a.device} and {tuple(b.shape)} on {b.device}")
+    a, b = a.contiguous(), b.contiguous()
+    B, T, H, W, _ = (int(v) for v in a.shape)
+    if alpha is not None:
+        _need(alpha, torch.uint8, "clip_stats.alpha")
+        if tuple(alpha.shape) != (B, T, H, W) or alpha.device != a.device:
+            raise ValueError(f"clip_stats.alpha: expected [{B}, {T}, {H}, {W}] on {a.device}, got {tuple(alpha.shape)} on {alpha.device}")
+        alpha = alpha.contiguous()
+    if out is None:
+        out = torch.empty(B, T, 2, CLIP_STATS_WORDS, device=a.device, dtype=torch.int64)
+    elif out.dtype != torch.int64 or tuple(out.shape) != (B, T, 2, CLIP_STATS_WORDS) or out.device != a.device or not out.is_contiguous():
+        raise ValueError(f"clip_stats.out: expected contiguous int64 [{B}, {T}, 2, {CLIP_STATS_WORDS}] on {a.device}, got {out.dtype} "
+                         f"{tuple(out.shape)} on {out.device}")
+    lib = _lib.load()
+    nws = int(lib.wan_clip_stats_workspace_bytes(B * T, H, W))
+    ws = torch.empty(max(nws, 1), device=a.device, dtype=torch.uint8)
+    _lib.check(lib.wan_clip_stats(_p(a), _p(b), _p(alpha), _p(out), B * T, H, W, int(smooth), _p(ws), nws, _stream()),
+               "wan_clip_stats")
+    return out
+
+
 @_on_tensor_device
 def lincomb(terms, out_dtype: torch.dtype) -> torch.Tensor:
     """sum_i c_i * x_i over <= 4 same-shape CUDA tensors in one pass (fp32 accumulate); `terms` is a list

@@ -27,6 +27,12 @@ into the ORIGINAL frames under that mask, ``keep_unedited`` does both (``wan_cha
 ``wan_frames_u8_composite``).  Nothing in the reference does this; the definition is ours, in integers:
 ``reference_change_mask`` / ``reference_composite_frames`` state it in numpy and are what the kernels equal byte for byte.
 
+How far is clip A from clip B: ``clip_stats`` is one pass of integer kernels over two uint8 clips (``wan_clip_stats``) that yields, per
+frame and split by a mask, the histogram of byte differences, the histogram of ``change_mask``'s smoothed difference and the sums of
+x264's 8-bit SSIM; ``ClipStats`` turns those into PSNR, MAE, quantiles, SSIM and the ``threshold`` for ``change_mask`` on the host.
+``vae_roundtrip_frames`` gives the clip a checkpoint's VAE alone makes of a clip, the floor under every such number.
+``reference_clip_stats`` states the definition in numpy and is what the kernels equal word for word.
+
 What the writer makes of more than one sample, and the compare clip: ``grid_frames`` is ``save_videos_grid`` up to the encoder
 (videox_fun/utils/utils.py:59-68: the ``make_grid(nrow=6)`` mosaic with its 2-pixel zero border, ``rescale``, the byte conversion)
 and ``compare_frames`` is ``save_side_by_side`` (fast_infer.py:183-206: ``_normalize_to_01`` of source and edit, the crop to the
@@ -52,6 +58,7 @@ from . import ops
 __all__ = ["frames_to_video", "video_to_frames", "load_video_frames", "reference_frames_to_video", "reference_video_to_frames",
            "fit_size", "fit_plan", "FitPlan", "fit_frames", "restore_frames", "reference_fit_frames",
            "change_mask", "composite_frames", "keep_unedited", "reference_change_mask", "reference_composite_frames",
+           "ClipStats", "clip_stats", "reference_clip_stats", "vae_roundtrip_frames",
            "grid_layout", "grid_frames", "compare_frames", "reference_grid_frames", "reference_compare_frames",
            "select_frame_indices", "yuv_matrix", "chroma_shape", "yuv_to_frames", "frames_to_yuv", "reference_yuv_to_frames",
            "reference_frames_to_yuv", "YuvClip", "read_y4m", "load_y4m_frames", "write_y4m"]
@@ -442,8 +449,9 @@ def change_mask(source_u8, edit_u8, *, threshold: int = 16, smooth: int = 2, gro
     pixel always has alpha 255), else ``ValueError``.
 
     The defaults are guesses.  The right ``threshold`` sits just above what a VAE round trip alone does to an untouched pixel, which
-    depends on the checkpoint and has not been measured: no real weights have been run yet.  Measure it on yours
-    (``reference_change_mask`` steps 1-2 on a clip edited with an empty instruction) before relying on them."""
+    depends on the checkpoint and has not been measured: no real weights have been run yet.  Measure it on yours before relying on
+    them: ``clip_stats(frames, vae_roundtrip_frames(vae, frames), smooth=smooth).threshold_for()`` is that ``threshold``, computed on
+    the device."""
     args = _mask_args("change_mask", threshold, smooth, grow, grow_t, feather)
     s, e = _as_clip(source_u8, "change_mask.source"), _as_clip(edit_u8, "change_mask.edit")
     if s.shape != e.shape:
@@ -488,6 +496,175 @@ def keep_unedited(original_u8, source_u8, edit_u8, plan: Optional[FitPlan] = Non
     ``source_u8``, ``plan``: what ``fit_frames`` made of it (``plan=None`` when the clip ran at its own size: then ``source_u8`` is
     ``original_u8``); ``edit_u8``: ``out.edit_videos``."""
     return composite_frames(original_u8, edit_u8, change_mask(source_u8, edit_u8, **mask_args), plan, out)
+
+
+# ---------------------------------------------------------------------------------------------- how far is clip A from clip B
+SSIM_C1, SSIM_C2, SSIM_ONE = 416, 235963, 1 << 20       # x264 / ffmpeg's 8-bit constants for 64 pixels; the fixed point of a window's q
+
+
+@dataclass(frozen=True)
+class ClipStats:
+    """Exact integer statistics of two uint8 clips per frame, split into region 0 (alpha == 0, or no alpha) and region 1 (alpha != 0):
+    what ``wan_clip_stats`` computes (include/wan_hip.h).  ``..`` is nothing for ``[T, H, W, 3]`` clips and ``B``
+    for a batch.  The methods are host arithmetic on these arrays and nothing else, so ``clip_stats`` and ``reference_clip_stats``
+    share them.  ``region``: 0, 1 or None (both pooled); ``per_frame=False`` pools the frame axis (a batch keeps its samples)."""
+    diff_hist: np.ndarray            # int64 [.., T, 2, 256]: bytes (all channels) with |a - b| == v
+    smooth_hist: np.ndarray          # int64 [.., T, 2, 256]: pixels whose smoothed difference (change_mask's steps 1-2) == v
+    ssim_sum: np.ndarray             # int64 [.., T, 2]: the sum of the windows' q, 2^20 = identical
+    ssim_windows: np.ndarray         # int64 [.., T, 2]: the number of windows, all three colour planes
+    smooth: int
+
+    @staticmethod
+    def _pool(x: np.ndarray, region, per_frame: bool, axis: int) -> np.ndarray:
+        """``x``: [.., T, 2, (256)] with the region at ``axis`` -> [.., T, (256)] or, pooled over the frames, [.., (256)]."""
+        if region is not None and int(region) not in (0, 1):
+            raise ValueError(f"ClipStats: region={region!r} (0, 1 or None)")
+        x = x.sum(axis) if region is None else np.take(x, int(region), axis=axis)
+        return x if per_frame else x.sum(axis)               # the frame axis has moved to where the region was
+
+    def _diff(self, region, per_frame):
+        h = self._pool(self.diff_hist, region, per_frame, -2)
+        return h, h.sum(-1), np.arange(256, dtype=np.int64)
+
+    def psnr(self, region=None, per_frame: bool = True) -> np.ndarray:
+        """``10 log10(255^2 count / SSE)`` in float64 over the bytes; ``inf`` where the SSE is 0, ``nan`` where there are no bytes."""
+        h, count, v = self._diff(region, per_frame)
+        sse = (h * v * v).sum(-1)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            out = 10.0 * np.log10(65025.0 * count / sse)
+        return np.where(count == 0, np.nan, np.where(sse == 0, np.inf, out))
+
+    def mae(self, region=None, per_frame: bool = True) -> np.ndarray:
+        """The mean absolute byte difference in float64; ``nan`` where there are no bytes."""
+        h, count, v = self._diff(region, per_frame)
+        with np.errstate(invalid="ignore"):
+            return np.where(count == 0, np.nan, (h * v).sum(-1) / count)
+
+    def max_diff(self, region=None, per_frame: bool = True) -> np.ndarray:
+        """The largest absolute byte difference (int64; 0 where there are no bytes)."""
+        h, _, v = self._diff(region, per_frame)
+        return np.where(h > 0, v, 0).max(-1)
+
+    def quantile(self, q: float, region=None, per_frame: bool = True) -> np.ndarray:
+        """The smallest ``v`` such that ``ceil(q count)`` bytes differ by at most ``v`` (int64; 0 where there are no bytes)."""
+        if not 0.0 <= float(q) <= 1.0:
+            raise ValueError(f"ClipStats.quantile: q={q!r} (0..1)")
+        h, count, _ = self._diff(region, per_frame)
+        need = np.ceil(float(q) * count).astype(np.int64)
+        return (np.cumsum(h, -1) >= need[..., None]).argmax(-1).astype(np.int64)
+
+    def ssim(self, region=None, per_frame: bool = True) -> np.ndarray:
+        """The mean SSIM of the region's 8 x 8 windows over the three colour planes, ``ssim_sum / (2^20 ssim_windows)`` in float64;
+        ``nan`` without windows."""
+        s, n = (self._pool(x, region, per_frame, -1) for x in (self.ssim_sum, self.ssim_windows))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(n == 0, np.nan, s / (float(SSIM_ONE) * n))
+
+    def threshold_for(self, max_changed: float = 1e-3, region=None) -> int:
+        """The ``threshold`` for ``change_mask(..., smooth=self.smooth)`` under which these two clips count as unchanged: the smallest
+        ``t`` in 0..254 such that the pixels with a smoothed difference above ``t``, over all frames (and samples), number at most
+        ``floor(max_changed * pixels)``; 254 if none does.  Run it on a clip and its ``vae_roundtrip_frames``."""
+        h = self._pool(self.smooth_hist, region, True, -2).reshape(-1, 256).sum(0)
+        above = int(h.sum()) - np.cumsum(h)                                      # above[t]: pixels with s > t
+        ok = np.nonzero(above[:255] <= math.floor(float(max_changed) * int(h.sum())))[0]
+        return int(ok[0]) if ok.size else 254
+
+
+def _stats_smooth(what: str, smooth) -> int:
+    smooth = int(smooth)
+    if not 0 <= smooth <= MASK_MAX_SMOOTH:
+        raise ValueError(f"{what}: smooth={smooth} (0..{MASK_MAX_SMOOTH})")
+    return smooth
+
+
+def _stats_alpha(what: str, alpha, shape):
+    """-> alpha as a uint8 tensor of the clips' [.., T, H, W], or None."""
+    if alpha is None:
+        return None
+    a = torch.from_numpy(alpha) if isinstance(alpha, np.ndarray) else alpha
+    if not torch.is_tensor(a) or a.dtype != torch.uint8 or tuple(a.shape) != tuple(shape[:-1]):
+        raise ValueError(f"{what}: alpha {getattr(a, 'dtype', type(a))} {tuple(getattr(a, 'shape', ()))} for clips {tuple(shape)}: "
+                         f"expected uint8 {tuple(shape[:-1])}")
+    return a
+
+
+def _clip_stats_of(words: np.ndarray, lead, smooth: int) -> ClipStats:
+    """int64 [N, 2, 514] as the kernel lays it out -> ClipStats with the clips' leading sizes."""
+    w = np.ascontiguousarray(words).reshape(*lead, 2, ops.CLIP_STATS_WORDS)
+    return ClipStats(w[..., :256].copy(), w[..., 256:512].copy(), w[..., 512].copy(), w[..., 513].copy(), smooth)
+
+
+def reference_clip_stats(a_u8, b_u8, alpha=None, *, smooth: int = 2) -> ClipStats:
+    """The definition of ``clip_stats`` in numpy int64 (float64 for the one division of an SSIM window) on the host, DESIGN.md section
+    4.3.4.  What the kernels equal word for word; never called by the product path."""
+    smooth = _stats_smooth("reference_clip_stats", smooth)
+    a, b = _mask_clips(a_u8, b_u8, "reference_clip_stats")
+    al = _stats_alpha("reference_clip_stats", alpha, a.shape)
+    lead, (H, W) = a.shape[:-3], a.shape[-3:-1]
+    a, b = a.reshape(-1, H, W, 3), b.reshape(-1, H, W, 3)
+    N = a.shape[0]
+    region = np.zeros((N, H, W), np.int64) if al is None else (al.cpu().numpy().reshape(N, H, W) != 0).astype(np.int64)
+    frame = np.arange(N, dtype=np.int64)[:, None, None]
+    words = np.zeros((N, 2, ops.CLIP_STATS_WORDS), np.int64)
+
+    diff = np.abs(a - b)                                                        # the byte histogram
+    key = ((frame * 2 + region)[..., None] * 256 + diff).ravel()
+    words[:, :, :256] = np.bincount(key, minlength=N * 512).reshape(N, 2, 256)
+
+    n = (2 * smooth + 1) ** 2                                                   # the smoothed histogram: reference_change_mask's steps 1-2
+    sm = (2 * _box_sum(diff.max(-1), smooth, (-1, -2), True) + n) // (2 * n)
+    key = ((frame * 2 + region) * 256 + sm).ravel()
+    words[:, :, 256:512] = np.bincount(key, minlength=N * 512).reshape(N, 2, 256)
+
+    h4, w4 = H >> 2, W >> 2                                                     # SSIM
+    if h4 >= 2 and w4 >= 2:
+        def blocks(x):                                                          # [N, 4 h4, 4 w4, ..] -> the 4 x 4 blocks' sums
+            x = x[:, :4 * h4, :4 * w4]
+            return x.reshape(N, h4, 4, w4, 4, *x.shape[3:]).sum((2, 4))
+
+        def windows(x):                                                         # 2 x 2 neighbouring blocks
+            return x[:, :-1, :-1] + x[:, 1:, :-1] + x[:, :-1, 1:] + x[:, 1:, 1:]
+
+        s1, s2, ss, s12 = (windows(blocks(x)) for x in (a, b, a * a + b * b, a * b))
+        vars_, covar = 64 * ss - s1 * s1 - s2 * s2, 64 * s12 - s1 * s2
+        f = [x.astype(np.float64) for x in (2 * s1 * s2 + SSIM_C1, 2 * covar + SSIM_C2, s1 * s1 + s2 * s2 + SSIM_C1, vars_ + SSIM_C2)]
+        q = np.rint((f[0] * f[1]) / (f[2] * f[3]) * float(SSIM_ONE)).astype(np.int64).sum(-1)      # [N, h4 - 1, w4 - 1]: three planes
+        wr = (windows(blocks(region)) != 0).astype(np.int64)
+        for r in (0, 1):
+            words[:, r, 512] = np.where(wr == r, q, 0).sum((1, 2))
+            words[:, r, 513] = 3 * (wr == r).sum((1, 2))
+    return _clip_stats_of(words, lead, smooth)
+
+
+def clip_stats(a_u8, b_u8, alpha=None, *, smooth: int = 2) -> ClipStats:
+    """How far is clip ``b_u8`` from clip ``a_u8``: one pass of integer kernels over the two clips on the device
+    (``wan_clip_stats``, four launches; the definition is ``reference_clip_stats``), then one copy of ``T * 2 * 514`` words to the
+    host.  PSNR, MAE, the maximum, quantiles, SSIM and the ``threshold`` for ``change_mask`` follow from those on the host
+    (``ClipStats``), each for the pixels where ``alpha`` is 0 and where it is not.
+
+    ``a_u8``, ``b_u8``: uint8 ``[T, H, W, 3]`` or ``[B, T, H, W, 3]`` of one shape, host or device; ``alpha``: uint8 ``[T, H, W]`` /
+    ``[B, T, H, W]`` as ``change_mask`` returns it, or None (everything is region 0); ``0 <= smooth <= 7``, else ``ValueError``."""
+    smooth = _stats_smooth("clip_stats", smooth)
+    a, b = _as_clip(a_u8, "clip_stats.a"), _as_clip(b_u8, "clip_stats.b")
+    if a.shape != b.shape:
+        raise ValueError(f"clip_stats: a {tuple(a.shape)} and b {tuple(b.shape)} differ in shape")
+    al = _stats_alpha("clip_stats", alpha, a.shape)
+    if al is not None:
+        al = al.to(a.device)
+    a5, b5, al5 = (x if x is None or a.dim() == 5 else x.unsqueeze(0) for x in (a, b, al))
+    return _clip_stats_of(ops.clip_stats(a5, b5, al5, smooth).cpu().numpy(), a.shape[:-3], smooth)
+
+
+def vae_roundtrip_frames(vae, frames_u8) -> torch.Tensor:
+    """The bytes ``WanPipeline`` would return for a clip if the DiT changed nothing: frames -> video -> the mode of the VAE's
+    posterior -> decoded -> frames, in the VAE's dtype, on the device.  ``frames_u8``: uint8 ``[T, H, W, 3]`` or ``[B, T, H, W, 3]``,
+    host or device; returns device frames of the same shape.  ``clip_stats(frames, vae_roundtrip_frames(vae, frames))`` is the error
+    floor of a checkpoint in pixels, and its ``threshold_for()`` the ``threshold`` that ``change_mask`` needs to ignore it."""
+    x = _as_clip(frames_u8, "vae_roundtrip_frames")
+    video = ops.frames_u8_to_video(x if x.dim() == 5 else x.unsqueeze(0), vae.dtype)
+    latents = torch.cat([vae.encode(video[i:i + 1])[0].mode() for i in range(video.shape[0])])
+    frames = ops.video_to_frames_u8(vae.decode(latents.to(vae.dtype)).sample)
+    return frames if x.dim() == 5 else frames[0]
 
 
 # ---------------------------------------------------------------------------------------------- the writer's grid, the compare clip
