@@ -59,7 +59,10 @@ const char* wan_last_error(void);
  * WAN_ATTN_VARIANT_* (kernel family | WAN_ATTN_VARIANT_XCD_PINNED | WAN_ATTN_VARIANT_SPLIT_TAIL) -- so that a benchmark
  * reports the kernel the dispatcher picked instead of a literal.  Read-only key "dev_experiments": 1 if the library was built with
  * `make EXPERIMENTS=1` (the timing-only instruments of the persistent GEMM behind "gemm_exp" -- cycle stamps, forced waits -- compiled
- * in; never in the product build: there "gemm_exp" does nothing). */
+ * in; never in the product build: there "gemm_exp" does nothing).
+ * "cross_fold" (WAN_CROSS_FOLD, default 1): the folded cross-attention branch of wan_dit_block_tail_forward (a9f below): 0 never,
+ * 1 by wan_cross_fold_plan's rule, 2 wherever the kernels are legal.  Read-only key "last_cross_fold": 1 if the most recent
+ * wan_dit_block_tail_forward of this process ran the folded branch, else 0. */
 wan_status_t wan_set_tuning(const char* key, int value);
 int wan_get_tuning(const char* key);
 #define WAN_ATTN_VARIANT_W4_LAZY 1          /* attn_fwd_w4_kernel<.,.,1|2>: 4 waves, lazy softmax reference, one launch */
@@ -327,6 +330,37 @@ wan_status_t wan_col_mean_bf16(const void* x_bf16, int64_t ld, int64_t rows_per_
 wan_status_t wan_qk_quantize_fp8(const void* q_bf16, const void* k_bf16, int64_t ld, int64_t rows, int dim, int64_t rows_per_batch,
                                  const float* k_mean, float q_scale, float k_scale, void* q8, void* k8, void* stream);
 
+/* ---------------------------------------------------------------------------
+ * a9f  Cross-attention over a padded prompt with the text values folded into the output projection.
+ *     replaces: WanT2VCrossAttention.forward (wan_transformer3d.py:313-333) + its `o` Linear for the usual case of a short prompt.
+ *               The reference pads the prompt with zero rows to text_len BEFORE text_embedding and masks nothing (context_lens = None,
+ *               :936): every text row behind the longest prompt of the call is one and the same row in every layer.  With `kept` rows
+ *               scored one by one and row `kept` standing for the pad_count = text_len - kept identical ones (its exp2-domain score
+ *               raised by log2(pad_count)), a head has kept + 1 <= 64 distinct keys and
+ *                   att . W_co^T = sum_h (P_h V_h) W_co,h^T = sum_h P_h (V_h W_co,h^T) = P . V'
+ *               -- the output projection contracts over num_heads * 64 probabilities instead of num_heads * 128 channels.
+ *     wan_cross_probs:       probs bf16 [batch * rows_per_batch][ldp >= num_heads * 64]: column h * 64 + j = softmax weight of key j
+ *                            of head h (the representative's includes all pad_count rows); columns j > kept are exact zeros.  q bf16
+ *                            [batch * rows_per_batch][ldq] PRE-SCALED (softmax_scale * log2 e, as wan_rmsnorm_rope's x0_scale writes
+ *                            it); k bf16 [batch][>= kept + 1 rows][ldk] (sample stride k_bstride).  fp32 scores (MFMA), softmax in the
+ *                            exp2 domain against the row maximum, normalised in fp32, ONE rounding to bf16.  0 <= kept <= 63.
+ *     wan_cross_fold_values: vfold bf16 [batch][dim][ldo >= num_heads * 64] = V'^T in nn.Linear layout (a weight of wan_gemm_bf16_ws):
+ *                            vfold[b][n][h * 64 + j] = bf16( sum_d w_co[n][h * 128 + d] * vt[b][h * 128 + d][j] ), j <= kept, zeros
+ *                            above; fp32 accumulation in a fixed order of d.  vt = the text V^T of wan_dit_block_forward.
+ *     wan_cross_fold_plan:   THE RULE (host arithmetic only): 1 when `rows` (= batch * rows_per_batch) query rows should take the
+ *                            folded branch -- tuning key "cross_fold" is not 0, bf16 weights, 1 <= kept, kept + 1 <= 64, kept <
+ *                            text_len, and (unless "cross_fold" = 2) num_heads * 64 >= 1024, % 128 == 0 and rows >= the measured
+ *                            crossover (cross_fold.hip).  kept = text_len means "prompt length not known": never folds.
+ *     wan_cross_fold_workspace_bytes: bytes of vfold for a batch (batch * dim * num_heads * 64 * 2).
+ *     All rows 16-byte aligned (ld* and strides % 8 == 0).  No scratch; the results do not depend on the launch.
+ * ------------------------------------------------------------------------- */
+wan_status_t wan_cross_probs(const void* q, int64_t ldq, const void* k, int64_t ldk, int64_t k_bstride, void* probs, int64_t ldp,
+                             int batch, int64_t rows_per_batch, int num_heads, int kept, int pad_count, void* stream);
+wan_status_t wan_cross_fold_values(const void* w_co, int64_t ldw, const void* vt, int64_t ldvt, int64_t vt_bstride, void* vfold,
+                                   int64_t ldo, int64_t vfold_bstride, int batch, int dim, int num_heads, int kept, void* stream);
+int wan_cross_fold_plan(int64_t rows, int num_heads, int text_len, int kept, int weights_bf16);
+int64_t wan_cross_fold_workspace_bytes(int batch, int dim);
+
 /* [rows, cols] bf16 (row stride ld) -> [cols, ldt] bf16 transposed; pad columns [rows, ldt) are zeroed.
  * Used when a caller hands attention() a row-major V (the reference's [B,L,N,D] layout). */
 wan_status_t wan_transpose_bf16(const void* in, int64_t ld, void* out_t, int64_t ldt,
@@ -458,6 +492,10 @@ wan_status_t wan_sp_channel_copy(void* dst, const void* src, int64_t bytes, int 
  *      valid_tokens = F*Hp*Wp <= rows_per_batch: keys beyond it (sequence padding) are masked, V^T covers them only.
  *      Workspaces are caller-owned (sizes: wan_dit_block_workspace_bytes); vt's pad columns [valid_tokens, ldvt) must be
  *      finite (zero them once); the two attention scratches follow wan_attention_workspace_bytes and may be NULL.
+ *      Cross-attention: when wan_cross_fold_plan(batch * rows_per_batch, num_heads, text_len, ws->text_kept, 1) says so and ws->vfold
+ *      is there, `cross-attention -> o GEMM` runs as wan_cross_probs (into ws->att) -> wan_cross_fold_values (into ws->vfold) -> one
+ *      o GEMM per sample over K = num_heads * 64 (a9f): the same sum with V' rounded to bf16 where the plain branch rounds the
+ *      attention output -- equal within the kernels' tolerances, not bit for bit.  A zero-initialised vfold / text_kept keeps the plain branch.
  * ------------------------------------------------------------------------- */
 typedef struct {
     int dim, ffn_dim, num_heads, text_len;
@@ -475,6 +513,12 @@ typedef struct {
     void* attn_ws_cross; int64_t attn_ws_cross_bytes;
     void* gemm_ws; int64_t gemm_ws_bytes;      /* wan_gemm_bf16_ws workspace shared by the block's Linears (wan_gemm_workspace_bytes of the
                                                   largest one; NULL = the one-workgroup-per-tile kernels) */
+    void* vfold; int64_t vfold_bytes;          /* the folded text values V'^T (a9f): wan_cross_fold_workspace_bytes(batch, dim) bytes, rewritten
+                                                  by every layer of every call; NULL = never fold */
+    int text_kept;                             /* longest prompt of the call in text rows (the host knows it: len(context[b])); rows behind it
+                                                  are identical padding.  <= 0 or >= text_len = not known: never fold.
+                                                  (vfold, vfold_bytes, text_kept were appended at the END of the struct under ABI 11: a host
+                                                  compiled against the shorter struct must be recompiled; zero-initialised they change nothing) */
 } wan_block_workspace;
 
 wan_status_t wan_dit_block_forward(float* x, const float* emod, const void* ctx_k, const void* ctx_vt,

@@ -97,7 +97,8 @@ class BlockWorkspace(Structure):
     _fields_ = ([(n, c_void_p) for n in ("h", "qk", "att", "cq", "ff", "vt")] + [("ldvt", c_int64)] +
                 [("attn_ws_self", c_void_p), ("attn_ws_self_bytes", c_int64),
                  ("attn_ws_cross", c_void_p), ("attn_ws_cross_bytes", c_int64),
-                 ("gemm_ws", c_void_p), ("gemm_ws_bytes", c_int64)])
+                 ("gemm_ws", c_void_p), ("gemm_ws_bytes", c_int64),
+                 ("vfold", c_void_p), ("vfold_bytes", c_int64), ("text_kept", c_int)])
 
 
 class DitWeights(Structure):
@@ -179,6 +180,12 @@ SIGNATURES = {
     "wan_qk_quantize_fp8": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int64, c_void_p, c_float, c_float, c_void_p, c_void_p,
                                     c_void_p]),
     "wan_attention_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
+    "wan_cross_probs": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int, c_int64, c_int, c_int, c_int,
+                                c_void_p]),
+    "wan_cross_fold_values": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_int, c_int, c_int,
+                                      c_int, c_void_p]),
+    "wan_cross_fold_plan": (c_int, [c_int64, c_int, c_int, c_int, c_int]),
+    "wan_cross_fold_workspace_bytes": (c_int64, [c_int, c_int]),
     "wan_sp_unique_id": (c_int, [c_void_p]),
     "wan_sp_init": (c_int, [ctypes.POINTER(c_void_p), c_void_p, c_int, c_int]),
     "wan_sp_init_from_comm": (c_int, [ctypes.POINTER(c_void_p), c_void_p, c_int, c_int]),

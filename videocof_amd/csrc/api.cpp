@@ -79,6 +79,7 @@ const TuningKey kTuningKeys[WAN_TUNE_COUNT] = {
     {"conv_mfma", "WAN_CONV_MFMA", 0},                  // matrix instruction of the VAE's LDS-patch convolution: 0 = by the per-frame plane (16x16x32 when four frames of it fill the chip; never by frame count -- chunked decodes stay bit-identical), 32 = v_mfma_f32_32x32x16_bf16, 16 = v_mfma_f32_16x16x32_bf16
     {"attn_persist", "WAN_ATTN_PERSIST", 1},            // short-KV (cross-attention) launches on the persistent form of the 4-wave kernel: one resident workgroup per CU walks the query blocks (0 = one workgroup per block, developer A/B)
     {"sp_reserve_cus", "WAN_SP_RESERVE_CUS", 0},        // CUs the persistent grids (gemm_pk, persistent cross-attention) leave free for communication kernels on another stream: they size themselves from wan_cu_count() - this (0 = the whole chip; init_sequence_parallel(reserve_cus=N) sets it)
+    {"cross_fold", "WAN_CROSS_FOLD", 1},                // cross-attention with the text values folded into the output projection (cross_fold.hip): 0 never, 1 by wan_cross_fold_plan's rule, 2 wherever the kernels are legal (developer A/B, tests)
 };
 struct Tuning {
     std::atomic<int> v[WAN_TUNE_COUNT];
@@ -113,6 +114,7 @@ extern "C" wan_status_t wan_set_tuning(const char* key, int value) {
 
 extern "C" int wan_get_tuning(const char* key) {
     if (key && !strcmp(key, "last_attn_variant")) return g_last_attn_variant.load(std::memory_order_relaxed);
+    if (key && !strcmp(key, "last_cross_fold")) return wan_last_cross_fold();
     if (key && !strcmp(key, "dev_experiments")) return WAN_DEV_EXPERIMENTS;      // 1: built with `make EXPERIMENTS=1` (the gemm_exp instruments of the persistent GEMM compiled in)
     if (key)
         for (int i = 0; i < WAN_TUNE_COUNT; ++i)

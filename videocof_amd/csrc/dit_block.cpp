@@ -90,9 +90,23 @@ extern "C" wan_status_t wan_dit_block_tail_forward(float* x, const float* emod, 
     WAN_TRY(wan_ln_modulate(x, w->norm3_w, w->norm3_b, 0, ws->h, M, C, M, eps, stream));
     WAN_TRY(wan_gemm_bf16_ws(ws->h, C, w->w_cq, C, w->b_cq, ws->cq, C, (int)M, C, C, WAN_EPI_BF16, nullptr, 0, GWS, GWSB, stream));
     WAN_TRY(wan_rmsnorm_rope(ws->cq, w->norm_cq, nullptr, nullptr, C, M, C, 128, eps, nullptr, nullptr, nullptr, qs, stream));
-    WAN_TRY(wan_attention_fwd(ws->cq, C, Ll * C, ctx_k, C, (int64_t)T * C, ctx_vt, T, (int64_t)C * T, ws->att, C, Ll * C, batch, (int)Ll,
-                              T, H, 128, 0.f, WAN_ATTN_Q_PRESCALED, ws->attn_ws_cross, ws->attn_ws_cross_bytes, stream));
-    WAN_TRY(wan_gemm_bf16_ws(ws->att, C, w->w_co, C, w->b_co, x, C, (int)M, C, C, WAN_EPI_RESID_F32, nullptr, 0, GWS, GWSB, stream));
+    const int kept = ws->text_kept;
+    const bool fold = ws->vfold && ws->vfold_bytes >= wan_cross_fold_workspace_bytes(batch, C) && wan_cross_fold_plan(M, H, T, kept, 1);
+    wan_note_cross_fold(fold ? 1 : 0);
+    if (fold) {
+        // the text values folded into the output projection (include/wan_hip.h a9f): P over the kept + 1 distinct keys of every head
+        // into ws->att, V'^T = W_co (x) V per sample into ws->vfold, then x += P . V' + b_co -- K = 64 H instead of 128 H
+        const int64_t Kf = (int64_t)H * 64;
+        WAN_TRY(wan_cross_probs(ws->cq, C, ctx_k, C, (int64_t)T * C, ws->att, Kf, batch, Ll, H, kept, T - kept, stream));
+        WAN_TRY(wan_cross_fold_values(w->w_co, C, ctx_vt, T, (int64_t)C * T, ws->vfold, Kf, (int64_t)C * Kf, batch, C, H, kept, stream));
+        for (int b = 0; b < batch; ++b)
+            WAN_TRY(wan_gemm_bf16_ws(at(ws->att, (int64_t)b * Ll * Kf * 2), Kf, at(ws->vfold, (int64_t)b * C * Kf * 2), Kf, w->b_co,
+                                  x + (int64_t)b * Ll * C, C, (int)Ll, C, (int)Kf, WAN_EPI_RESID_F32, nullptr, 0, GWS, GWSB, stream));
+    } else {
+        WAN_TRY(wan_attention_fwd(ws->cq, C, Ll * C, ctx_k, C, (int64_t)T * C, ctx_vt, T, (int64_t)C * T, ws->att, C, Ll * C, batch, (int)Ll,
+                                  T, H, 128, 0.f, WAN_ATTN_Q_PRESCALED, ws->attn_ws_cross, ws->attn_ws_cross_bytes, stream));
+        WAN_TRY(wan_gemm_bf16_ws(ws->att, C, w->w_co, C, w->b_co, x, C, (int)M, C, C, WAN_EPI_RESID_F32, nullptr, 0, GWS, GWSB, stream));
+    }
     // ---- FFN (:507-511)
     WAN_TRY(wan_ln_modulate(x, scale_mlp, shift_mlp, 1, ws->h, M, C, Ll, eps, stream));
     WAN_TRY(wan_gemm_bf16_ws(ws->h, C, w->w_ffn0, C, w->b_ffn0, ws->ff, F, (int)M, F, C, WAN_EPI_GELU_BF16, nullptr, 0, GWS, GWSB, stream));

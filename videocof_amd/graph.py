@@ -107,7 +107,9 @@ class GraphedForward:
                int(m.mask_source_frames), len(context), torch.cuda.current_device(), tuple(m._fp8),
                bool(m.use_block_composite), bool(m.use_forward_composite), tuple(m.fp8_attn_exponents), bool(m.fp8_attn_smooth_k), bool(getattr(m, 'fp8_attn_calibrate', False)),
                # a call the model's cfg_skip rule halves enqueues other launches than a full one of the same shape
-               bool(m.cfg_skip_now(x.shape[0])))
+               bool(m.cfg_skip_now(x.shape[0])),
+               # the longest prompt decides which cross-attention branch the blocks enqueue and how many text rows it scores
+               max(int(u.shape[0]) for u in context))
         epoch = m._graph_epoch
         for k in [k for k, e in self._entries.items() if e.epoch != epoch]:
             stale = self._entries.pop(k)                 # weights / fp8 copies / workspaces were replaced since the capture

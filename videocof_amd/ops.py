@@ -542,6 +542,52 @@ def attention_fwd(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, num_heads:
     return out
 
 
+def cross_fold_plan(rows: int, num_heads: int, text_len: int, kept: int, weights_bf16: bool = True) -> bool:
+    """``wan_cross_fold_plan`` (include/wan_hip.h a9f): THE rule -- whether `rows` query rows take the folded cross-attention branch."""
+    return bool(_lib.load().wan_cross_fold_plan(int(rows), int(num_heads), int(text_len), int(kept), int(bool(weights_bf16))))
+
+
+@_on_tensor_device
+def cross_probs(q: torch.Tensor, k: torch.Tensor, num_heads: int, kept: int, pad_count: int,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``wan_cross_probs``: q bf16 [B, L, H*128] pre-scaled (dense samples: L rows of stride q.stride(1) each), k bf16 [B, T, H*128]
+    -> softmax weights bf16 [B*L, H*64] over keys 0..kept (key `kept` standing for `pad_count` identical rows)."""
+    _need(q, torch.bfloat16, "cross_probs.q")
+    _need(k, torch.bfloat16, "cross_probs.k")
+    B, L, C = q.shape
+    if k.dim() != 3 or k.shape[0] != B or k.shape[2] != C or C != num_heads * 128 or k.shape[1] < kept + 1:
+        raise ValueError(f"cross_probs: q {tuple(q.shape)} / k {tuple(k.shape)} / heads {num_heads} / kept {kept} disagree")
+    if B > 1 and q.stride(0) != L * q.stride(1):
+        raise ValueError("cross_probs: the samples of q must follow each other without a gap")
+    if out is None:
+        out = torch.empty(B * L, num_heads * 64, device=q.device, dtype=torch.bfloat16)
+    _need(out, torch.bfloat16, "cross_probs.out")
+    if tuple(out.shape) != (B * L, num_heads * 64):
+        raise ValueError(f"cross_probs: out shape {tuple(out.shape)} != ({B * L},{num_heads * 64})")
+    _lib.check(_lib.load().wan_cross_probs(_p(q), q.stride(1), _p(k), k.stride(1), k.stride(0), _p(out), out.stride(0), B, L,
+                                           int(num_heads), int(kept), int(pad_count), _stream()), "wan_cross_probs")
+    return out
+
+
+@_on_tensor_device
+def cross_fold_values(w_co: torch.Tensor, vt: torch.Tensor, num_heads: int, kept: int,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``wan_cross_fold_values``: w_co bf16 [C, C], vt bf16 [B, C, T] (the text V^T) -> V'^T bf16 [B, C, H*64] in nn.Linear layout."""
+    _need(w_co, torch.bfloat16, "cross_fold_values.w_co")
+    _need(vt, torch.bfloat16, "cross_fold_values.vt")
+    B, C, T = vt.shape
+    if tuple(w_co.shape) != (C, C) or C != num_heads * 128:
+        raise ValueError(f"cross_fold_values: w_co {tuple(w_co.shape)} / vt {tuple(vt.shape)} / heads {num_heads} disagree")
+    if out is None:
+        out = torch.empty(B, C, num_heads * 64, device=vt.device, dtype=torch.bfloat16)
+    _need(out, torch.bfloat16, "cross_fold_values.out")
+    if tuple(out.shape) != (B, C, num_heads * 64):
+        raise ValueError(f"cross_fold_values: out shape {tuple(out.shape)} != ({B},{C},{num_heads * 64})")
+    _lib.check(_lib.load().wan_cross_fold_values(_p(w_co), w_co.stride(0), _p(vt), vt.stride(1), vt.stride(0), _p(out), out.stride(1),
+                                                 out.stride(0), B, C, int(num_heads), int(kept), _stream()), "wan_cross_fold_values")
+    return out
+
+
 @_on_tensor_device
 def rmsnorm_rope_fp8(x0: torch.Tensor, w0: torch.Tensor, x1: Optional[torch.Tensor], w1: Optional[torch.Tensor], head_dim: int,
                      eps: float, rope: Optional[Tuple[torch.Tensor, torch.Tensor]], rope_params: Optional[RopeParams],

@@ -182,6 +182,8 @@ class WanTransformer3DModel(nn.Module):
         self._usp = False                   # this forward runs the Ulysses branch (set by forward)
         self._comm_events = None            # bench.py: list collecting (start, end) HIP events around the EXPOSED exchanges
         self.cache_context = False          # hoist step-invariant text K/V (parity neutral)
+        self._text_kept = text_len          # longest prompt of the current call in text rows (text_len = not known: no cross-attention fold)
+        self.last_cross_fold = False        # whether the most recent block ran the folded cross-attention branch (wan_cross_fold_plan)
         self._ctx_cache = None
         self._fp8 = ()                      # enable_fp8_linear: which projections run in e4m3 (lossy, opt-in)
         self.fp8_attn_exponents = (5, 2)    # "attn": q8 = e4m3(q * scale * log2e * 2^5), k8 = e4m3(k * 2^2) (include/wan_hip.h a9')
@@ -1132,12 +1134,30 @@ class WanTransformer3DModel(nn.Module):
         a = self._ln_operand(blk, "cq", x, blk.n3w, blk.n3b, False, B * n, bufs, h, bf16)
         self._linear(blk, "cq", a, ops.EPI_BF16, cq)
         ops.rmsnorm_rope_(cq, blk.ncq, None, None, self.d, self.eps, x0_scale=self._qs)
-        ops.attention_fwd(cq.view(B, n, C), *ctx_kv, self.num_heads, out=att.view(B, n, C), q_prescaled=True, workspace=ws_cross)
-        self._linear(blk, "co", self._row_operand(blk, "co", att, bufs, bf16), ops.EPI_RESID_F32, x)
+        H, kept = self.num_heads, self._text_kept
+        self.last_cross_fold = bool(load().wan_cross_fold_plan(B * n, H, self.text_len, kept, int(bf16 or not (blk.f8 and "co" in blk.f8))))
+        if self.last_cross_fold:
+            # the text values folded into the output projection: the launches of wan_dit_block_tail_forward's folded branch
+            probs = att.reshape(-1)[:B * n * H * 64].view(B * n, H * 64)
+            ops.cross_probs(cq.view(B, n, C), ctx_kv[0], H, kept, self.text_len - kept, out=probs)
+            vfold = self._vfold(bufs, B)
+            ops.cross_fold_values(blk.w_co, ctx_kv[1], H, kept, out=vfold)
+            for b in range(B):
+                ops.gemm(probs[b * n:(b + 1) * n], vfold[b], blk.b_co, ops.EPI_RESID_F32, out=x[b * n:(b + 1) * n])
+        else:
+            ops.attention_fwd(cq.view(B, n, C), *ctx_kv, self.num_heads, out=att.view(B, n, C), q_prescaled=True, workspace=ws_cross)
+            self._linear(blk, "co", self._row_operand(blk, "co", att, bufs, bf16), ops.EPI_RESID_F32, x)
         # ---- FFN (:507-511)
         a = self._ln_operand(blk, "w1", x, em[4], em[3], True, n, bufs, h, bf16)
         self._linear(blk, "w1", a, ops.EPI_GELU_BF16, ff)
         self._linear(blk, "w2", self._row_operand(blk, "w2", ff, bufs, bf16), ops.EPI_RESID_F32, x, gate=em[5], rows_per_batch=n)
+
+    def _vfold(self, bufs, B):
+        """V'^T of the folded cross-attention branch (include/wan_hip.h a9f), bf16 [B, C, 64 H]: part of the activation set, but allocated
+        only by a call that folds -- a shape the rule keeps on the plain branch allocates exactly what it always did."""
+        if getattr(bufs, "vfold", None) is None:
+            bufs.vfold = torch.empty(B, self.dim, self.num_heads * 64, device=self._device, dtype=torch.bfloat16)
+        return bufs.vfold
 
     def _run_block(self, blk: _Block, em, xs, bufs, ctx_kv, rp, B, Ll, L, seq_len):
         """One WanAttentionBlock (:464-515) in place on the fp32 residual stream xs [B*Ll, C].
@@ -1198,6 +1218,11 @@ class WanTransformer3DModel(nn.Module):
             vt = getattr(bufs, "vt", None)                       # (None under Ulysses: the tail composite does not touch qk / vt)
             holder.cws = BlockWorkspace(p(bufs.h), p(bufs.qk), p(bufs.att), p(bufs.cq), p(bufs.ff), p(vt) if vt is not None else None,
                                         vt.stride(1) if vt is not None else 0, None, bufs.nself, None, bufs.ncross, None, 0)
+        # the prompt lengths of THIS call: wan_cross_fold_plan decides inside the composite, given V'^T's buffer
+        fold = bool(load().wan_cross_fold_plan(B * Ll, self.num_heads, self.text_len, self._text_kept, 1))
+        holder.cws.text_kept = self._text_kept
+        holder.cws.vfold = self._vfold(bufs, B).data_ptr() if fold else None
+        holder.cws.vfold_bytes = bufs.vfold.numel() * 2 if fold else 0
         # the attention scratches belong to the call sites (AttentionWorkspace objects that may be re-allocated when another
         # shape asks for more): take their CURRENT addresses on every call, never a cached pointer
         holder.cws.attn_ws_self = self._ws_self.get(self._device, max(bufs.nself, 16)).data_ptr()
@@ -1209,8 +1234,9 @@ class WanTransformer3DModel(nn.Module):
         # every GEMM shape of wan_dit_block_forward: the four per-token Linears at M = B * Ll and the V^T projection, which runs per
         # sample at M = L valid tokens (a smaller M can ask for MORE workspace: the split-K form of small shapes) -- the composite must
         # never fall back to another kernel than the per-op path takes (ops.gemm sizes its own request), or the two stop being bit-identical
+        # ... and, when this call folds the cross-attention, its output projection: per sample at K = 64 heads
         for (m_, n_, k_) in ((M, 2 * self.dim, self.dim), (M, self.ffn_dim, self.dim), (M, self.dim, self.ffn_dim), (M, self.dim, self.dim),
-                             (L, self.dim, self.dim)):
+                             (L, self.dim, self.dim)) + (((Ll, self.dim, self.num_heads * 64),) if fold else ()):
             t = ops.gemm_workspace(self._device, m_, n_, k_)
             if t is not None and (gws is None or t.numel() > gws.numel()):
                 gws = t
@@ -1247,6 +1273,7 @@ class WanTransformer3DModel(nn.Module):
             check(lib.wan_dit_forward(*args, ops._stream()), "wan_dit_forward")
         else:       # a cfg_skip step: the unpatchify store writes the result `rep` times along the batch axis
             check(lib.wan_dit_forward_rep(*args, rep, ops._stream()), "wan_dit_forward_rep")
+        self.last_cross_fold = bool(load().wan_get_tuning(b"last_cross_fold"))
         return out
 
     def _block_composite(self, blk: _Block, em, xs, bufs, ctx_kv, rp, B, Ll, L):
@@ -1262,6 +1289,7 @@ class WanTransformer3DModel(nn.Module):
         else:
             check(load().wan_dit_block_forward(*args, p(self._rope_dev[0].data_ptr()), p(self._rope_dev[1].data_ptr()), ctypes.byref(rp),
                                                B, Ll, L, ops._stream()), "wan_dit_block_forward")
+        self.last_cross_fold = bool(load().wan_get_tuning(b"last_cross_fold"))
 
     @torch.no_grad()
     def head_forward(self, x: torch.Tensor, e: torch.Tensor) -> torch.Tensor:
@@ -1276,14 +1304,17 @@ class WanTransformer3DModel(nn.Module):
 
     @torch.no_grad()
     def block_forward(self, x: torch.Tensor, e: torch.Tensor, context: torch.Tensor, grid_sizes, block_index: int = 0,
-                      frame_split_indices=None, ground_frame_indices=None) -> torch.Tensor:
+                      frame_split_indices=None, ground_frame_indices=None, text_kept: Optional[int] = None) -> torch.Tensor:
         """``WanAttentionBlock.forward`` (:464-515) of block ``block_index`` on a given residual stream.
         x fp32 [B, L, C]; e fp32 [B, 6, C] (the time projection; the block adds its own ``modulation``, :494);
         context [B, text_len, C] (already through ``text_embedding``); grid_sizes (F, Hp, Wp) with F*Hp*Wp <= L.
+        ``text_kept``: the longest prompt behind ``context`` in rows, when the caller knows that every row from there on is the
+        same padding row (what ``text_embedding`` makes of the reference's zero rows); None = not known, the plain cross-attention.
         Returns the new residual stream, fp32 [B, L, C].  Single device only."""
         if self.sp_world_size != 1 or self.force_ulysses:
             raise NotImplementedError("block_forward is the single-device composite")
         self._usp = False
+        self._text_kept = self.text_len if text_kept is None else int(text_kept)
         B, Ll, C = x.shape
         grid = tuple(int(v) for v in grid_sizes)
         L = grid[0] * grid[1] * grid[2]
@@ -1340,6 +1371,9 @@ class WanTransformer3DModel(nn.Module):
             raise NotImplementedError("per-token timesteps (Wan2.2-5B) are never produced by WanPipeline")
         if t.numel() != B or len(context) != B:
             raise ValueError(f"batch mismatch: x has {B} samples, t {t.numel()}, context {len(context)}")
+        # rows of the padded prompts that differ: everything behind the longest prompt is one repeated row (_text_embed pads with zero
+        # rows BEFORE text_embedding, as the reference does), which the folded cross-attention branch scores once
+        self._text_kept = max(int(u.shape[0]) for u in context)
         # Samples with DIFFERENT CoF position maps in one call (rope_apply_qk takes them per sample, :160-179; WanPipeline never produces
         # this): the kernels take one map per launch, and a sample's result does not depend on its batch mates, so the call is served
         # group by group -- samples that share a map together, the outputs back in the caller's order.
