@@ -596,6 +596,31 @@ wan_status_t wan_solver_step(void* x0_out, void* prev_out, int dtype, const void
                              const void* m2, const float* noise, float a_s, float a_v, float c_s, float c_0, float c_1,
                              float c_2, float c_n, int64_t n, void* stream);
 
+/* a17c  Temporal context windows (DESIGN.md "Temporal context windows"): a clip of Fs latent frames is denoised as K overlapping
+ *      windows of n frames each, window k starting at latent frame starts[k] (host array; ascending from 0, the last one at
+ *      Fs - n, no gap: anything else is WAN_ERR_INVALID; K <= WAN_WINDOW_MAX).  The loop's state is ONE tensor
+ *          state [B, C, Fs + K*G + Fs, h, w] = [source | ground_0 .. ground_{K-1} | target]      (G grounding frames, 0 = none)
+ *      and a window is [C, n + G + n, h, w] = [source[a_k : a_k + n] | ground_k | target[a_k : a_k + n]].  hw = h * w elements per
+ *      frame; dtype 0 fp32, 1 bf16 (state, windows and predictions alike).  16-byte accesses when a frame is a multiple of
+ *      16 bytes and the bases (and rep_stride) are aligned, element-wise otherwise.
+ *      wan_window_gather: out = [rep][k1 - k0][B] windows, the model's input batch of windows [k0, k1); rep in {1, 2} writes the
+ *          doubled batch of a guided step in the same pass, copy r at out + r * rep_stride elements
+ *          (rep_stride >= (k1 - k0) * B * C * (2n + G) * hw).
+ *          replaces: per window two slices and a cat, a cat over the windows, and `torch.cat([latents] * 2)` (pipeline_wan.py:700).
+ *      wan_window_blend: pred = [K][B] window predictions (after guidance) -> out, the prediction for the state:
+ *          source frames   0                                        (the CoF mask, pipeline_wan.py:736)
+ *          ground_k        window k's grounding block, bits unchanged
+ *          target frame f  sum over the windows k that cover f, ascending, of alpha[k * Fs + f] * pred_k[f - a_k]
+ *          in float32 with SEPARATE roundings -- round(alpha * p) first, then acc = round(acc + round(alpha * p)) per further
+ *          window, one final rounding to `dtype`; never a fused multiply-add.  alpha: device float32 [K, Fs], the normalised
+ *          weights of videocof_amd.window_plan (exactly 1.0f where one window covers f: that frame is the window's prediction
+ *          unchanged). */
+#define WAN_WINDOW_MAX 64
+wan_status_t wan_window_gather(void* out, const void* state, int dtype, const int* starts, int K, int k0, int k1, int B, int C,
+                               int Fs, int n, int G, int64_t hw, int rep, int64_t rep_stride, void* stream);
+wan_status_t wan_window_blend(void* out, const void* pred, int dtype, const float* alpha, const int* starts, int K, int B, int C,
+                              int Fs, int n, int G, int64_t hw, void* stream);
+
 /* ===========================================================================
  * WanVAE (videox_fun/models/wan_vae.py).  Activations are CHANNELS-LAST bf16 [T, H, W, C].
  * ------------------------------------------------------------------------- */

@@ -219,6 +219,10 @@ SIGNATURES = {
                             c_int64, c_void_p]),
     "wan_solver_step": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float,
                                 c_float, c_float, c_float, c_float, c_float, c_int64, c_void_p]),
+    "wan_window_gather": (c_int, [c_void_p, c_void_p, c_int, POINTER(c_int), c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                  c_int64, c_int, c_int64, c_void_p]),
+    "wan_window_blend": (c_int, [c_void_p, c_void_p, c_int, c_void_p, POINTER(c_int), c_int, c_int, c_int, c_int, c_int, c_int,
+                                 c_int64, c_void_p]),
     "wan_gemm_bf16_batched": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64,
                                       c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "wan_embedding_rows": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p]),

@@ -1365,6 +1365,75 @@ def solver_step(sample: torch.Tensor, v: torch.Tensor, a_s: float, a_v: float, m
     return x0, prev
 
 
+# ------------------------------------------------------------------ temporal context windows (videocof_amd/windows.py)
+def _window_args(starts, frames: int, window: int, ground: int, name: str):
+    starts = [int(a) for a in starts]
+    if not starts:
+        raise ValueError(f"{name}: no windows")
+    return (ctypes.c_int * len(starts))(*starts), len(starts), int(frames), int(window), int(ground)
+
+
+@_on_tensor_device
+def window_gather(state: torch.Tensor, starts, window: int, ground: int, k0: int = 0, k1: Optional[int] = None, rep: int = 1,
+                  out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Windows [k0, k1) of the loop state [B, C, Fs + K*G + Fs, h, w] = [source | ground_0 .. ground_{K-1} | target] as the model's
+    input batch [rep * (k1 - k0) * B, C, n + G + n, h, w] in ONE launch (``wan_window_gather``): window k is
+    [source[a_k : a_k + n] | ground_k | target[a_k : a_k + n]], the batch reads [rep][window][sample].  fp32 or bf16."""
+    if state.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"window_gather: dtype {state.dtype} not supported (fp32 or bf16)")
+    _need(state, state.dtype, "window_gather.state")
+    if state.dim() != 5 or not state.is_contiguous():
+        raise ValueError(f"window_gather.state: a contiguous [B, C, F, h, w] tensor, got {tuple(state.shape)}")
+    B, C, Ftot, h, w = state.shape
+    K = len(starts)
+    if (Ftot - K * int(ground)) % 2 or Ftot - K * int(ground) < 2:
+        raise ValueError(f"window_gather.state: {Ftot} frames are not [Fs | {K} x {ground} | Fs]")
+    arr, K, Fs, n, G = _window_args(starts, (Ftot - K * int(ground)) // 2, window, ground, "window_gather")
+    k1 = K if k1 is None else int(k1)
+    nk = max(k1 - int(k0), 0)
+    shape = (int(rep) * nk * B, C, 2 * n + G, h, w)
+    if out is None:
+        out = torch.empty(shape, device=state.device, dtype=state.dtype)
+    elif tuple(out.shape) != shape or out.dtype != state.dtype or not out.is_contiguous() or out.device != state.device:
+        raise ValueError(f"window_gather.out: {out.dtype} {tuple(out.shape)} for {state.dtype} {shape}")
+    _lib.check(_lib.load().wan_window_gather(_p(out), _p(state), 0 if state.dtype == torch.float32 else 1, arr, K, int(k0), k1,
+                                             B, C, Fs, n, G, h * w, int(rep), nk * B * C * (2 * n + G) * h * w, _stream()),
+               "wan_window_gather")
+    return out
+
+
+@_on_tensor_device
+def window_blend(pred: torch.Tensor, alpha: torch.Tensor, starts, frames: int, ground: int,
+                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The K window predictions [K * B, C, n + G + n, h, w] (window-major, after guidance) as the prediction for the loop state
+    [B, C, Fs + K*G + Fs, h, w] in ONE launch (``wan_window_blend``): source frames 0, ground_k = window k's grounding block,
+    target frame f = sum_k alpha[k, f] * pred_k[f - a_k] over the covering windows in ascending k -- float32, every product and
+    sum rounded on its own.  ``alpha``: device float32 [K, Fs] (``window_plan(...).alpha``).  fp32 or bf16, in and out alike."""
+    if pred.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"window_blend: dtype {pred.dtype} not supported (fp32 or bf16)")
+    _need(pred, pred.dtype, "window_blend.pred")
+    _need(alpha, torch.float32, "window_blend.alpha")
+    if pred.dim() != 5 or not pred.is_contiguous():
+        raise ValueError(f"window_blend.pred: a contiguous [K * B, C, F, h, w] tensor, got {tuple(pred.shape)}")
+    KB, C, Fw, h, w = pred.shape
+    if (Fw - int(ground)) % 2 or Fw - int(ground) < 2:
+        raise ValueError(f"window_blend.pred: {Fw} frames are not [n | {ground} | n]")
+    arr, K, Fs, n, G = _window_args(starts, frames, (Fw - int(ground)) // 2, ground, "window_blend")
+    if KB % K:
+        raise ValueError(f"window_blend.pred: {KB} samples for {K} windows")
+    if tuple(alpha.shape) != (K, Fs) or not alpha.is_contiguous() or alpha.device != pred.device:
+        raise ValueError(f"window_blend.alpha: {tuple(alpha.shape)} on {alpha.device} for [{K}, {Fs}] on {pred.device}")
+    B = KB // K
+    shape = (B, C, 2 * Fs + K * G, h, w)
+    if out is None:
+        out = torch.empty(shape, device=pred.device, dtype=pred.dtype)
+    elif tuple(out.shape) != shape or out.dtype != pred.dtype or not out.is_contiguous() or out.device != pred.device:
+        raise ValueError(f"window_blend.out: {out.dtype} {tuple(out.shape)} for {pred.dtype} {shape}")
+    _lib.check(_lib.load().wan_window_blend(_p(out), _p(pred), 0 if pred.dtype == torch.float32 else 1, _p(alpha), arr, K, B, C,
+                                            Fs, n, G, h * w, _stream()), "wan_window_blend")
+    return out
+
+
 # ------------------------------------------------------------------ umT5 text encoder rows (SURVEY.md 8f-3)
 def _avail(t: torch.Tensor) -> int:
     """Elements from t's first element to the end of its storage."""

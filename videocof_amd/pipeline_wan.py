@@ -328,6 +328,11 @@ class WanPipeline:
         # plus the extensions tests/test_oracle_vs_reference.py lists.  compare=True: also return the reference's compare clip (save_side_by_side, fast_infer.py:183-206, as its writer's bytes) in
         # `compare_videos`, composed on the device from the uint8 source frames and the edit segment (video_io.compare_frames)
         compare = bool(switches.pop("compare", False))
+        # `temporal_window=None, temporal_overlap=16, window_batch=None` (PIXEL frames; window_batch in windows): denoise a clip longer
+        # than `temporal_window` as overlapping windows of that length, blended every step -- see `denoise_windows` below
+        temporal_window = switches.pop("temporal_window", None)
+        temporal_overlap = switches.pop("temporal_overlap", 16)
+        window_batch = switches.pop("window_batch", None)
         if switches:
             raise TypeError(f"__call__() got an unexpected keyword argument {next(iter(switches))!r}")
         compare_source = None
@@ -372,6 +377,15 @@ class WanPipeline:
 
         ratio = getattr(self.vae, "temporal_compression_ratio", 4)
         condition_count = 1 if source_frames == 1 else (source_frames - 1) // ratio + 1         # :630-631
+        window_latents = None
+        if temporal_window is not None:
+            from .windows import window_latent_frames, window_plan
+            window_latents = window_latent_frames(temporal_window, temporal_overlap, ratio)
+            if window_batch is not None and (isinstance(window_batch, bool) or not isinstance(window_batch, int) or window_batch < 1):
+                raise ValueError(f"window_batch={window_batch!r}: None (all windows in one forward) or a window count >= 1")
+            if video is None and source_latents is None and latents is None:
+                raise ValueError(f"temporal_window={temporal_window}: the windows are cut from a source clip; this call has none "
+                                 "(no `video`, `source_latents` or `latents`)")
         ground_latent_count = 0
         t_stage = self._stage("vae_encode")
         if cot:
@@ -385,7 +399,27 @@ class WanPipeline:
         self._stage("vae_encode", t_stage)
         B, _, Ftot, hl, wl = latents.shape
         ps = self.transformer.config.patch_size
-        seq_len = math.ceil((hl * wl) / (ps[1] * ps[2]) * Ftot)                                 # :686-689
+        plan = None                  # temporal context windows: None = the clip fits one window (or the option is off): today's path
+        if window_latents is not None:
+            if Ftot != 2 * condition_count + ground_latent_count:
+                raise ValueError(f"temporal_window={temporal_window}: latents of {Ftot} frames are not [source | grounding | target] = "
+                                 f"[{condition_count} | {ground_latent_count} | {condition_count}]")
+            plan = window_plan(condition_count, *window_latents)
+            plan = plan if plan.K > 1 else None
+        if plan is not None:
+            if capture_graph == "loop":
+                raise NotImplementedError("temporal_window with capture_graph='loop': the windowed loop is not recorded as one graph "
+                                          "(use capture_graph='step')")
+            if getattr(self.transformer, "teacache", None) is not None:
+                raise NotImplementedError("temporal_window with TeaCache: it keeps one residual per call and counts calls, and a "
+                                          "windowed step is several windows (and possibly several calls)")
+            # the loop state [source | ground_0 .. ground_{K-1} | target]: every window owns a grounding block (all start as the same
+            # noise: the random stream of the call is unchanged), the target is shared
+            cc, g1 = condition_count, condition_count + ground_latent_count
+            latents = torch.cat([latents[:, :, :cc]] + [latents[:, :, cc:g1]] * plan.K + [latents[:, :, g1:]], dim=2)
+        win_frames = Ftot if plan is None else 2 * plan.window + ground_latent_count            # frames of one forward
+        win_cc = condition_count if plan is None else plan.window                               # its source frames
+        seq_len = math.ceil((hl * wl) / (ps[1] * ps[2]) * win_frames)                           # :686-689
         self.transformer.num_inference_steps = num_inference_steps
         prev_cache = getattr(self.transformer, "cache_context", False)
         if hasattr(self.transformer, "cache_context"):
@@ -395,12 +429,12 @@ class WanPipeline:
         prev_skip = getattr(self.transformer, "skip_source_frames", 0)
         if hasattr(self.transformer, "skip_source_frames"):
             # noise_pred[:, :, :condition_count] is zeroed below (:736): the last block need not produce it
-            self.transformer.skip_source_frames = condition_count if skip_source_prediction else 0
+            self.transformer.skip_source_frames = win_cc if skip_source_prediction else 0
 
         # the CoF mask of :736 on the device: the unpatchify kernel writes zeros for the source frames
         prev_mask = getattr(self.transformer, "mask_source_frames", None)
         if prev_mask is not None:
-            self.transformer.mask_source_frames = condition_count
+            self.transformer.mask_source_frames = win_cc
         forward = self.transformer
         if capture_graph not in (False, True, "step", "loop"):
             raise ValueError(f"capture_graph={capture_graph!r}: False, True / 'step' (one hipGraph per forward) or 'loop' (the whole loop)")
@@ -470,9 +504,72 @@ class WanPipeline:
                         latents = out.pop("latents", latents)
             return latents
 
+        def denoise_windows(state, embeds):
+            """The same loop over a clip longer than the window (DESIGN.md "Temporal context windows").  `state` is
+            [source | ground_0 .. ground_{K-1} | target]; a step gathers the K windows [source[a:a+n] | ground_k | target[a:a+n]]
+            out of it (wan_window_gather, which also writes the doubled batch of a guided step), runs them as ONE forward of
+            K * B samples (`window_batch` windows per forward if set), applies guidance per window, blends the K predictions into
+            one for the state (wan_window_blend: CoF mask, each window's grounding, the weighted target) and steps the sampler
+            ONCE on the whole state.  The callback receives the state in this windowed layout."""
+            from . import ops
+            K, n, G = plan.K, plan.window, ground_latent_count
+            alpha = torch.from_numpy(plan.alpha).to(state.device)
+            per_call = K if window_batch is None else min(int(window_batch), K)
+            neg, pos = (embeds[:len(embeds) // 2], embeds[len(embeds) // 2:]) if do_cfg else ([], embeds)
+            can_suspend = hasattr(self.transformer, "_cfg_skip_suspended")
+            for i, t in enumerate(timesteps):
+                self.transformer.current_steps = i
+                if self._interrupt:
+                    continue
+                state = state.contiguous()
+                nB = state.shape[0]
+                preds = None
+                for k0 in range(0, K, per_call):
+                    k1 = min(k0 + per_call, K)
+                    nk = k1 - k0
+                    # cfg_skip as in `denoise`: a halved step runs the conditional windows only.  The model's own rule halves ANY
+                    # batch of two or more samples, which a batch of windows is: it stays suspended unless the literal order is asked for
+                    half = do_cfg and cfg_skip_now is not None and cfg_skip_now(2 * nk * nB)
+                    doubled = do_cfg and not (half and not self._cfg_skip_literal)
+                    x = ops.window_gather(state, plan.starts, n, G, k0, k1, rep=2 if doubled else 1)
+                    x = self.scheduler.scale_model_input(x, t)
+                    nb = x.shape[0]
+                    fsi = [n] * nb if use_rope_map else None
+                    gfi = [(n, n + G)] * nb if use_rope_map and cot else None
+                    suspend = can_suspend and not (half and doubled)
+                    if suspend:
+                        self.transformer._cfg_skip_suspended = True
+                    try:
+                        noise_pred = forward(x=x, context=(neg * nk + pos * nk) if doubled else pos * nk, t=t.expand(nb),
+                                             seq_len=seq_len, frame_split_indices=fsi, ground_frame_indices=gfi)
+                    finally:
+                        if suspend:
+                            self.transformer._cfg_skip_suspended = False
+                    if doubled:
+                        nu, nt = noise_pred.chunk(2)
+                        noise_pred = nu + self.guidance_scale * (nt - nu)
+                    if nk == K:
+                        preds = noise_pred
+                    else:
+                        if preds is None:
+                            preds = torch.empty((K * nB,) + tuple(noise_pred.shape[1:]), device=noise_pred.device, dtype=noise_pred.dtype)
+                        preds[k0 * nB:k1 * nB].copy_(noise_pred)
+                noise_pred = ops.window_blend(preds.contiguous(), alpha, plan.starts, plan.frames, G)
+                state = self.scheduler.step(noise_pred, t, state, **extra_step_kwargs, return_dict=False)[0]
+                if callback_on_step_end is not None:
+                    vals = {"latents": state, "prompt_embeds": prompt_embeds, "negative_prompt_embeds": negative_prompt_embeds}
+                    out = callback_on_step_end(self, i, t, {k: vals[k] for k in (callback_on_step_end_tensor_inputs or ())})
+                    if out:
+                        state = out.pop("latents", state)
+            # [source | ground_0 | target]: the shape a whole-clip call returns
+            Fs = plan.frames
+            return torch.cat([state[:, :, :Fs + G], state[:, :, Fs + K * G:]], dim=2)
+
         t_stage = self._stage("denoise_loop")
         try:
-            if capture_graph == "loop":
+            if plan is not None:
+                latents = denoise_windows(latents, in_prompt_embeds)
+            elif capture_graph == "loop":
                 # the whole loop as ONE hipGraph (videocof_amd.GraphedLoop): first call of a signature eager, second captures
                 if callback_on_step_end is not None:
                     raise NotImplementedError("capture_graph='loop' replays all steps in one launch: no per-step callback")
