@@ -621,6 +621,36 @@ wan_status_t wan_window_gather(void* out, const void* state, int dtype, const in
 wan_status_t wan_window_blend(void* out, const void* pred, int dtype, const float* alpha, const int* starts, int K, int B, int C,
                               int Fs, int n, int G, int64_t hw, void* stream);
 
+/* a17d  Spatial context windows: the same in three axes.  Each axis has its own plan in LATENT cells -- t_starts
+ *      [Kt] windows of n frames over Fs, y_starts [Ky] of th rows over H, x_starts [Kx] of tw columns over W; each as a17c's
+ *      `starts` (host array, ascending from 0, the last at extent - length, no gap, at most WAN_WINDOW_MAX) -- and the windows are
+ *      the K = Kt * Ky * Kx tiles of one shape, tile k = (kt * Ky + ky) * Kx + kx.  The loop's state is
+ *          state [B, C, Fs + Kt*G + Fs, H, W] = [source | ground_0 .. ground_{Kt-1} | target]
+ *      (every TEMPORAL window owns a grounding block; the spatial tiles of one temporal window share it) and tile (kt, ky, kx) is
+ *          [C, n + G + n, th, tw] = [source[a_t : a_t + n, tile] | ground_kt[:, tile] | target[a_t : a_t + n, tile]],
+ *      tile = rows [y0, y0 + th) x columns [x0, x0 + tw).  dtype 0 fp32, 1 bf16.  A tile row is tw elements at pitch W: the access
+ *      unit is the largest of 16, 8, 4 bytes or one element that divides (in bytes) the row length, the pitch, every x0, the frame
+ *      and tile-frame sizes, rep_stride and the base addresses, so no unit straddles a tile edge.
+ *      wan_tile_gather: out = [rep][k1 - k0][B] tiles, the model's input batch of tiles [k0, k1); rep and rep_stride as in
+ *          wan_window_gather (rep_stride >= (k1 - k0) * B * C * (2n + G) * th * tw elements).
+ *      wan_tile_blend: pred = [K][B] tile predictions (after guidance) -> out, the prediction for the state:
+ *          source frames                       0
+ *          grounding frame g of block kt and
+ *          target frame f, at (y, x)           the sum over the covering tiles only, in ascending k, of w * p, with
+ *                                              w = round(round(at * ay[ky * H + y]) * ax[kx * W + x]),
+ *                                              at = at_tab[kt * Fs + f] for target frames and 1.0f for grounding frames
+ *          in float32 with SEPARATE roundings -- the first term is round(w * p), every later one acc = round(acc + round(w * p)),
+ *          one final rounding to `dtype`; never a fused multiply-add.  at_tab [Kt, Fs], ay [Ky, H], ax [Kx, W]: device float32,
+ *          the three axes' videocof_amd.window_plan(...).alpha.  With Ky = Kx = 1 both entries compute what the a17c pair does.
+ *      Everything is validated on the host before anything is enqueued (each axis' plan, [k0, k1) inside K, rep / rep_stride,
+ *      row and frame counts below 2^31); a failure is WAN_ERR_INVALID. */
+wan_status_t wan_tile_gather(void* out, const void* state, int dtype, const int* t_starts, const int* y_starts, const int* x_starts,
+                             int Kt, int Ky, int Kx, int k0, int k1, int B, int C, int Fs, int H, int W, int n, int th, int tw,
+                             int G, int rep, int64_t rep_stride, void* stream);
+wan_status_t wan_tile_blend(void* out, const void* pred, int dtype, const float* at_tab, const float* ay, const float* ax,
+                            const int* t_starts, const int* y_starts, const int* x_starts, int Kt, int Ky, int Kx, int B, int C,
+                            int Fs, int H, int W, int n, int th, int tw, int G, void* stream);
+
 /* ===========================================================================
  * WanVAE (videox_fun/models/wan_vae.py).  Activations are CHANNELS-LAST bf16 [T, H, W, C].
  * ------------------------------------------------------------------------- */

@@ -13,7 +13,7 @@ Host side mirrors the reference's interface for this path only:
     videocof_amd.cache_utils                <- videox_fun/models/cache_utils.py (TeaCache, opt-in)
     videocof_amd.dist                       <- videox_fun/dist/{fuser,wan_xfuser}.py (Ulysses on RCCL)
     videocof_amd.video_io                   <- fast_infer.py load_video_frames + videox_fun/utils/utils.py save_videos_grid's byte conversion
-    videocof_amd.windows                    (no counterpart) temporal context windows: clips longer than the trained length, opt-in
+    videocof_amd.windows                    (no counterpart) temporal and spatial context windows: clips longer / frames larger than trained, opt-in
 
 Device arithmetic lives in ``libwan_hip.so`` (csrc/, C ABI in include/wan_hip.h).
 """
@@ -34,5 +34,6 @@ from .video_io import grid_frames, compare_frames, reference_grid_frames, refere
 from .video_io import yuv_matrix, yuv_to_frames, frames_to_yuv, reference_yuv_to_frames, reference_frames_to_yuv  # noqa: F401
 from .video_io import YuvClip, read_y4m, load_y4m_frames, write_y4m  # noqa: F401
 from .windows import WindowPlan, window_plan, window_latent_frames, reference_window_gather, reference_window_blend  # noqa: F401
+from .windows import TilePlan, spatial_window_cells, reference_tile_gather, reference_tile_blend  # noqa: F401
 
 __version__ = "0.1.0"

@@ -223,6 +223,10 @@ SIGNATURES = {
                                   c_int64, c_int, c_int64, c_void_p]),
     "wan_window_blend": (c_int, [c_void_p, c_void_p, c_int, c_void_p, POINTER(c_int), c_int, c_int, c_int, c_int, c_int, c_int,
                                  c_int64, c_void_p]),
+    "wan_tile_gather": (c_int, [c_void_p, c_void_p, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int)] + [c_int] * 15
+                                + [c_int64, c_void_p]),
+    "wan_tile_blend": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, POINTER(c_int), POINTER(c_int),
+                               POINTER(c_int)] + [c_int] * 12 + [c_void_p]),
     "wan_gemm_bf16_batched": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64,
                                       c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "wan_embedding_rows": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p]),

@@ -1434,6 +1434,89 @@ def window_blend(pred: torch.Tensor, alpha: torch.Tensor, starts, frames: int, g
     return out
 
 
+# ------------------------------------------------------------------ spatial context windows (videocof_amd/windows.py, TilePlan)
+def _tile_starts(starts, name: str):
+    if len(starts) != 3:
+        raise ValueError(f"{name}: starts = (t_starts, y_starts, x_starts), got {len(starts)} entries")
+    axes = [[int(a) for a in s] for s in starts]
+    if not all(axes):
+        raise ValueError(f"{name}: an axis without windows")
+    return [(ctypes.c_int * len(a))(*a) for a in axes], [len(a) for a in axes]
+
+
+@_on_tensor_device
+def tile_gather(state: torch.Tensor, starts, tile, ground: int, k0: int = 0, k1: Optional[int] = None, rep: int = 1,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Tiles [k0, k1) of the loop state [B, C, Fs + Kt*G + Fs, H, W] = [source | ground_0 .. ground_{Kt-1} | target] as the model's
+    input batch [rep * (k1 - k0) * B, C, n + G + n, th, tw] in ONE launch (``wan_tile_gather``).  ``starts`` = (t_starts, y_starts,
+    x_starts), ``tile`` = (n, th, tw), all in latent cells (``TilePlan``); tile k = (kt * Ky + ky) * Kx + kx is
+    [source[a_t : a_t + n, tile] | ground_kt[:, tile] | target[a_t : a_t + n, tile]].  fp32 or bf16."""
+    if state.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"tile_gather: dtype {state.dtype} not supported (fp32 or bf16)")
+    _need(state, state.dtype, "tile_gather.state")
+    if state.dim() != 5 or not state.is_contiguous():
+        raise ValueError(f"tile_gather.state: a contiguous [B, C, F, H, W] tensor, got {tuple(state.shape)}")
+    B, C, Ftot, H, W = state.shape
+    arrs, (Kt, Ky, Kx) = _tile_starts(starts, "tile_gather")
+    n, th, tw = (int(v) for v in tile)
+    G = int(ground)
+    if (Ftot - Kt * G) % 2 or Ftot - Kt * G < 2:
+        raise ValueError(f"tile_gather.state: {Ftot} frames are not [Fs | {Kt} x {G} | Fs]")
+    Fs = (Ftot - Kt * G) // 2
+    k1 = Kt * Ky * Kx if k1 is None else int(k1)
+    nk = max(k1 - int(k0), 0)
+    shape = (int(rep) * nk * B, C, 2 * n + G, th, tw)
+    if min(shape[2:]) < 1:
+        raise ValueError(f"tile_gather: tile {(n, th, tw)} with {G} grounding frames")
+    if out is None:
+        out = torch.empty(shape, device=state.device, dtype=state.dtype)
+    elif tuple(out.shape) != shape or out.dtype != state.dtype or not out.is_contiguous() or out.device != state.device:
+        raise ValueError(f"tile_gather.out: {out.dtype} {tuple(out.shape)} for {state.dtype} {shape}")
+    _lib.check(_lib.load().wan_tile_gather(_p(out), _p(state), 0 if state.dtype == torch.float32 else 1, *arrs, Kt, Ky, Kx, int(k0), k1,
+                                           B, C, Fs, H, W, n, th, tw, G, int(rep), nk * B * C * (2 * n + G) * th * tw, _stream()),
+               "wan_tile_gather")
+    return out
+
+
+@_on_tensor_device
+def tile_blend(pred: torch.Tensor, tables, starts, extent, ground: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The K = Kt * Ky * Kx tile predictions [K * B, C, n + G + n, th, tw] (tile-major, after guidance) as the prediction for the
+    loop state [B, C, Fs + Kt*G + Fs, H, W] in ONE launch (``wan_tile_blend``): source frames 0; a grounding frame of block kt and a
+    target frame at (y, x) = the sum over the covering tiles in ascending k of w * p, w = (at * ay) * ax -- float32, every product
+    and sum rounded on its own (at = 1 for grounding frames).  ``tables`` = (at [Kt, Fs], ay [Ky, H], ax [Kx, W]): device float32,
+    the three axes' ``window_plan(...).alpha``; ``starts`` = (t_starts, y_starts, x_starts); ``extent`` = (Fs, H, W)."""
+    if pred.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"tile_blend: dtype {pred.dtype} not supported (fp32 or bf16)")
+    _need(pred, pred.dtype, "tile_blend.pred")
+    if pred.dim() != 5 or not pred.is_contiguous():
+        raise ValueError(f"tile_blend.pred: a contiguous [K * B, C, F, th, tw] tensor, got {tuple(pred.shape)}")
+    KB, C, Fw, th, tw = pred.shape
+    G = int(ground)
+    if (Fw - G) % 2 or Fw - G < 2:
+        raise ValueError(f"tile_blend.pred: {Fw} frames are not [n | {G} | n]")
+    n = (Fw - G) // 2
+    arrs, (Kt, Ky, Kx) = _tile_starts(starts, "tile_blend")
+    Fs, H, W = (int(v) for v in extent)
+    K = Kt * Ky * Kx
+    if KB % K:
+        raise ValueError(f"tile_blend.pred: {KB} samples for {K} tiles")
+    if len(tables) != 3:
+        raise ValueError(f"tile_blend: tables = (at, ay, ax), got {len(tables)} entries")
+    for name, tab, shape in zip(("at", "ay", "ax"), tables, ((Kt, Fs), (Ky, H), (Kx, W))):
+        _need(tab, torch.float32, f"tile_blend.{name}")
+        if tuple(tab.shape) != shape or not tab.is_contiguous() or tab.device != pred.device:
+            raise ValueError(f"tile_blend.{name}: {tuple(tab.shape)} on {tab.device} for {list(shape)} on {pred.device}")
+    B = KB // K
+    shape = (B, C, 2 * Fs + Kt * G, H, W)
+    if out is None:
+        out = torch.empty(shape, device=pred.device, dtype=pred.dtype)
+    elif tuple(out.shape) != shape or out.dtype != pred.dtype or not out.is_contiguous() or out.device != pred.device:
+        raise ValueError(f"tile_blend.out: {out.dtype} {tuple(out.shape)} for {pred.dtype} {shape}")
+    _lib.check(_lib.load().wan_tile_blend(_p(out), _p(pred), 0 if pred.dtype == torch.float32 else 1, *[_p(t) for t in tables], *arrs,
+                                          Kt, Ky, Kx, B, C, Fs, H, W, n, th, tw, G, _stream()), "wan_tile_blend")
+    return out
+
+
 # ------------------------------------------------------------------ umT5 text encoder rows (SURVEY.md 8f-3)
 def _avail(t: torch.Tensor) -> int:
     """Elements from t's first element to the end of its storage."""

@@ -333,6 +333,11 @@ class WanPipeline:
         temporal_window = switches.pop("temporal_window", None)
         temporal_overlap = switches.pop("temporal_overlap", 16)
         window_batch = switches.pop("window_batch", None)
+        # `spatial_window=None, spatial_overlap=(96, 128)` ((rows, columns) in PIXELS): denoise frames larger than `spatial_window` as
+        # overlapping tiles of that size, blended every step; combines with `temporal_window`, `window_batch` then
+        # counts tiles.  The default overlap is a guess: no real checkpoint has been run with it.  Opt-in and lossy; no quality claim.
+        spatial_window = switches.pop("spatial_window", None)
+        spatial_overlap = switches.pop("spatial_overlap", (96, 128))
         if switches:
             raise TypeError(f"__call__() got an unexpected keyword argument {next(iter(switches))!r}")
         compare_source = None
@@ -377,14 +382,22 @@ class WanPipeline:
 
         ratio = getattr(self.vae, "temporal_compression_ratio", 4)
         condition_count = 1 if source_frames == 1 else (source_frames - 1) // ratio + 1         # :630-631
-        window_latents = None
+        window_latents = tile_cells = None
         if temporal_window is not None:
             from .windows import window_latent_frames, window_plan
             window_latents = window_latent_frames(temporal_window, temporal_overlap, ratio)
+        if spatial_window is not None:
+            from .windows import TilePlan, spatial_window_cells, window_plan
+            tile_cells = spatial_window_cells(spatial_window, spatial_overlap,
+                                              getattr(getattr(self.vae, "config", None), "spatial_compression_ratio", 8),
+                                              self.transformer.config.patch_size[1])
+        for name, option in (("temporal_window", temporal_window), ("spatial_window", spatial_window)):
+            if option is None:
+                continue
             if window_batch is not None and (isinstance(window_batch, bool) or not isinstance(window_batch, int) or window_batch < 1):
                 raise ValueError(f"window_batch={window_batch!r}: None (all windows in one forward) or a window count >= 1")
             if video is None and source_latents is None and latents is None:
-                raise ValueError(f"temporal_window={temporal_window}: the windows are cut from a source clip; this call has none "
+                raise ValueError(f"{name}={option}: the windows are cut from a source clip; this call has none "
                                  "(no `video`, `source_latents` or `latents`)")
         ground_latent_count = 0
         t_stage = self._stage("vae_encode")
@@ -406,20 +419,36 @@ class WanPipeline:
                                  f"[{condition_count} | {ground_latent_count} | {condition_count}]")
             plan = window_plan(condition_count, *window_latents)
             plan = plan if plan.K > 1 else None
-        if plan is not None:
+        tiles = None                 # spatial context windows: None = every frame fits one tile (or the option is off): the path above
+        if tile_cells is not None:
+            if Ftot != 2 * condition_count + ground_latent_count:
+                raise ValueError(f"spatial_window={spatial_window}: latents of {Ftot} frames are not [source | grounding | target] = "
+                                 f"[{condition_count} | {ground_latent_count} | {condition_count}]")
+            (tile_h, tile_w), (over_h, over_w) = tile_cells
+            plan_y, plan_x = window_plan(hl, tile_h, over_h), window_plan(wl, tile_w, over_w)
+            if plan_y.K * plan_x.K > 1:
+                # the t axis: the temporal windows, or one window of the whole clip without them
+                tiles = TilePlan(plan if plan is not None else window_plan(condition_count, max(condition_count, 2), 0), plan_y, plan_x)
+        windows = tiles if tiles is not None else plan
+        if windows is not None:
+            option = "spatial_window" if tiles is not None else "temporal_window"
             if capture_graph == "loop":
-                raise NotImplementedError("temporal_window with capture_graph='loop': the windowed loop is not recorded as one graph "
+                raise NotImplementedError(f"{option} with capture_graph='loop': the windowed loop is not recorded as one graph "
                                           "(use capture_graph='step')")
             if getattr(self.transformer, "teacache", None) is not None:
-                raise NotImplementedError("temporal_window with TeaCache: it keeps one residual per call and counts calls, and a "
+                raise NotImplementedError(f"{option} with TeaCache: it keeps one residual per call and counts calls, and a "
                                           "windowed step is several windows (and possibly several calls)")
-            # the loop state [source | ground_0 .. ground_{K-1} | target]: every window owns a grounding block (all start as the same
-            # noise: the random stream of the call is unchanged), the target is shared
+            # the loop state [source | ground_0 .. ground_{Kt-1} | target]: every temporal window owns a grounding block (all start as
+            # the same noise: the random stream of the call is unchanged; the spatial tiles of a temporal window share its block),
+            # the target is shared
             cc, g1 = condition_count, condition_count + ground_latent_count
-            latents = torch.cat([latents[:, :, :cc]] + [latents[:, :, cc:g1]] * plan.K + [latents[:, :, g1:]], dim=2)
-        win_frames = Ftot if plan is None else 2 * plan.window + ground_latent_count            # frames of one forward
-        win_cc = condition_count if plan is None else plan.window                               # its source frames
-        seq_len = math.ceil((hl * wl) / (ps[1] * ps[2]) * win_frames)                           # :686-689
+            blocks = tiles.Kt if tiles is not None else plan.K
+            latents = torch.cat([latents[:, :, :cc]] + [latents[:, :, cc:g1]] * blocks + [latents[:, :, g1:]], dim=2)
+        win_n = None if windows is None else tiles.t.window if tiles is not None else plan.window       # source frames of one window
+        win_frames = Ftot if windows is None else 2 * win_n + ground_latent_count                # frames of one forward
+        win_cc = condition_count if windows is None else win_n                                   # its source frames
+        win_hw = hl * wl if tiles is None else tiles.y.window * tiles.x.window                   # its latent cells per frame
+        seq_len = math.ceil(win_hw / (ps[1] * ps[2]) * win_frames)                               # :686-689
         self.transformer.num_inference_steps = num_inference_steps
         prev_cache = getattr(self.transformer, "cache_context", False)
         if hasattr(self.transformer, "cache_context"):
@@ -510,10 +539,22 @@ class WanPipeline:
             out of it (wan_window_gather, which also writes the doubled batch of a guided step), runs them as ONE forward of
             K * B samples (`window_batch` windows per forward if set), applies guidance per window, blends the K predictions into
             one for the state (wan_window_blend: CoF mask, each window's grounding, the weighted target) and steps the sampler
-            ONCE on the whole state.  The callback receives the state in this windowed layout."""
+            ONCE on the whole state.  The callback receives the state in this windowed layout.
+            With spatial context windows the windows are the K = Kt * Ky * Kx tiles of `tiles`, cut and blended by
+            wan_tile_gather / wan_tile_blend; the state has one grounding block per TEMPORAL window."""
             from . import ops
-            K, n, G = plan.K, plan.window, ground_latent_count
-            alpha = torch.from_numpy(plan.alpha).to(state.device)
+            G = ground_latent_count
+            if tiles is None:
+                K, Kt, n = plan.K, plan.K, plan.window
+                alpha = torch.from_numpy(plan.alpha).to(state.device)
+                gather = lambda s, k0, k1, rep: ops.window_gather(s, plan.starts, n, G, k0, k1, rep=rep)
+                blend = lambda p: ops.window_blend(p, alpha, plan.starts, plan.frames, G)
+            else:
+                K, Kt, n = tiles.K, tiles.Kt, tiles.t.window
+                starts = (tiles.t.starts, tiles.y.starts, tiles.x.starts)
+                tables = tuple(torch.from_numpy(axis.alpha).to(state.device) for axis in (tiles.t, tiles.y, tiles.x))
+                gather = lambda s, k0, k1, rep: ops.tile_gather(s, starts, tiles.shape, G, k0, k1, rep=rep)
+                blend = lambda p: ops.tile_blend(p, tables, starts, tiles.extent, G)
             per_call = K if window_batch is None else min(int(window_batch), K)
             neg, pos = (embeds[:len(embeds) // 2], embeds[len(embeds) // 2:]) if do_cfg else ([], embeds)
             can_suspend = hasattr(self.transformer, "_cfg_skip_suspended")
@@ -531,7 +572,7 @@ class WanPipeline:
                     # batch of two or more samples, which a batch of windows is: it stays suspended unless the literal order is asked for
                     half = do_cfg and cfg_skip_now is not None and cfg_skip_now(2 * nk * nB)
                     doubled = do_cfg and not (half and not self._cfg_skip_literal)
-                    x = ops.window_gather(state, plan.starts, n, G, k0, k1, rep=2 if doubled else 1)
+                    x = gather(state, k0, k1, 2 if doubled else 1)
                     x = self.scheduler.scale_model_input(x, t)
                     nb = x.shape[0]
                     fsi = [n] * nb if use_rope_map else None
@@ -554,7 +595,7 @@ class WanPipeline:
                         if preds is None:
                             preds = torch.empty((K * nB,) + tuple(noise_pred.shape[1:]), device=noise_pred.device, dtype=noise_pred.dtype)
                         preds[k0 * nB:k1 * nB].copy_(noise_pred)
-                noise_pred = ops.window_blend(preds.contiguous(), alpha, plan.starts, plan.frames, G)
+                noise_pred = blend(preds.contiguous())
                 state = self.scheduler.step(noise_pred, t, state, **extra_step_kwargs, return_dict=False)[0]
                 if callback_on_step_end is not None:
                     vals = {"latents": state, "prompt_embeds": prompt_embeds, "negative_prompt_embeds": negative_prompt_embeds}
@@ -562,12 +603,12 @@ class WanPipeline:
                     if out:
                         state = out.pop("latents", state)
             # [source | ground_0 | target]: the shape a whole-clip call returns
-            Fs = plan.frames
-            return torch.cat([state[:, :, :Fs + G], state[:, :, Fs + K * G:]], dim=2)
+            Fs = condition_count
+            return torch.cat([state[:, :, :Fs + G], state[:, :, Fs + Kt * G:]], dim=2)
 
         t_stage = self._stage("denoise_loop")
         try:
-            if plan is not None:
+            if windows is not None:
                 latents = denoise_windows(latents, in_prompt_embeds)
             elif capture_graph == "loop":
                 # the whole loop as ONE hipGraph (videocof_amd.GraphedLoop): first call of a signature eager, second captures

@@ -724,8 +724,21 @@ class WanTransformer3DModel(nn.Module):
 
     # ------------------------------------------------------------------ pieces of forward
     def _time_embed(self, t: torch.Tensor):
-        w = self._w
         s = sinusoidal_embedding_1d(self.freq_dim, t.to(self._device)).float()
+        if s.shape[0] > self._TIME_EMBED_ROWS:
+            # A sample's embedding must not depend on its batch mates (a batch of context windows is compared with its windows run
+            # one by one, tests/test_gpu_tiles.py), but torch.addmm's does once the BLAS picks another kernel for more rows:
+            # measured on an MI355X, the rows of 1 .. 16 samples carry the same bits and those of 17 differ in the last fp32 bit,
+            # which the bf16 kernels behind it turn into 1e-3.  Larger batches go through in groups of 16 rows: the calls a batch of
+            # up to 16 makes, so nothing changes for those.  No host synchronisation: capturable as before.
+            parts = [self._time_embed_rows(s[i:i + self._TIME_EMBED_ROWS]) for i in range(0, s.shape[0], self._TIME_EMBED_ROWS)]
+            return torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts])
+        return self._time_embed_rows(s)
+
+    _TIME_EMBED_ROWS = 16
+
+    def _time_embed_rows(self, s: torch.Tensor):
+        w = self._w
         e = torch.addmm(w["tm_b2"], torch.nn.functional.silu(torch.addmm(w["tm_b0"], s, w["tm_w0"].t())), w["tm_w2"].t())
         e0 = torch.addmm(w["tp_b"], torch.nn.functional.silu(e), w["tp_w"].t()).unflatten(1, (6, self.dim))
         return e, e0          # fp32 [B,C], [B,6,C]

@@ -5,6 +5,10 @@ runs the model on the windows, blends their predictions into one prediction for 
 ("Temporal context windows").  ``window_plan`` fixes where the windows start and with which weight each of them
 enters a frame; ``reference_window_gather`` / ``reference_window_blend`` state what ``wan_window_gather`` / ``wan_window_blend``
 compute, in plain torch (the blend in float32 with separately rounded products and sums: the kernel's bits).
+
+Spatial context windows are the same in three axes: a ``TilePlan`` holds one ``WindowPlan`` per axis (t, y, x, all
+in latent cells), the windows are its K = Kt * Ky * Kx tiles of one shape, and ``reference_tile_gather`` / ``reference_tile_blend``
+state what ``wan_tile_gather`` / ``wan_tile_blend`` compute.
 """
 from __future__ import annotations
 
@@ -14,7 +18,8 @@ from typing import Optional, Tuple
 import numpy as np
 import torch
 
-__all__ = ["WindowPlan", "window_plan", "window_latent_frames", "reference_window_gather", "reference_window_blend"]
+__all__ = ["WindowPlan", "window_plan", "window_latent_frames", "reference_window_gather", "reference_window_blend",
+           "TilePlan", "spatial_window_cells", "reference_tile_gather", "reference_tile_blend"]
 
 
 @dataclass(frozen=True)
@@ -124,4 +129,144 @@ def reference_window_blend(pred: torch.Tensor, plan: WindowPlan, ground: int) ->
             term = alpha[k, f].to(pred.device) * p[k][:, :, n + G + f - plan.starts[k]].float()
             acc = term if acc is None else acc + term
         out[:, :, Fs + K * G + f] = acc.to(pred.dtype)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ spatial context windows
+@dataclass(frozen=True)
+class TilePlan:
+    """Windows in three axes: ``t``, ``y``, ``x`` are the axes' ``window_plan(extent, window, overlap)`` in LATENT cells (an axis
+    whose extent fits its window has one window of the whole extent).  The K = Kt * Ky * Kx tiles all have the shape
+    ``(n, th, tw)``; tile ``k = (kt * Ky + ky) * Kx + kx``.  Its weight at latent position (f, y, x) is
+    ``round(round(at[kt][f] * ay[ky][y]) * ax[kx][x])`` in float32 (``at := 1`` for grounding frames): ``at[kt][f]`` exactly when
+    Ky = Kx = 1, exactly 1 where one tile covers the position."""
+    t: WindowPlan
+    y: WindowPlan
+    x: WindowPlan
+
+    @property
+    def Kt(self) -> int:
+        return self.t.K
+
+    @property
+    def Ky(self) -> int:
+        return self.y.K
+
+    @property
+    def Kx(self) -> int:
+        return self.x.K
+
+    @property
+    def K(self) -> int:
+        return self.t.K * self.y.K * self.x.K
+
+    @property
+    def shape(self) -> Tuple[int, int, int]:
+        """(n, th, tw): latent frames, rows and columns of every tile."""
+        return self.t.window, self.y.window, self.x.window
+
+    @property
+    def extent(self) -> Tuple[int, int, int]:
+        """(Fs, H, W): latent frames, rows and columns of the clip."""
+        return self.t.frames, self.y.frames, self.x.frames
+
+    def index(self, kt: int, ky: int, kx: int) -> int:
+        return (kt * self.Ky + ky) * self.Kx + kx
+
+    def split(self, k: int) -> Tuple[int, int, int]:
+        """(kt, ky, kx) of tile k."""
+        if not 0 <= k < self.K:
+            raise IndexError(f"tile {k} of {self.K}")
+        return k // (self.Ky * self.Kx), (k // self.Kx) % self.Ky, k % self.Kx
+
+    def origin(self, k: int) -> Tuple[int, int, int]:
+        """(a_t, y0, x0): where tile k starts."""
+        kt, ky, kx = self.split(k)
+        return self.t.starts[kt], self.y.starts[ky], self.x.starts[kx]
+
+    def weights(self, k: int, ground: bool = False) -> np.ndarray:
+        """float32 [Fs, H, W] ([H, W] for grounding frames): tile k's weight at every position of the clip, 0 outside the tile."""
+        kt, ky, kx = self.split(k)
+        ay, ax = self.y.alpha[ky], self.x.alpha[kx]
+        if ground:
+            return (np.float32(1.0) * ay)[:, None] * ax[None, :]
+        return (self.t.alpha[kt][:, None] * ay[None, :])[:, :, None] * ax[None, None, :]      # float32: each product rounded on its own
+
+    def covering(self, f: int, y: int, x: int) -> Tuple[int, ...]:
+        """The tiles that cover latent position (f, y, x), ascending."""
+        return tuple(self.index(kt, ky, kx) for kt in self.t.covering(f) for ky in self.y.covering(y) for kx in self.x.covering(x))
+
+
+def spatial_window_cells(spatial_window, spatial_overlap, ratio: int = 8, patch: int = 2) -> Tuple[Tuple[int, int], Tuple[int, int]]:
+    """The pipeline's ``spatial_window`` = (h, w) / ``spatial_overlap`` = (oy, ox), both in PIXELS, as latent cells:
+    ``((th, tw), (oy, ox))``.  Each side of ``spatial_window`` must be a multiple of ratio * patch (a tile is patchified on its
+    own) and at least that; each side of ``spatial_overlap`` a non-negative multiple of ``ratio`` that leaves the tiles a stride."""
+    ratio, patch = int(ratio), int(patch)
+    pairs = []
+    for name, v in (("spatial_window", spatial_window), ("spatial_overlap", spatial_overlap)):
+        if isinstance(v, (str, bytes)) or not hasattr(v, "__len__") or len(v) != 2:
+            raise ValueError(f"{name}={v!r} is not a pair (rows, columns) of pixel counts")
+        for e in v:
+            if isinstance(e, bool) or not isinstance(e, (int, np.integer)):
+                raise ValueError(f"{name}={tuple(v)!r}: {e!r} is not an integer pixel count")
+        pairs.append((int(v[0]), int(v[1])))
+    (wh, ww), (oh, ow) = pairs
+    unit = ratio * patch
+    for side in (wh, ww):
+        if side < unit or side % unit != 0:
+            raise ValueError(f"spatial_window={(wh, ww)}: {side} must be a positive multiple of {unit} pixels (the VAE's spatial ratio "
+                             f"{ratio} times the patch {patch})")
+    for side in (oh, ow):
+        if side < 0 or side % ratio != 0:
+            raise ValueError(f"spatial_overlap={(oh, ow)}: {side} must be a non-negative multiple of the VAE's spatial ratio {ratio}")
+    cells, over = (wh // ratio, ww // ratio), (oh // ratio, ow // ratio)
+    for n, o, side in zip(cells, over, (oh, ow)):
+        if o > n - 1:
+            raise ValueError(f"spatial_overlap={(oh, ow)}: {side} pixels ({o} cells) leave tiles of spatial_window={(wh, ww)} "
+                             f"({cells[0]} x {cells[1]} cells) no stride: at most {ratio * (n - 1)}")
+    return cells, over
+
+
+def reference_tile_gather(state: torch.Tensor, plan: TilePlan, ground: int, k0: int = 0, k1: Optional[int] = None,
+                          rep: int = 1) -> torch.Tensor:
+    """``wan_tile_gather`` in torch: tiles [k0, k1) of ``state`` [B, C, Fs + Kt*G + Fs, H, W] as the batch
+    [rep][k1 - k0][B] x [C, n + G + n, th, tw]; the spatial tiles of one temporal window share its grounding block."""
+    (n, th, tw), (Fs, _, _), G, Kt = plan.shape, plan.extent, int(ground), plan.Kt
+    k1 = plan.K if k1 is None else k1
+    tiles = []
+    for k in range(k0, k1):
+        kt = plan.split(k)[0]
+        a, y0, x0 = plan.origin(k)
+        s = state[:, :, :, y0:y0 + th, x0:x0 + tw]
+        tiles.append(torch.cat([s[:, :, a:a + n], s[:, :, Fs + kt * G:Fs + (kt + 1) * G],
+                                s[:, :, Fs + Kt * G + a:Fs + Kt * G + a + n]], dim=2))
+    return torch.cat(tiles * int(rep))
+
+
+def reference_tile_blend(pred: torch.Tensor, plan: TilePlan, ground: int) -> torch.Tensor:
+    """``wan_tile_blend`` in torch: ``pred`` [K*B, C, n + G + n, th, tw] (tile-major) -> the prediction for the state
+    [B, C, Fs + Kt*G + Fs, H, W].  Source frames 0; grounding frame g of block kt and target frame f at (y, x): the sum over the
+    covering tiles in ascending k of w * p, in float32 with the first term round(w * p) and every later one
+    acc = round(acc + round(w * p)); one rounding to ``pred.dtype``."""
+    (n, th, tw), (Fs, H, W), G, Kt, K = plan.shape, plan.extent, int(ground), plan.Kt, plan.K
+    B = pred.shape[0] // K
+    p = pred.reshape(K, B, *pred.shape[1:])
+    acc = torch.zeros(B, pred.shape[1], Kt * G + Fs, H, W, dtype=torch.float32, device=pred.device)
+    seen = torch.zeros(Kt * G + Fs, H, W, dtype=torch.bool, device=pred.device)
+
+    def add(frames, ys, xs, w, x):
+        term = w.to(pred.device) * x.float()
+        region, s = acc[:, :, frames, ys, xs], seen[frames, ys, xs]
+        region.copy_(torch.where(s, region + term, term))
+        s.fill_(True)
+
+    for k in range(K):
+        kt = plan.split(k)[0]
+        a, y0, x0 = plan.origin(k)
+        ys, xs = slice(y0, y0 + th), slice(x0, x0 + tw)
+        if G:
+            add(slice(kt * G, (kt + 1) * G), ys, xs, torch.from_numpy(plan.weights(k, ground=True)[ys, xs]), p[k][:, :, n:n + G])
+        add(slice(Kt * G + a, Kt * G + a + n), ys, xs, torch.from_numpy(plan.weights(k)[a:a + n, ys, xs]), p[k][:, :, n + G:])
+    out = torch.zeros(B, pred.shape[1], 2 * Fs + Kt * G, H, W, dtype=pred.dtype, device=pred.device)
+    out[:, :, Fs:] = acc.to(pred.dtype)
     return out
