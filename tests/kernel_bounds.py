@@ -4,11 +4,12 @@ A rel-L2 over a whole tensor does not see a wrong tile, a wrong row segment or e
 here every element is held against a bound of its OWN, derived from the number formats and the operation count of the kernel
 -- nothing below is fitted to what a kernel returns.  Everything is evaluated in fp64 on the CPU.
 
-Unit roundoffs (round to nearest even, p significand bits -> u = 2^-p):  bf16 p = 8 -> 2^-8;  fp32 p = 24 -> 2^-24.
+Unit roundoffs (round to nearest even, p significand bits -> u = 2^-p):  bf16 p = 8 -> 2^-8;  fp32 p = 24 -> 2^-24;  e4m3 p = 4 -> 2^-4.
 A truncating conversion has 2 u; the bounds allow u for the output rounding, so truncation is rejected.
 
-Plain module: no fixtures, no pytest hooks.  tests/test_kernel_bounds_host.py checks it on the CPU (honest emulations inside,
-mutants outside); tests/test_gpu_kernel_elementwise.py and tests/test_gpu_vae_elementwise.py use it on the kernels.
+Plain module: no fixtures, no pytest hooks.  tests/test_kernel_bounds_host.py, tests/test_vae_bounds_host.py and
+tests/test_fp8_bounds_host.py check it on the CPU (honest emulations inside, mutants outside); tests/test_gpu_kernel_elementwise.py,
+tests/test_gpu_vae_elementwise.py and tests/test_gpu_fp8_elementwise.py use it on the kernels.
 """
 import math
 
@@ -147,6 +148,12 @@ def attention_bound(q, k, v, scale, k_len=None):
       adds them up (16 u): 20 u on the numerator, 20 u on the denominator, 2 u for the division = 42, taken as 64:
       f = 2^-24 (4 Lk + 2 (Lk / 64 + 1) + 4 + 64).
     * 2^-8 |ref|: the output rounding."""
+    ref, p, s, f, pv = _attention_parts(q, k, v, scale, k_len)
+    return ref, U_BF16 * ref.abs() + (ATTN_C_P * U_BF16 + s + f) * pv
+
+
+def _attention_parts(q, k, v, scale, k_len=None):
+    """(ref, p, s_i [Lq, 1], f, p @ |v|) of attention_bound's docstring, shared with the fp8 forms below."""
     ref, p = attention_ref(q, k, v, scale, k_len)
     qd, kd, vd = _d(q), _d(k), _d(v)
     if k_len is not None:
@@ -156,7 +163,7 @@ def attention_bound(q, k, v, scale, k_len=None):
     d = 2.0 ** -23 * (130.0 * S + 2.0)
     s = 2.0 * (torch.exp2(d) - 1.0)
     f = U_F32 * (4.0 * Lk + 2.0 * (Lk / 64.0 + 1.0) + 4.0 + 64.0)
-    return ref, U_BF16 * ref.abs() + (ATTN_C_P * U_BF16 + s + f) * (p @ vd.abs())
+    return ref, p, s, f, p @ vd.abs()
 
 
 HEAVY = 400.0
@@ -216,6 +223,12 @@ def ln_modulate_bound(x, scale_rows, shift_rows, add_one, eps):
       terms, relative error dim u, halved by the square root and doubled again by the rounding of each (x - mean) and its square,
       + division, eps add, v_rsq_f32 (1 ulp): (dim + 8) u relative on z;
     * four elementwise roundings (x - mean, * rstd, * a, + c)."""
+    ref, e32 = _ln_modulate_parts(x, scale_rows, shift_rows, add_one, eps)
+    return ref, U_BF16 * ref.abs() + e32
+
+
+def _ln_modulate_parts(x, scale_rows, shift_rows, add_one, eps):
+    """(ref, the fp32 part of ln_modulate_bound: everything but the output rounding)."""
     x = _d(x)
     dim = x.shape[-1]
     a = (1.0 if add_one else 0.0) + (_d(scale_rows) if scale_rows is not None else torch.zeros_like(x))
@@ -227,9 +240,8 @@ def ln_modulate_bound(x, scale_rows, shift_rows, add_one, eps):
     z = (x - mean) * rstd
     ref = z * a + c
     az = (a * z).abs()
-    bound = (U_BF16 * ref.abs() + a.abs() * rstd * dim * U_F32 * x.abs().mean(dim=-1, keepdim=True)
-             + az * (dim + 8) * U_F32 + 4 * U_F32 * (az + c.abs()))
-    return ref, bound
+    e32 = a.abs() * rstd * dim * U_F32 * x.abs().mean(dim=-1, keepdim=True) + az * (dim + 8) * U_F32 + 4 * U_F32 * (az + c.abs())
+    return ref, e32
 
 
 def rmsnorm_rope_bound(x, w, eps, post_scale=1.0, rotate=None, head_dim=128):
@@ -394,6 +406,262 @@ def softmax_rows_bound(s, n, scale):
     return p, U_BF16 * p + p * U_F32 * (rel + row + n + 4.0) + 2.0 ** -120
 
 
+# ------------------------------------------------------------------------------------------------ fp8 (OCP e4m3) kernels
+# The fp8 mode is lossy because of the QUANTISATION; on the e4m3 operands a kernel is handed it is as exact as its bf16 sibling, and
+# that is what these bounds state.  e4m3fn: 4 significand bits (u = 2^-4), smallest normal 2^-6, subnormal step 2^-9 (half: 2^-10).
+FP8 = torch.float8_e4m3fn
+FP8_MAX = 448.0
+U_E4M3 = 2.0 ** -4
+SUB_E4M3 = 2.0 ** -10      # half the subnormal step of e4m3, in units of the block / row scale
+LOG2E = 1.4426950408889634
+LN2 = 0.6931471805599453
+
+
+def dq(q8, row_scale):
+    """fp64 value of a row-scaled e4m3 GEMM operand: q8 [rows, K] * row_scale[rows] (exact: 4 x 24 significand bits)."""
+    return q8.detach().cpu().float().double() * _d(row_scale)[:, None]
+
+
+def dq_pow2(q8, exp):
+    """fp64 value of an attention operand stored as e4m3(x 2^exp): undoes the power of two exactly."""
+    return q8.detach().cpu().float().double() * 2.0 ** -exp
+
+
+def gemm_fp8_ref_and_term(aq, sa, wq, sw, bias, K):
+    """wan_gemm_fp8 / wan_gemm_fp8_ws: acc = (aq @ wq^T) * (sw[n] * sa[m]) (+ bias).  Returns (ref, acc_term) to be used with
+    gemm_bound / resid_bound / gelu_bound / gelu_from_acc_bound exactly like the bf16 pair (gemm_ref, gemm_acc_term):
+        acc_term = 2 K u32 |a| @ |w|^T + 3 u32 |a @ w^T| (+ 2 u32 (|a| @ |w|^T + |bias|)),   a, w the de-quantised operands
+    * the product of two e4m3 numbers has 8 significand bits: exact in fp32, no term;
+    * K fp32 additions in any order, each rounding or truncating (gemm_acc_term with the TRUE K): the 128-term sum inside one
+      v_mfma_scale_f32_16x16x128_f8f6f4, the chain over K tiles, the two phases of the persistent kernel's schedule P and the
+      stream-K combine only re-associate the same sum.  The term scales with the row and column scales like the sum itself, so it
+      is evaluated on the de-quantised magnitudes.  (Assumes the matrix pipe's internal adder is at least as wide as an fp32
+      truncating add; docs/TEST_BOUNDS.md records what was measured);
+    * the scale application acc * (sw[n] * sa[m]): two products, and one more in case the order changes: 3 u32 |acc|;
+    * the bias is one more addition, as in gemm_acc_term."""
+    a, w = dq(aq, sa), dq(wq, sw)
+    acc = a @ w.t()
+    mag = a.abs() @ w.abs().t()
+    term = 2.0 * K * U_F32 * mag + 3.0 * U_F32 * acc.abs()
+    if bias is not None:
+        term = term + 2.0 * U_F32 * (mag + _d(bias).abs())
+        acc = acc + _d(bias)
+    return acc, term
+
+
+def gemm_fp8_bound(aq, sa, wq, sw, bias, K, out_dtype):
+    """EPI_BF16 / EPI_BF16_T / EPI_F32 of the fp8 GEMMs: (ref, u_out |ref| + acc_term of gemm_fp8_ref_and_term)."""
+    ref, term = gemm_fp8_ref_and_term(aq, sa, wq, sw, bias, K)
+    return ref, gemm_bound(None, None, None, K, out_dtype, ref, term)
+
+
+def _e4m3_cast(x32):
+    """torch's float8_e4m3fn cast (round to nearest even, subnormals kept) of a float32 tensor clamped to the finite range."""
+    return x32.clamp(-FP8_MAX, FP8_MAX).to(FP8)
+
+
+def quantize_rows_fp8_ref(x):
+    """EXACT definition of wan_quantize_rows_fp8 (quantize_rows_fp8_kernel, videocof_amd/csrc/norm_kernels.hip) in float32, the
+    kernel's own operations in its own order:  amax = max(max|x|, 1e-12);  s = amax * fl(1 / 448);  q = e4m3(clamp(x * fl(448 / amax))).
+    x bf16 [rows, cols] -> (codes uint8 [rows, cols], s float32 [rows]).  The only operation that is not a single correctly rounded
+    IEEE operation by construction is the division; the build compiles it to the correctly rounded expansion."""
+    xf = x.detach().cpu().float()
+    amax = xf.abs().amax(dim=1).clamp_min(torch.tensor(1e-12, dtype=torch.float32))
+    s = amax * (torch.tensor(1.0, dtype=torch.float32) / torch.tensor(448.0, dtype=torch.float32))
+    inv = torch.tensor(448.0, dtype=torch.float32) / amax
+    return _e4m3_cast(xf * inv[:, None]).view(torch.uint8), s
+
+
+MX_POS = [32 * ((key >> 3) & 1) + 16 * (key >> 5) + 8 * ((key >> 4) & 1) + (key & 7) for key in range(64)]
+
+
+def vt_quantize_mx_ref(vt, H, Lk):
+    """EXACT definition of wan_vt_quantize_mx (vt_quantize_mx_kernel, videocof_amd/csrc/attn_fwd.hip).  vt bf16 [B, H * 128, >= pad],
+    pad = roundup(Lk, 64).  Per channel row and per MX block of 32 CONSECUTIVE keys (key half kt of a 64-key tile):
+        byte = max(biased_exponent(block max) - 7, 1)   (E8M0; an all-zero or denormal block takes the smallest normal scale)
+        code = e4m3(v / 2^(byte - 127))                 (block max / scale in [128, 256): nothing saturates)
+    stored with the key permutation of the attention kernel's P registers, position 32 hi + 16 kt + 8 g + j <- key 32 kt + 16 g + 8 hi + j
+    (MX_POS[key]), and the scale bytes as [B][H][tile][32 kt + (d & 31)][d >> 5].
+    Returns (codes uint8 [B, C, pad] in STORED order, scale bytes uint8 [B * H * tiles * 256], de-quantised V^T fp64 [B, C, pad] in
+    KEY order)."""
+    B, C = vt.shape[:2]
+    pad = (Lk + 63) // 64 * 64
+    nt = pad // 64
+    x = vt.detach().cpu()[:, :, :pad].float().reshape(B, C, nt, 2, 32)
+    amax = x.abs().amax(dim=-1)
+    ebits = (amax.contiguous().view(torch.int32) >> 23) & 0xFF
+    byte = (ebits - 7).clamp_min(1)                                         # [B, C, nt, 2]
+    scale = torch.exp2((byte - 127).float())                                # exact powers of two, >= 2^-126
+    codes_key = (x / scale[..., None]).to(FP8)                              # division by a power of two
+    deq = (codes_key.float().double() * scale.double()[..., None]).reshape(B, C, pad)
+    stored = torch.empty(B, C, nt, 64, dtype=torch.uint8)
+    stored[..., torch.tensor(MX_POS)] = codes_key.view(torch.uint8).reshape(B, C, nt, 64)
+    sc = byte.to(torch.uint8).view(B, H, 4, 32, nt, 2).permute(0, 1, 4, 5, 3, 2).reshape(-1)
+    return stored.reshape(B, C, pad), sc.contiguous(), deq
+
+
+def ln_modulate_fp8_bound(x, scale_rows, shift_rows, add_one, eps):
+    """wan_ln_modulate_fp8: y as wan_ln_modulate in fp32 (NOT rounded to bf16), then the row quantiser: amax = max|y|, s = amax fl(1/448),
+    q = e4m3(y fl(448 / amax)).  Returns (y_ref, bound on |q s - y_ref| per element, s_ref [rows], tolerance of s [rows]):
+        bound = (1 + 2^-4) e32 + 2^-4 |y| + 2^-10 s (1 + 2^-20) + 4 u32 |y|
+    * e32: the fp32 part of ln_modulate_bound (no bf16 term: there is no bf16 rounding); the quantiser sees the computed y, so its
+      relative rounding applies to |y| + e32;  * 2^-4 |y|: the e4m3 half ulp;  * 2^-10 s: half the subnormal step of the code, times
+      the scale (the 2^-20: s may be that much larger than s_ref, see below);
+    * the scale's own error: s * fl(448 / amax) = 1 up to three roundings (the constant, the division, the product) and the product
+      y * inv rounds once: 4 u32 |y|.  That amax itself is off by up to max e32 changes nothing in q * s: both factors move together.
+    * s against s_ref = max|y_ref| / 448: |amax - amax_ref| <= max_c e32 (the fp32 ln term at the row's extreme elements), two
+      roundings: tolerance max_c e32 / 448 + 2 u32 s_ref."""
+    y, e32 = _ln_modulate_parts(x, scale_rows, shift_rows, add_one, eps)
+    s_ref = y.abs().amax(dim=-1) / FP8_MAX
+    s_tol = e32.amax(dim=-1) / FP8_MAX + 2.0 * U_F32 * s_ref
+    bound = (1.0 + U_E4M3) * e32 + U_E4M3 * y.abs() + SUB_E4M3 * (1.0 + 2.0 ** -20) * s_ref[:, None] + 4.0 * U_F32 * y.abs()
+    return y, bound, s_ref, s_tol
+
+
+def attention_qk8_bound(qd, kd, v, k_len=None):
+    """wan_attention_fwd_qk8, one head: attention_bound on the DE-QUANTISED q8 / k8 (dq_pow2) and the bf16 v, scale 1 in the exp2
+    domain (q carries softmax_scale log2(e)).  Everything behind the scores is the lazy bf16 form (attn_fwd_w4_kernel<.., QK8 = true>
+    shares its softmax and P.V code with the bf16 instantiation): P rounded to bf16 once, the row sum from the unrounded p, c = 1.
+    The score: two v_mfma_scale_f32_32x32x64_f8f6f4 (channels 0-63, 64-127) chained through the accumulator = a 128-term sum of
+    EXACT products (8 significand bits), the operand scales 2^-q_exp, 2^-k_exp are exponent adjustments -- the same term count as the
+    bf16 form's 128-term MFMA chain, so d_i = 2^-23 (130 S_i + 2) is kept.  It stands for the same reason the fp8 GEMM's accumulation
+    term does, and with a margin as thin: the fp8 matrix pipe's internal adder is NOT as wide as a truncating fp32 add (measured on the
+    16x16x128 form: up to 0.95 x 2^-16 sum |a w| per instruction, docs/TEST_BOUNDS.md), and 128 2^-23 S_i happens to be 2^-16 S_i --
+    what 128 truncating fp32 additions are granted is what the pipe's narrower adder needs.  Returns (ref, bound)."""
+    return attention_bound(qd, kd, v, LN2, k_len)
+
+
+def attention_f8_bound(qd, kd, vd, k_len=None):
+    """wan_attention_fwd_f8 (max-free attempt), one head, against the fp64 softmax of the de-quantised q8 / k8 with the DE-QUANTISED
+    V (vt_quantize_mx_ref).  Read in attn_fwd_f8_kernel: p~_j = exp2(s_j) (no reference subtracted), the row sum l adds the
+    UNROUNDED fp32 p~ (sk[] / s1k0.. are summed before the conversion), every 32 consecutive keys form one MX block whose scale is
+    2^(floor(log2 sigma_b) - 7), sigma_b the block's fp32 sum; codes e4m3(p~ / scale_b); the V scales are exact powers of two.
+        bound = u16 |ref| + (s_i + f) (p @ |v|) + sum_j (2^-4 p_j + 2^-10 scale_b(j) / l) |v_j| + 2^-126 / l sum_j |v_j|
+    * the qk8 bound with the P term c u16 (p @ |v|) replaced: each probability carries the e4m3 half ulp 2^-4 relative and half the
+      subnormal step 2^-10 scale_b absolute (p~ / scale_b < 256: nothing saturates); scale_b from the REFERENCE's own block sums,
+      taken one binade up where sigma_b (1 + s_i + 34 u32) crosses a power of two (the kernel's sum has the score error s_i and 32
+      additions);  * s_i and f as in attention_bound (f's rescale allowance is unused here: the max-free form never rescales);
+    * the last term: exp2 results below the normal range are flushed (p~ < 2^-126).
+    Returns (ref, bound)."""
+    ref, p, s, f, pv = _attention_parts(qd, kd, vd, LN2, k_len)
+    q, k, v = _d(qd), _d(kd), _d(vd)
+    if k_len is not None:
+        k, v = k[:k_len], v[:k_len]
+    Lk = k.shape[0]
+    sc = q @ k.t()                                                          # log2-domain scores
+    m = sc.max(dim=-1, keepdim=True).values
+    l_rel = torch.exp2(sc - m).sum(dim=-1, keepdim=True)                    # l = l_rel 2^m
+    nb = (Lk + 31) // 32
+    pp = torch.zeros(q.shape[0], nb * 32, dtype=torch.float64)
+    pp[:, :Lk] = p
+    sig_rel = pp.view(-1, nb, 32).sum(dim=-1) * (1.0 + s + 34.0 * U_F32)    # sigma_b / l, widened
+    # scale_b / l = 2^(floor(log2 sigma_b) - 7) / l  with  log2 sigma_b = log2 sig_rel + log2 l.  Evaluated in the log domain: l = l_rel 2^m
+    # and sigma_b are unnormalised max-free quantities spanning 2^+-150 and more, where forming 2^m or sigma_b itself would overflow or
+    # underflow; only the RATIO scale_b / l, which is at most 2^-7, is ever exponentiated
+    log2_l = m + torch.log2(l_rel)
+    e_b = torch.floor(torch.log2(sig_rel.clamp_min(1e-300)) + log2_l)
+    scale_rel = torch.exp2(e_b - 7.0 - log2_l)                              # [Lq, nb]
+    scale_rel = torch.where(sig_rel > 0, scale_rel, torch.zeros_like(scale_rel))
+    va = torch.zeros(nb * 32, v.shape[1], dtype=torch.float64)
+    va[:Lk] = v.abs()
+    p_term = U_E4M3 * pv + SUB_E4M3 * (scale_rel @ va.view(nb, 32, -1).sum(dim=1))
+    flush = torch.exp2(-126.0 - log2_l) * v.abs().sum(dim=0, keepdim=True)
+    return ref, U_BF16 * ref.abs() + (s + f) * pv + p_term + flush
+
+
+def decisive_qkv_e4m3(L, H, seed, q_exp=5, k_exp=2, D=128):
+    """decisive_qkv as the fp8 attention kernels receive it: q pre-scaled by softmax_scale log2(e), rounded to bf16, then
+    q8 = e4m3(q 2^q_exp), k8 = e4m3(k 2^k_exp).  Asserted here, on the CPU: nothing saturates; the fp64 softmax of the DE-QUANTISED
+    operands keeps between 0.5 and 0.99 of row i on key i.
+    The guard key (heavy_key() does not carry over: 400 2^k_exp saturates) is a channel-0 pair that is exact in e4m3: every real key has
+    k_0 = 0, every query q_0 = 2^(6 - g), the guard key k_0 = 2^g e_0 with g = 8 - k_exp (code 256) -- score 64 in log2 units with EVERY
+    query, asserted to exceed every real score of every row by at least 40 and to stay below 100 (exp2 stays finite in the max-free form:
+    admitted, the key takes all the mass instead of tripping the redo check).
+    Returns dict(q8, k8 [L, H, D] float8, v bf16 [L, H, D], guard float8 [D], qd, kd fp64 de-quantised)."""
+    q, k, v, _ = decisive_qkv(L, H, seed, D=D)
+    c = D ** -0.5 * LOG2E
+    qp = (q.float() * c).to(torch.bfloat16)
+    g = 8 - k_exp
+    qp[..., 0] = 2.0 ** (6 - g)
+    qx, kx = qp.float() * 2.0 ** q_exp, k.float() * 2.0 ** k_exp
+    sat = int((qx.abs() > FP8_MAX).sum() + (kx.abs() > FP8_MAX).sum())
+    assert sat == 0, (L, H, q_exp, k_exp, sat)
+    q8, k8 = qx.to(FP8), kx.to(FP8)
+    guard = torch.zeros(D)
+    guard[0] = 2.0 ** g * 2.0 ** k_exp
+    assert float(guard[0]) <= FP8_MAX
+    guard8 = guard.to(FP8)
+    qd, kd = dq_pow2(q8, q_exp), dq_pow2(k8, k_exp)
+    assert float(qd[..., 0].min()) == float(qd[..., 0].max()) == 2.0 ** (6 - g) and float(kd[..., 0].abs().max()) == 0.0
+    gscore = float(qd[0, 0, 0]) * float(guard8.float()[0]) * 2.0 ** -k_exp
+    worst_real = -1e30
+    for h in range(H):
+        sc = qd[:, h] @ kd[:, h].t()
+        diag = torch.softmax(sc * LN2, dim=-1).diagonal()
+        assert 0.5 < float(diag.min()) and float(diag.max()) < 0.99, (L, h, q_exp, k_exp, float(diag.min()), float(diag.max()))
+        worst_real = max(worst_real, float(sc.max()))
+    assert gscore >= worst_real + 40.0 and gscore < 100.0, (gscore, worst_real)
+    return dict(q8=q8, k8=k8, v=v, guard=guard8, qd=qd, kd=kd, guard_score=gscore, max_real_score=worst_real)
+
+
+def wide_range_qkv_e4m3(Lq, Lk, seed, q_exp=5, k_exp=2, D=128):
+    """One head of e4m3 operands whose exp2-domain scores span 150 binades: channel 1 of every query is 8, channel 1 of key 5 is
+    +2.5 (score +20), whole 32-key blocks (every third block from block 1 on) carry -12, -13, -14, -15 or -16 there (scores -96 ... -128:
+    in the max-free form their block sums are tiny, denormal or zero -- scale word 0 --, their exponentials flushed), every other key
+    0; the remaining channels hold unit-variance noise (scores ~ N(0, 1.44^2)).  Channel 0 is the guard channel of
+    decisive_qkv_e4m3.  Returns the same dict."""
+    g = torch.Generator().manual_seed(seed)
+    c = D ** -0.5 * LOG2E
+    qp = (torch.randn(Lq, 1, D, generator=g) * c).to(torch.bfloat16)
+    k = torch.randn(Lk, 1, D, generator=g).to(torch.bfloat16)
+    gk = 8 - k_exp
+    qp[..., 0], k[..., 0] = 2.0 ** (6 - gk), 0.0
+    qp[..., 1], k[..., 1] = 8.0, 0.0
+    k[5 % Lk, 0, 1] = 2.5
+    deep = [-12.0, -13.0, -14.0, -15.0, -16.0]
+    for i, b in enumerate(range(1, (Lk + 31) // 32, 3)):
+        k[32 * b:32 * b + 32, 0, 1] = deep[i % 5]
+    qx, kx = qp.float() * 2.0 ** q_exp, k.float() * 2.0 ** k_exp
+    assert int((qx.abs() > FP8_MAX).sum() + (kx.abs() > FP8_MAX).sum()) == 0
+    q8, k8 = qx.to(FP8), kx.to(FP8)
+    assert torch.equal(q8.float()[..., 1], qx[..., 1]) and torch.equal(k8.float()[..., 1], kx[..., 1])      # exact in e4m3
+    j = torch.arange(Lk, dtype=torch.float64)
+    off = torch.stack([torch.sin(0.37 * j + 0.11 * d) + (1.0 if d % 2 else -1.0) * (j % 7) * 0.25 for d in range(D)], dim=-1)
+    v = (0.2 * torch.randn(Lk, 1, D, generator=g, dtype=torch.float64) + off[:, None, :]).to(torch.bfloat16)
+    guard = torch.zeros(D)
+    guard[0] = 2.0 ** gk * 2.0 ** k_exp
+    return dict(q8=q8, k8=k8, v=v, guard=guard.to(FP8), qd=dq_pow2(q8, q_exp), kd=dq_pow2(k8, k_exp))
+
+
+def heavy_half_qkv_e4m3(Lq, Lk, seed, q_exp=5, k_exp=2, D=128):
+    """One head of e4m3 operands in which the two MX blocks of a 64-key tile differ by 2^20 in mass and the HEAVY block carries no V:
+    channel 1 of every query is 8; channel 1 of key 5 (tile 0, key half 0) and of key 104 (tile 1, key half 1) is 2.5 -- score +20 --
+    and V is exactly zero over the 32 keys of each of those two blocks; every other key has unit-variance noise scores and random V, so
+    the output is carried by blocks that hold about 2^-20 of their tile's mass.  A P scale taken per 64-key tile instead of per
+    32-key block turns those probabilities into e4m3 subnormals (or zero) of the tile scale and loses the output of every row, while
+    the per-block scale keeps them at full e4m3 precision.  Needs Lk >= 128.  Channel 0 is the guard channel of decisive_qkv_e4m3.
+    Returns the same dict."""
+    assert Lk >= 128
+    g = torch.Generator().manual_seed(seed)
+    c = D ** -0.5 * LOG2E
+    qp = (torch.randn(Lq, 1, D, generator=g) * c).to(torch.bfloat16)
+    k = torch.randn(Lk, 1, D, generator=g).to(torch.bfloat16)
+    gk = 8 - k_exp
+    qp[..., 0], k[..., 0] = 2.0 ** (6 - gk), 0.0
+    qp[..., 1], k[..., 1] = 8.0, 0.0
+    k[5, 0, 1] = k[104, 0, 1] = 2.5
+    qx, kx = qp.float() * 2.0 ** q_exp, k.float() * 2.0 ** k_exp
+    assert int((qx.abs() > FP8_MAX).sum() + (kx.abs() > FP8_MAX).sum()) == 0
+    q8, k8 = qx.to(FP8), kx.to(FP8)
+    assert torch.equal(q8.float()[..., 1], qx[..., 1]) and torch.equal(k8.float()[..., 1], kx[..., 1])      # exact in e4m3
+    v = (torch.randn(Lk, 1, D, generator=g) + torch.linspace(-1, 1, D)).to(torch.bfloat16)
+    v[0:32] = 0.0
+    v[96:128] = 0.0
+    guard = torch.zeros(D)
+    guard[0] = 2.0 ** gk * 2.0 ** k_exp
+    return dict(q8=q8, k8=k8, v=v, guard=guard.to(FP8), qd=dq_pow2(q8, q_exp), kd=dq_pow2(k8, k_exp))
+
+
 # ------------------------------------------------------------------------------------------------ comparison
 def _ranges(idx):
     return [(int(idx[:, d].min()), int(idx[:, d].max())) for d in range(idx.shape[1])]
@@ -421,29 +689,35 @@ def assert_within(out, ref, bound, what):
 
 # ------------------------------------------------------------------------------------------------ guard bands
 POISON16 = 0x7FC1        # as bf16: a NaN; twice in a row (0x7FC17FC1) as fp32: a NaN too
+POISON8 = 0x7F           # as e4m3fn: a NaN (S.1111.111); the bytes of 0x7FC1 are not both NaN in e4m3 (0xC1 = -2.25)
 
 
 class Guarded:
     """A [rows, cols] (or [batch, rows, cols]) tensor handed out as the strided interior of a larger buffer that is filled
-    with a poison bit pattern (NaN in bf16 and fp32 alike, so it doubles as input poison): `rows_before` / `rows_after` guard rows
+    with a poison bit pattern (NaN in bf16 and fp32 alike -- 0x7F bytes, a NaN in e4m3fn, for the one-byte types -- so it doubles as
+    input poison): `rows_before` / `rows_after` guard rows
     per batch entry, `cols_before` columns left of and `ld - cols_before - cols` columns right of every row.  ``view`` is the
     interior; ``check()`` asserts that every byte outside it still holds the pattern."""
 
-    def __init__(self, shape, dtype, ld=None, rows_before=2, rows_after=2, cols_before=0, device="cpu", poison=POISON16):
+    def __init__(self, shape, dtype, ld=None, rows_before=2, rows_after=2, cols_before=0, device="cpu", poison=None):
         self.batched = len(shape) == 3
         B, rows, cols = shape if self.batched else (1,) + tuple(shape)
         self.esize = torch.empty((), dtype=dtype).element_size()
-        assert self.esize in (2, 4)
+        assert self.esize in (1, 2, 4)
         ld = cols_before + cols if ld is None else ld
         assert ld >= cols_before + cols
         self.B, self.rows, self.cols, self.ld, self.rb, self.c0 = B, rows, cols, ld, rows_before, cols_before
+        # the buffer is held in `unit`s: bytes for the one-byte types (poison 0x7F: NaN as e4m3fn), 16-bit words otherwise
+        unit = torch.uint8 if self.esize == 1 else torch.int16
+        poison = (POISON8 if self.esize == 1 else POISON16) if poison is None else poison
         self.poison = poison - 0x10000 if poison >= 0x8000 else poison
-        per16 = self.esize // 2
-        self.raw = torch.full((B, rows_before + rows + rows_after, ld * per16), self.poison, dtype=torch.int16, device=device)
+        per16 = max(1, self.esize // 2)
+        self.raw = torch.full((B, rows_before + rows + rows_after, ld * per16), self.poison, dtype=unit, device=device)
         typed = self.raw.view(dtype)                                        # [B, R, ld]
         v = typed[:, rows_before:rows_before + rows, cols_before:cols_before + cols]
         self.view = v if self.batched else v[0]
         self._per16 = per16
+        self._unit = "bytes" if self.esize == 1 else "16-bit words"
 
     def fill(self, t):
         self.view.copy_(t)
@@ -459,7 +733,7 @@ class Guarded:
         if bad.shape[0]:
             b, r, c = (int(i) for i in bad[0])
             (b0, b1), (r0_, r1_), (c0_, c1_) = _ranges(bad)
-            raise AssertionError(f"{what}: {bad.shape[0]} 16-bit words outside the tensor were written: batch {b0}-{b1}, rows "
+            raise AssertionError(f"{what}: {bad.shape[0]} {self._unit} outside the tensor were written: batch {b0}-{b1}, rows "
                                  f"{r0_ - self.rb}-{r1_ - self.rb} of {self.rows}, cols {c0_ // self._per16 - self.c0}-"
                                  f"{c1_ // self._per16 - self.c0} of {self.cols} (first: batch {b}, row {r - self.rb}, col "
                                  f"{c // self._per16 - self.c0})")
