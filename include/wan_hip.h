@@ -56,7 +56,7 @@ const char* wan_last_error(void);
  * wan_set_tuning is an atomic store: safe against concurrent launches, which see the old or the new value.
  * wan_get_tuning returns -1 for an unknown key.  No reference counterpart (the reference has no native code).
  * Read-only key "last_attn_variant": what the most recent wan_attention_fwd call of this process launched, as
- * WAN_ATTN_VARIANT_* (kernel family | WAN_ATTN_VARIANT_XCD_PINNED | WAN_ATTN_VARIANT_SPLIT_TAIL) -- so that a benchmark
+ * WAN_ATTN_VARIANT_* (kernel family | WAN_ATTN_VARIANT_XCD_PINNED | WAN_ATTN_VARIANT_SPLIT_TAIL | WAN_ATTN_VARIANT_SPARSE) -- so that a benchmark
  * reports the kernel the dispatcher picked instead of a literal.  Read-only key "dev_experiments": 1 if the library was built with
  * `make EXPERIMENTS=1` (the timing-only instruments of the persistent GEMM behind "gemm_exp" -- cycle stamps, forced waits -- compiled
  * in; never in the product build: there "gemm_exp" does nothing).
@@ -73,6 +73,7 @@ int wan_get_tuning(const char* key);
 #define WAN_ATTN_VARIANT_FAMILY_MASK 15
 #define WAN_ATTN_VARIANT_XCD_PINNED 16      /* every (batch, head) pinned to one XCD */
 #define WAN_ATTN_VARIANT_SPLIT_TAIL 32      /* the last partial round ran split over the keys (+ merge kernel) */
+#define WAN_ATTN_VARIANT_SPARSE 64          /* listed key tiles per query block (wan_attention_fwd_sparse): the lazy form's SPARSE instantiation */
 
 /* ---------------------------------------------------------------------------
  * a4  LayerNorm (no affine) + adaLN modulate, or LayerNorm with affine.
@@ -273,6 +274,35 @@ int wan_attention_plan(int batch, int Lq, int Lk, int num_heads, int head_dim, i
 #define WAN_ATTN_QK_FP8 2                   /* wan_attention_plan only: plan for wan_attention_fwd_qk8 */
 #define WAN_ATTN_PV_FP8 4                   /* wan_attention_plan only, with WAN_ATTN_QK_FP8: plan for wan_attention_fwd_f8 */
 #define WAN_ATTN_QSCALE(softmax_scale) ((softmax_scale) * 1.4426950408889634f)
+
+/* a9s Local self-attention: every query block attends a LIST of key tiles (LOSSY by construction, opt-in; no reference counterpart:
+ *     the reference's attention() is dense).  Query block qb = rows [256 qb, 256 qb + 256) attends exactly the keys of the physical
+ *     64-key tiles tiles[row_ptr[qb] .. row_ptr[qb + 1]): dense attention over those keys (of the last physical tile only keys < Lk),
+ *     no mask inside a listed tile.  One list serves every head and sample of a call.
+ *     The lists (host memory, int32; n_qblocks = ceil(Lq / 256), n_ktiles = ceil(Lk / 64)) must satisfy, checked in this order:
+ *       row_ptr[0] == 0; row_ptr non-decreasing; every row non-empty; every tile in [0, n_ktiles); every row strictly ascending.
+ *     wan_attn_sparse_validate: host arithmetic only (no GPU needed); WAN_ERR_INVALID with wan_last_error() naming the first offence.
+ *     wan_attn_sparse_create:   validates, then uploads once (synchronous copies: call it outside a stream capture).  The plan owns its
+ *                               device copy and remembers Lq, Lk; it may serve any number of calls, on any stream, until destroyed --
+ *                               the caller keeps it alive until the last launch that uses it has completed.
+ *     wan_attn_sparse_listed:   total listed (query block, tile) pairs; listed / (n_qblocks * n_ktiles) is the density.
+ *     wan_attention_fwd_sparse: q / k / vt / out / strides / softmax_scale / flags exactly as wan_attention_fwd.  Lq, Lk must be the
+ *                               plan's (WAN_ERR_INVALID otherwise).  Every check happens on the host before anything is enqueued, so
+ *                               every index the kernel reads lies inside its tensor by construction.  ONE launch of the lazy-reference
+ *                               kernel (attn_fwd_w4_kernel<0,false,1|2,...,SPARSE>), no scratch; capturable.  With every tile listed
+ *                               for every block the result equals wan_attention_fwd(workspace = NULL) bit for bit.
+ *     wan_get_tuning("last_attn_variant") reports WAN_ATTN_VARIANT_W4_LAZY | WAN_ATTN_VARIANT_SPARSE (| _XCD_PINNED). */
+typedef struct wan_attn_sparse wan_attn_sparse;
+wan_status_t wan_attn_sparse_validate(const int32_t* row_ptr, const int32_t* tiles, int n_qblocks, int n_ktiles);
+wan_status_t wan_attn_sparse_create(const int32_t* row_ptr, const int32_t* tiles, int Lq, int Lk, wan_attn_sparse** out);
+void wan_attn_sparse_destroy(wan_attn_sparse* plan);
+int64_t wan_attn_sparse_listed(const wan_attn_sparse* plan);
+wan_status_t wan_attention_fwd_sparse(const void* q, int64_t ldq, int64_t q_bstride,
+                                      const void* k, int64_t ldk, int64_t k_bstride,
+                                      const void* vt, int64_t ldvt, int64_t vt_bstride,
+                                      void* out, int64_t ldo, int64_t o_bstride,
+                                      int batch, int Lq, int Lk, const wan_attn_sparse* plan, int num_heads, int head_dim,
+                                      float softmax_scale, int flags, void* stream);
 
 /* a9' Self-attention with the QK^T product on the fp8 matrix pipe (LOSSY, opt-in; the role of the reference's
  *     `sageattn` branch, attention_utils.py:152-211 with attention_type = "SAGE_ATTENTION": 8-bit QK^T, 16-bit P.V).

@@ -25,7 +25,7 @@ ATTN_VARIANT_NAMES = {1: "attn_fwd_w4_kernel<.,.,ref> (4-wave, lazy softmax refe
                       4: "attn_fwd_w4_kernel<0,.,1,false,true> (4-wave, lazy softmax reference, QK^T on the fp8 matrix pipe)",
                       5: "attn_fwd_f8_kernel (4-wave, QK^T and P.V on the fp8 matrix pipe, checked max-free softmax) + "
                          "attn_fwd_w4_kernel<0,false,1,true,true> (fp8-QK^T lazy-reference fix-up of flagged workgroups)"}
-ATTN_VARIANT_XCD_PINNED, ATTN_VARIANT_SPLIT_TAIL = 16, 32
+ATTN_VARIANT_XCD_PINNED, ATTN_VARIANT_SPLIT_TAIL, ATTN_VARIANT_SPARSE = 16, 32, 64
 GEMM_VARIANT_KERNELS = {0: "gemm_bf16_kernel", 1: "gemm256_kernel", 2: "gemm_w4_kernel", 3: "gemm_pk_kernel"}      # wan_gemm_plan / wan_gemm_ws_plan (WAN_GEMM_VARIANT_*)
 
 
@@ -35,6 +35,8 @@ def attn_variant_name(code: int) -> str:
         name += ", heads pinned to XCDs"
     if code & ATTN_VARIANT_SPLIT_TAIL:
         name += " + split-KV tail round (4-wave SPLIT kernel + attn_combine_kernel)"
+    if code & ATTN_VARIANT_SPARSE:
+        name += ", listed key tiles per query block (SPARSE instantiation)"
     return name
 
 WAN_OK, WAN_ERR_INVALID, WAN_ERR_UNSUPPORTED, WAN_ERR_LAUNCH = 0, 1, 2, 3
@@ -179,6 +181,13 @@ SIGNATURES = {
     "wan_col_mean_bf16": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "wan_qk_quantize_fp8": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int, c_int64, c_void_p, c_float, c_float, c_void_p, c_void_p,
                                     c_void_p]),
+    "wan_attn_sparse_validate": (c_int, [c_void_p, c_void_p, c_int, c_int]),
+    "wan_attn_sparse_create": (c_int, [c_void_p, c_void_p, c_int, c_int, POINTER(c_void_p)]),
+    "wan_attn_sparse_destroy": (None, [c_void_p]),
+    "wan_attn_sparse_listed": (c_int64, [c_void_p]),
+    "wan_attention_fwd_sparse": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64,
+                                         c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64,
+                                         c_int, c_int, c_int, c_void_p, c_int, c_int, c_float, c_int, c_void_p]),
     "wan_attention_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
     "wan_cross_probs": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int, c_int64, c_int, c_int, c_int,
                                 c_void_p]),

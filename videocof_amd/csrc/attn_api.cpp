@@ -129,6 +129,44 @@ wan_status_t validate(const WanAttnCall& c) {
     return WAN_OK;
 }
 
+// Listed key tiles (wan_attention_fwd_sparse): ONE launch of the self-attention lazy form, whatever the shape -- no scratch, so no
+// max-free attempt, and no split tail round (the workgroups of a sparse launch differ in length; plan_tail's arithmetic assumes they
+// do not).  Heads are pinned to XCDs under the dense rule.
+WanAttnPlan plan_sparse(int batch, int Lq, int num_heads, bool pre) {
+    WanAttnPlan p;
+    p.self = true;
+    p.sparse = true;
+    p.ref2 = !pre || wan_tune(WAN_TUNE_ATTN_REF) == 2;
+    p.nwg = (int64_t)((Lq + kQPerWG - 1) / kQPerWG) * num_heads * batch;
+    p.xcd = wan_tune(WAN_TUNE_ATTN_XCD_MAP) != 0 && (num_heads * batch) % 8 == 0;
+    p.variant = p.family | WAN_ATTN_VARIANT_SPARSE | (p.xcd ? WAN_ATTN_VARIANT_XCD_PINNED : 0);
+    return p;
+}
+
+// The list contract, in the order wan_hip.h states it.  Host arithmetic only: the kernel trusts every index it reads.
+wan_status_t validate_lists(const int32_t* row_ptr, const int32_t* tiles, int n_qblocks, int n_ktiles) {
+    WAN_REQUIRE(row_ptr && tiles, WAN_ERR_INVALID, "wan_attn_sparse: null list");
+    WAN_REQUIRE(n_qblocks > 0 && n_ktiles > 0, WAN_ERR_INVALID, "wan_attn_sparse: n_qblocks=%d n_ktiles=%d", n_qblocks, n_ktiles);
+    WAN_REQUIRE(row_ptr[0] == 0, WAN_ERR_INVALID, "wan_attn_sparse: row_ptr[0]=%d must be 0", row_ptr[0]);
+    for (int b = 0; b < n_qblocks; ++b) {          // the offsets first: no tile is read through an offset that has not passed
+        const int64_t lo = row_ptr[b], hi = row_ptr[b + 1];
+        WAN_REQUIRE(hi >= lo, WAN_ERR_INVALID, "wan_attn_sparse: row_ptr decreases at query block %d (%lld -> %lld)", b, (long long)lo, (long long)hi);
+        WAN_REQUIRE(hi > lo, WAN_ERR_INVALID, "wan_attn_sparse: query block %d lists no tile (an empty row)", b);
+    }
+    for (int b = 0; b < n_qblocks; ++b) {
+        const int64_t lo = row_ptr[b], hi = row_ptr[b + 1];
+        for (int64_t i = lo; i < hi; ++i) {
+            WAN_REQUIRE(tiles[i] >= 0, WAN_ERR_INVALID, "wan_attn_sparse: query block %d lists the negative tile %d", b, tiles[i]);
+            WAN_REQUIRE(tiles[i] < n_ktiles, WAN_ERR_INVALID, "wan_attn_sparse: query block %d lists tile %d beyond the last (n_ktiles=%d)", b, tiles[i], n_ktiles);
+            if (i > lo) {
+                WAN_REQUIRE(tiles[i] != tiles[i - 1], WAN_ERR_INVALID, "wan_attn_sparse: query block %d lists tile %d twice (a duplicate)", b, tiles[i]);
+                WAN_REQUIRE(tiles[i] > tiles[i - 1], WAN_ERR_INVALID, "wan_attn_sparse: query block %d is not ascending (%d after %d)", b, tiles[i], tiles[i - 1]);
+            }
+        }
+    }
+    return WAN_OK;
+}
+
 wan_status_t attention_fwd(const WanAttnCall& c, void* stream) {
     const wan_status_t vs = validate(c);
     if (vs != WAN_OK || c.Lq == 0) return vs;
@@ -193,4 +231,62 @@ extern "C" wan_status_t wan_attention_fwd_f8(const void* q8, int64_t ldq8, int64
     const WanAttnCall c = {q8, ldq8, q8_bstride, k8, ldk8, k8_bstride, vt, ldvt, vt_bstride, out, ldo, o_bstride, batch, Lq, Lk, num_heads, head_dim,
                            1.0f, WAN_ATTN_Q_PRESCALED, workspace, workspace_bytes, nullptr, true, q_exp, k_exp, v8, ldv8, v8_bstride, v8_scales};
     return attention_fwd(c, stream);
+}
+
+// ---- listed key tiles per query block (local self-attention).  The plan is host-validated lists plus their one device copy.
+struct wan_attn_sparse {
+    int* d_lists = nullptr;     // row_ptr [n_qblocks + 1], then tiles [listed]
+    int Lq = 0, Lk = 0, n_qblocks = 0, n_ktiles = 0;
+    int64_t listed = 0;
+};
+
+extern "C" wan_status_t wan_attn_sparse_validate(const int32_t* row_ptr, const int32_t* tiles, int n_qblocks, int n_ktiles) {
+    return validate_lists(row_ptr, tiles, n_qblocks, n_ktiles);
+}
+
+extern "C" wan_status_t wan_attn_sparse_create(const int32_t* row_ptr, const int32_t* tiles, int Lq, int Lk, wan_attn_sparse** out) {
+    WAN_REQUIRE(out != nullptr, WAN_ERR_INVALID, "wan_attn_sparse_create: null out");
+    *out = nullptr;
+    WAN_REQUIRE(Lq > 0 && Lk > 0, WAN_ERR_INVALID, "wan_attn_sparse_create: Lq=%d Lk=%d", Lq, Lk);
+    const int nqb = (Lq + kQPerWG - 1) / kQPerWG, nkt = (Lk + kKV - 1) / kKV;
+    if (const wan_status_t vs = validate_lists(row_ptr, tiles, nqb, nkt); vs != WAN_OK) return vs;
+    wan_attn_sparse* p = new wan_attn_sparse();
+    p->Lq = Lq; p->Lk = Lk; p->n_qblocks = nqb; p->n_ktiles = nkt; p->listed = row_ptr[nqb];
+    const size_t head = (size_t)(nqb + 1) * sizeof(int32_t), body = (size_t)p->listed * sizeof(int32_t);
+    hipError_t e = hipMalloc((void**)&p->d_lists, head + body);
+    if (e == hipSuccess) e = hipMemcpy(p->d_lists, row_ptr, head, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(p->d_lists + nqb + 1, tiles, body, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        if (p->d_lists) (void)hipFree(p->d_lists);
+        delete p;
+        wan_set_error("wan_attn_sparse_create: cannot upload the lists: %s", hipGetErrorString(e));
+        return WAN_ERR_LAUNCH;
+    }
+    *out = p;
+    return WAN_OK;
+}
+
+extern "C" void wan_attn_sparse_destroy(wan_attn_sparse* p) {
+    if (p == nullptr) return;
+    if (p->d_lists) (void)hipFree(p->d_lists);
+    delete p;
+}
+
+extern "C" int64_t wan_attn_sparse_listed(const wan_attn_sparse* p) { return p ? p->listed : 0; }
+
+extern "C" wan_status_t wan_attention_fwd_sparse(const void* q, int64_t ldq, int64_t q_bstride, const void* k, int64_t ldk, int64_t k_bstride,
+                                                 const void* vt, int64_t ldvt, int64_t vt_bstride, void* out, int64_t ldo, int64_t o_bstride,
+                                                 int batch, int Lq, int Lk, const wan_attn_sparse* plan, int num_heads, int head_dim,
+                                                 float softmax_scale, int flags, void* stream) {
+    WAN_REQUIRE(plan != nullptr, WAN_ERR_INVALID, "wan_attention_fwd_sparse: null plan");
+    WanAttnCall c = {q, ldq, q_bstride, k, ldk, k_bstride, vt, ldvt, vt_bstride, out, ldo, o_bstride, batch, Lq, Lk, num_heads, head_dim,
+                     softmax_scale, flags, nullptr, 0};
+    c.sp_row_ptr = plan->d_lists;
+    c.sp_tiles = plan->d_lists + plan->n_qblocks + 1;
+    if (const wan_status_t vs = validate(c); vs != WAN_OK) return vs;
+    WAN_REQUIRE(Lq == plan->Lq && Lk == plan->Lk, WAN_ERR_INVALID, "wan_attention_fwd_sparse: Lq=%d Lk=%d, the plan was made for Lq=%d Lk=%d",
+                Lq, Lk, plan->Lq, plan->Lk);
+    const WanAttnPlan p = plan_sparse(batch, Lq, num_heads, (flags & WAN_ATTN_Q_PRESCALED) != 0);
+    WAN_REQUIRE(p.nwg < (int64_t)1 << 31, WAN_ERR_UNSUPPORTED, "wan_attention_fwd_sparse: grid too large");
+    return wan_attn_launch(c, p, (hipStream_t)stream);
 }

@@ -17,6 +17,7 @@ struct WanAttnCall {
     const int* k_lens;                         // _varlen: device array of batch key counts, or NULL
     bool qk8; int q_exp, k_exp;                // _qk8 / _f8: q and k are e4m3 with these scale exponents
     const void* v8; int64_t ldv8, v8_bs; const void* vs8;      // _f8: the MX e4m3 V^T and its scales, or NULL (bf16 P.V)
+    const int* sp_row_ptr; const int* sp_tiles;                // _sparse: the plan's device lists (validated when it was created), or NULL
 };
 
 // Split-KV tail round (plan_tail in attn_api.cpp): the last `tq` query blocks of every (batch, head) leave the main launch
@@ -29,6 +30,7 @@ struct WanAttnPlan {
     bool self = false;          // long KV stream (Lk > 1024): the attn_self instantiations; otherwise attn_cross
     bool ref2 = false;          // lazy reference in the packed-shift form (REF = 2) instead of the accumulator form (REF = 1)
     bool xcd = false;           // heads pinned to XCDs
+    bool sparse = false;        // listed key tiles per query block (wan_attention_fwd_sparse): ONE launch of the lazy form, no scratch
     bool persist = false; int persist_grid = 0;     // cross-attention: `persist_grid` resident workgroups walk the `nwg` query blocks
     int64_t nwg = 0;            // workgroups (query blocks x heads x batch) of the main launch
     int64_t flag_bytes = 0;     // scratch layout: [flag_bytes: 16-byte header + one int per workgroup of the un-split grid][tail partials]

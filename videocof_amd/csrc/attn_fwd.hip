@@ -74,6 +74,10 @@ struct AttnArgs {
     // packed ragged batches (wan_attention_fwd_varlen): keys of batch b end at klens[b] (device memory, clamped to [1, Lk]); NULL =
     // every batch attends Lk keys.  The reference packs such batches behind cu_seqlens (attention_utils.py:95-146)
     const int* klens;
+    // SPARSE form (wan_attention_fwd_sparse): query block qb attends the PHYSICAL 64-key tiles sp_tiles[sp_row_ptr[qb] .. sp_row_ptr[qb + 1])
+    // (strictly ascending, non-empty, every entry < ceil(Lk / 64): checked on the host before the plan's device copy is made)
+    const int* sp_row_ptr;
+    const int* sp_tiles;
 };
 
 // VARIANT (template parameter of the kernels below) only names the instantiation so profiles separate the two
@@ -180,10 +184,16 @@ constexpr float kW4Trigger = 0x1p40f;
 // operations complete in issue order, so `s_waitcnt vmcnt(16)` at the top of the next block waits for exactly those requests and
 // leaves the 16 stores in flight), and the stores go through a per-block buffer descriptor whose range check drops rows >= Lq -- every
 // lane always issues all 16 (16 bytes each, after the two lanes of a row have traded halves), which is what makes the count exact.
-template <int VARIANT, bool SPLIT, int REF, bool FIX = false, bool QK8 = false, bool PERSIST = false>
+// SPARSE (opt-in, lossy: local self-attention): the block's KV stream is a LIST of physical tiles instead of 0 .. nkv-1.  The loop, the
+// ring and the schedule are those of the lazy form over `nkv` = the length of the list; what changes is where a logical tile t turns
+// into an address (k_rsrc / v_rsrc) and which key indices the peeled last tile masks.  The list index is workgroup-uniform and the list
+// is never written while a launch runs: it is read through the constant address space, i.e. by scalar loads, and the tile number for
+// interval t + 1 is requested in interval t, so that no load sits between a fence and the tile requests behind it.
+template <int VARIANT, bool SPLIT, int REF, bool FIX = false, bool QK8 = false, bool PERSIST = false, bool SPARSE = false>
 __global__ __launch_bounds__(kW4Threads) __attribute__((amdgpu_waves_per_eu(1, 1)))
 void attn_fwd_w4_kernel(AttnArgs a) {
     constexpr bool MAXFREE = REF == 0, SPLAT = REF == 1, PKSUB = REF == 2;
+    static_assert(!SPARSE || (!SPLIT && !FIX && !QK8 && !PERSIST && !MAXFREE && VARIANT == 0), "the sparse form is the plain self-attention lazy-reference kernel");
     static_assert(!PERSIST || (!SPLIT && !FIX && !QK8 && !MAXFREE), "the persistent form is the plain lazy-reference kernel");
     static_assert(!QK8 || (SPLAT && VARIANT == 0), "the fp8 QK^T form is the self-attention lazy-reference kernel");
     static_assert(!(SPLIT && MAXFREE), "the split tail round runs the lazy-reference form");
@@ -215,6 +225,8 @@ void attn_fwd_w4_kernel(AttnArgs a) {
     // ---- the query block this workgroup works on (PERSIST: re-evaluated for every block it walks).  Everything below that depends on
     // the block -- operand origins, key count, the Q fragments -- is state that `setup_block` / `load_q` rewrite.
     int qblk, batch, head, split, t0, Lk, nkv;
+    typedef const __attribute__((address_space(4))) int* sp_list_t;
+    sp_list_t sp_list = nullptr;         // SPARSE: the block's list; Lk stays the PHYSICAL key count, nkv is the list's length
     const bf16_t *Q, *K, *VT;
     const unsigned char* K8;
     bf16_t* O;
@@ -237,6 +249,12 @@ void attn_fwd_w4_kernel(AttnArgs a) {
         if constexpr (SPLIT) Lk = min(a.Lk - t0 * kKV, a.tiles_per_split * kKV);
         else Lk = a.klens != nullptr ? max(1, min(a.klens[batch], a.Lk)) : a.Lk;        // scalar: one s_load per workgroup
         nkv = (Lk + kKV - 1) / kKV;
+        if constexpr (SPARSE) {
+            const sp_list_t rp = (sp_list_t)(uintptr_t)a.sp_row_ptr;
+            const int first = rp[qblk];
+            nkv = rp[qblk + 1] - first;
+            sp_list = (sp_list_t)(uintptr_t)a.sp_tiles + first;
+        }
         Q = a.q + batch * a.q_bs + head * kD;
         K = a.k + batch * a.k_bs + head * kD + (int64_t)t0 * kKV * a.ldk;
         K8 = QK8 ? a.k8 + batch * a.k8_bs + head * kD + (int64_t)t0 * kKV * a.ldk8 : nullptr;
@@ -300,7 +318,19 @@ void attn_fwd_w4_kernel(AttnArgs a) {
     }
     const int64_t k_row_bytes = QK8 ? a.ldk8 : a.ldk * 2;
     const int64_t k_tile_bytes = (int64_t)kKV * k_row_bytes;
+    // SPARSE: logical tile t of the block's list -> physical tile (one scalar load; t is clamped like the requests themselves)
+    auto sp_tile = [&](int t) -> int { return sp_list[min(t, nkv - 1)]; };
+    int sp_next1 = 0, sp_next2 = 0;     // SPARSE: physical tiles t + 1 and t + 2 of the interval about to run (scalar state)
+    auto k_rsrc_at = [&](int tc) {      // SPARSE: physical tile tc
+        const int64_t left = (int64_t)(Lk - tc * kKV) * k_row_bytes;             // bytes from the tile origin to the end of physical row Lk-1
+        return __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)K + tc * k_tile_bytes), 0,
+                                                 (int)min(left, (int64_t)0x7fffffff), 0x00020000);
+    };
+    auto v_rsrc_at = [&](int tc) {
+        return __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)VT + (int64_t)tc * kKV * 2), 0, 0x7fffffff, 0x00020000);
+    };
     auto k_rsrc = [&](int t) {          // tile min(t, nkv-1): a request past the end re-stages the last tile into a dead slot
+        if constexpr (SPARSE) return k_rsrc_at(sp_tile(t));
         const int tc = min(t, nkv - 1);
         const int64_t left = (int64_t)(Lk - tc * kKV) * k_row_bytes;             // bytes from the tile origin to the end of row Lk-1
         const char* const k_origin = QK8 ? (const char*)K8 : (const char*)K;
@@ -308,6 +338,7 @@ void attn_fwd_w4_kernel(AttnArgs a) {
                                                  (int)min(left, (int64_t)0x7fffffff), 0x00020000);
     };
     auto v_rsrc = [&](int t) {          // tile min(t, nkv-1) (t <= nkv - 1 on every call); V^T pad columns exist up to roundup(Lk, 64)
+        if constexpr (SPARSE) return v_rsrc_at(sp_tile(t));
         return __builtin_amdgcn_make_buffer_rsrc((void*)((const char*)VT + (int64_t)min(t, nkv - 1) * kKV * 2), 0, 0x7fffffff, 0x00020000);
     };
     auto stage_k_piece = [&](__amdgpu_buffer_rsrc_t r, int kslot, int j) {
@@ -442,14 +473,16 @@ void attn_fwd_w4_kernel(AttnArgs a) {
     float nm[2] = {0.f, 0.f};   // -m of the wave's two query blocks (log2 units)
     f32x2 nmp[2];               // PKSUB: (-m, -m), the v_pk_add_f32 operand
     if constexpr (!MAXFREE) {
-        if (nkv == 1 && Lk < kKV) {
+        int lk0 = Lk;           // keys of tile 0 that exist
+        if constexpr (SPARSE) lk0 = Lk - sp_tile(0) * kKV;
+        if (nkv == 1 && lk0 < kKV) {
 #pragma unroll
             for (int qb = 0; qb < 2; ++qb)
 #pragma unroll
                 for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
                     for (int r = 0; r < 16; ++r)
-                        if (32 * kt + 16 * (r >> 3) + 8 * hi + (r & 7) >= Lk) s0[qb][kt][r] = -INFINITY;
+                        if (32 * kt + 16 * (r >> 3) + 8 * hi + (r & 7) >= lk0) s0[qb][kt][r] = -INFINITY;
         }
 #pragma unroll
         for (int qb = 0; qb < 2; ++qb) {
@@ -551,7 +584,11 @@ void attn_fwd_w4_kernel(AttnArgs a) {
         // in slot (f + 4) % 5 (segment C; its first four are requested in B28..B31, when K slots 0..2 and the spare slot 4 are
         // free, and K fragments 0..3 of the next interval are requested behind the fence)
         u32x4 fr[5];
-        const __amdgpu_buffer_rsrc_t rk = k_rsrc(t + 2), rv = v_rsrc(t + 1);
+        // SPARSE: this interval's tiles were looked up one interval ago; the lookup for the next one (tile t + 3) goes out here and
+        // has the whole interval to land
+        const __amdgpu_buffer_rsrc_t rk = SPARSE ? k_rsrc_at(sp_next2) : k_rsrc(t + 2), rv = SPARSE ? v_rsrc_at(sp_next1) : v_rsrc(t + 1);
+        int sp_next3 = 0;
+        if constexpr (SPARSE) sp_next3 = sp_tile(t + 3);
         float e[64];
         f32x2 dd[32];                                         // PKSUB: shifted score pairs
         float ps0 = carry[0], ps1 = carry[1];                // this tile's row sums so far (first key half)
@@ -620,11 +657,13 @@ void attn_fwd_w4_kernel(AttnArgs a) {
         l_run[1] += ps1;
         carry[0] = cn0;
         carry[1] = cn1;
+        if constexpr (SPARSE) { sp_next1 = sp_next2; sp_next2 = sp_next3; }
     };
 
     const int nfull = nkv - 1;  // tiles handled by the steady-state intervals; the last tile is peeled
     int it = 0;
     bool last_in_s1 = false;
+    if constexpr (SPARSE) { sp_next1 = sp_tile(1); sp_next2 = sp_tile(2); }
     for (; it + 2 <= nfull; it += 2) {          // `it` is even here: K(it+1) sits in slot 1, V(it) in slot 0
         interval(s0, s1, pa, pb, std::integral_constant<int, 1>{}, std::integral_constant<int, 0>{}, it);
         fence();
@@ -658,7 +697,8 @@ void attn_fwd_w4_kernel(AttnArgs a) {
     // here with the mask (the first two that the last interval produced ahead of time, and `carry`, are dropped).
     {
         u32x4 pf[2][4];
-        const int kv0 = it * kKV;
+        int kv0 = it * kKV;
+        if constexpr (SPARSE) kv0 = sp_tile(it) * kKV;      // physical keys against the physical Lk: only the list's last entry can be partial
         const unsigned vb = (it & 1) * kVTileBytes;
         if (last_in_s1) {                                  // value copies (a select of array lvalues would pin both in memory)
 #pragma unroll
@@ -1246,14 +1286,14 @@ __global__ void vt_pad_check_kernel(const bf16_t* vt, int64_t ldvt, int64_t vt_b
 
 // ---- the instantiations, written ONCE: the LDS reservation and the run-time -> template dispatch both walk this list, so a form
 // cannot be launched without having been reserved, and each is reserved with the size it is launched with.
-constexpr int attn_form_id(int variant, bool split, int ref, bool fix = false, bool qk8 = false, bool persist = false) {
-    return variant | (split ? 2 : 0) | ref << 2 | (fix ? 16 : 0) | (qk8 ? 32 : 0) | (persist ? 64 : 0);
+constexpr int attn_form_id(int variant, bool split, int ref, bool fix = false, bool qk8 = false, bool persist = false, bool sparse = false) {
+    return variant | (split ? 2 : 0) | ref << 2 | (fix ? 16 : 0) | (qk8 ? 32 : 0) | (persist ? 64 : 0) | (sparse ? 256 : 0);
 }
 constexpr int kAttnFormF8 = 128;        // attn_fwd_f8_kernel
 template <auto KERNEL, int ID, int LDS_BYTES>
 struct AttnForm { static constexpr auto kernel = KERNEL; static constexpr int id = ID, lds = LDS_BYTES; };
-template <int VARIANT, bool SPLIT, int REF, bool FIX = false, bool QK8 = false, bool PERSIST = false>
-using W4Form = AttnForm<&attn_fwd_w4_kernel<VARIANT, SPLIT, REF, FIX, QK8, PERSIST>, attn_form_id(VARIANT, SPLIT, REF, FIX, QK8, PERSIST), kLdsBytesW4>;
+template <int VARIANT, bool SPLIT, int REF, bool FIX = false, bool QK8 = false, bool PERSIST = false, bool SPARSE = false>
+using W4Form = AttnForm<&attn_fwd_w4_kernel<VARIANT, SPLIT, REF, FIX, QK8, PERSIST, SPARSE>, attn_form_id(VARIANT, SPLIT, REF, FIX, QK8, PERSIST, SPARSE), kLdsBytesW4>;
 using F8Form = AttnForm<&attn_fwd_f8_kernel, kAttnFormF8, kLdsBytesF8>;
 // f(form) for every form until one answers true; false if none did
 template <class F>
@@ -1266,7 +1306,10 @@ bool any_attn_form(F&& f) {
         || f(W4Form<1, false, 1, false, false, true>{}) || f(W4Form<1, false, 2, false, false, true>{})     // persistent cross-attention
         || f(W4Form<0, false, 1, false, true>{}) || f(W4Form<0, true, 1, false, true>{})            // fp8 QK^T: main, tail
         || f(W4Form<0, false, 1, true, true>{})                                                     // fp8 QK^T fix-up behind the all-fp8 attempt
-        || f(F8Form{});                                                                             // fp8 QK^T and fp8 P.V, checked max-free
+        || f(F8Form{})                                                                              // fp8 QK^T and fp8 P.V, checked max-free
+        // listed key tiles (local attention).  Kept LAST: the mangled names of these two begin with those of the dense lazy forms, and
+        // tests/test_isa_static.py takes the first kernel of the assembly that matches a name
+        || f(W4Form<0, false, 1, false, false, false, true>{}) || f(W4Form<0, false, 2, false, false, false, true>{});
 }
 
 wan_status_t launch_form(int id, dim3 grid, hipStream_t st, const AttnArgs& a) {
@@ -1340,6 +1383,7 @@ wan_status_t wan_attn_launch(const WanAttnCall& c, const WanAttnPlan& plan, hipS
     a.vt = (const bf16_t*)c.vt; a.ldvt = c.ldvt; a.vt_bs = c.vt_bs;
     a.o = (bf16_t*)c.out; a.ldo = c.ldo; a.o_bs = c.o_bs;
     a.Lq = c.Lq; a.Lk = c.Lk; a.H = num_heads; a.klens = c.k_lens;
+    a.sp_row_ptr = c.sp_row_ptr; a.sp_tiles = c.sp_tiles;
     a.scale_log2e = (c.flags & WAN_ATTN_Q_PRESCALED) != 0 ? 1.0f : c.softmax_scale * 1.4426950408889634f;
     a.nsplit = 1;
     if (plan.scratch) a.flags = (int*)c.workspace + 4;
@@ -1352,7 +1396,7 @@ wan_status_t wan_attn_launch(const WanAttnCall& c, const WanAttnPlan& plan, hipS
     const int v = plan.self || q8 ? 0 : 1, lazy_ref = plan.ref2 ? 2 : 1;
     if (f8) { WAN_LAUNCH_FORM(kAttnFormF8, grid); WAN_CHECK_LAUNCH("wan_attention_fwd_f8"); }
     if (maxfree) { WAN_LAUNCH_FORM(attn_form_id(v, false, 0), grid); WAN_CHECK_LAUNCH("wan_attention_fwd"); }
-    WAN_LAUNCH_FORM(attn_form_id(v, false, fix ? 1 : lazy_ref, fix, q8, plan.persist), plan.persist ? dim3((unsigned)plan.persist_grid) : grid);
+    WAN_LAUNCH_FORM(attn_form_id(v, false, fix ? 1 : lazy_ref, fix, q8, plan.persist, plan.sparse), plan.persist ? dim3((unsigned)plan.persist_grid) : grid);
     if (tp.tq > 0) {
         WAN_CHECK_LAUNCH("wan_attention_fwd");
         a.qblk0 = tp.main_qb; a.nsplit = tp.nsplit; a.tiles_per_split = tp.tiles_per_split;

@@ -61,7 +61,7 @@ def _check_capturable(model) -> None:
 
 
 class _Entry:
-    __slots__ = ("x", "t", "graph", "out", "calls", "kv", "epoch", "bufs", "attn_bufs")
+    __slots__ = ("x", "t", "graph", "out", "calls", "kv", "epoch", "bufs", "attn_bufs", "local_plan")
 
 
 class GraphedForward:
@@ -109,7 +109,9 @@ class GraphedForward:
                # a call the model's cfg_skip rule halves enqueues other launches than a full one of the same shape
                bool(m.cfg_skip_now(x.shape[0])),
                # the longest prompt decides which cross-attention branch the blocks enqueue and how many text rows it scores
-               max(int(u.shape[0]) for u in context))
+               max(int(u.shape[0]) for u in context),
+               # local attention enqueues other launches (per layer) and reads the plan's device lists
+               tuple(sorted((m.local_attention or {}).items())))
         epoch = m._graph_epoch
         for k in [k for k, e in self._entries.items() if e.epoch != epoch]:
             stale = self._entries.pop(k)                 # weights / fp8 copies / workspaces were replaced since the capture
@@ -120,6 +122,7 @@ class GraphedForward:
             ent = self._entries[key] = _Entry()
             ent.x, ent.t = torch.empty_like(x), torch.empty(x.shape[0], device=x.device, dtype=key_t)
             ent.graph, ent.out, ent.calls, ent.kv, ent.epoch, ent.bufs, ent.attn_bufs = None, None, 0, None, epoch, None, None
+            ent.local_plan = None
         ent.x.copy_(x)
         ent.t.copy_(t.to(key_t).expand(x.shape[0]))
         prev = m.cache_context
@@ -149,6 +152,8 @@ class GraphedForward:
                 ent.bufs = m._bufs[m._bufs_last]
                 ent.bufs.pinned = True
                 ent.attn_bufs = [ws.buf for ws in (m._ws_self, m._ws_cross, m._ws_self_sfx, m._ws_cross_sfx)]
+                # ... and the key-tile lists of a local-attention forward (built by the eager warm-up call above)
+                ent.local_plan = getattr(m, "_local_plan_last", None) if m.local_attention is not None else None
             ent.graph.replay()
             self.replays += 1
             return ent.out.clone()
@@ -202,6 +207,9 @@ class GraphedLoop:
         m = self.model
         if m.teacache is not None:
             raise NotImplementedError("TeaCache decides per step on the host whether the blocks run: not capturable")
+        if getattr(m, "local_attention", None) is not None:
+            raise NotImplementedError("local attention with capture_graph='loop': the recorded loop does not hold the key-tile plans "
+                                      "(and a from-step switch changes the launches inside it); use capture_graph='step'")
         T, D = m.text_len, m.text_dim
         key = key + (tuple(latents.shape), latents.dtype, len(context), torch.cuda.current_device(), tuple(m._fp8),
                      bool(m.use_block_composite), bool(m.use_forward_composite), int(m.skip_source_frames), int(m.mask_source_frames),

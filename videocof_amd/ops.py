@@ -11,6 +11,7 @@ import functools
 import math
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -539,6 +540,85 @@ def attention_fwd(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, num_heads:
                                      B, Lq, Lk, num_heads, head_dim, float(scale),
                                      _lib.ATTN_Q_PRESCALED if q_prescaled else 0, _p(ws), ws_bytes if ws is not None else 0,
                                      _stream()), "wan_attention_fwd")
+    return out
+
+
+def attn_sparse_validate(row_ptr, tiles, n_qblocks: int, n_ktiles: int) -> None:
+    """``wan_attn_sparse_validate`` (host arithmetic, no GPU): ValueError naming the first offence of the list contract."""
+    rp = np.ascontiguousarray(row_ptr, dtype=np.int32)
+    tl = np.ascontiguousarray(tiles, dtype=np.int32)
+    if rp.ndim != 1 or tl.ndim != 1 or rp.size != int(n_qblocks) + 1 or int(rp.max()) > tl.size:       # the library reads tiles[row_ptr[..]]
+        raise ValueError(f"attn_sparse: row_ptr must hold n_qblocks + 1 = {int(n_qblocks) + 1} offsets into the {tl.size} tiles")
+    _lib.check(_lib.load().wan_attn_sparse_validate(rp.ctypes.data, tl.ctypes.data if tl.size else None, int(n_qblocks), int(n_ktiles)),
+               "wan_attn_sparse_validate")
+
+
+class AttnSparsePlan:
+    """Owns one ``wan_attn_sparse`` handle: the validated key-tile lists of a local-attention plan (``local_attention.py``) and their
+    device copy, for calls with exactly these ``Lq`` / ``Lk`` on ``device``.  Create it outside a graph capture (the upload is a
+    synchronous copy); keep it alive while launches that use it are in flight."""
+
+    def __init__(self, row_ptr, tiles, Lq: int, Lk: int, device):
+        self.device = torch.device(device)
+        self.Lq, self.Lk = int(Lq), int(Lk)
+        self.n_qblocks, self.n_ktiles = (self.Lq + 255) // 256, (self.Lk + 63) // 64
+        rp = np.ascontiguousarray(row_ptr, dtype=np.int32)
+        tl = np.ascontiguousarray(tiles, dtype=np.int32)
+        attn_sparse_validate(rp, tl, self.n_qblocks, self.n_ktiles)
+        self._handle = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().wan_attn_sparse_create(rp.ctypes.data, tl.ctypes.data, self.Lq, self.Lk, ctypes.byref(self._handle)),
+                       "wan_attn_sparse_create")
+
+    @property
+    def listed(self) -> int:
+        return int(_lib.load().wan_attn_sparse_listed(self._handle))
+
+    @property
+    def density(self) -> float:
+        return self.listed / float(self.n_qblocks * self.n_ktiles)
+
+    def close(self) -> None:
+        if getattr(self, "_handle", None):
+            _lib.load().wan_attn_sparse_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:       # interpreter shutdown: the library may be gone
+            pass
+
+
+@_on_tensor_device
+def attention_fwd_sparse(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, num_heads: int, plan: AttnSparsePlan,
+                         k_len: Optional[int] = None, softmax_scale: Optional[float] = None, out: Optional[torch.Tensor] = None,
+                         q_prescaled: bool = False) -> torch.Tensor:
+    """``wan_attention_fwd_sparse``: operands as ``attention_fwd``; query block i (256 rows) attends exactly the keys of the 64-key
+    tiles ``plan`` lists for it.  One launch, no workspace.  LOSSY against dense attention unless every tile is listed."""
+    for nm, t in (("q", q), ("k", k), ("vt", vt)):
+        _need(t, torch.bfloat16, "attention_sparse." + nm)
+        if t.dim() != 3:
+            raise ValueError(f"attention_sparse.{nm} must be 3-D [B, rows, cols]")
+    B, Lq, C = q.shape
+    Lk = k.shape[1] if k_len is None else int(k_len)
+    if Lk > k.shape[1] or Lk <= 0:
+        raise ValueError(f"attention_sparse: k_len={Lk} outside (0, {k.shape[1]}]")
+    if not isinstance(plan, AttnSparsePlan) or not plan._handle:
+        raise ValueError("attention_sparse: plan must be a live ops.AttnSparsePlan")
+    if plan.device != q.device:
+        raise ValueError(f"attention_sparse: the plan lives on {plan.device}, q on {q.device}")
+    head_dim = C // num_heads
+    if out is None:
+        out = torch.empty(B, Lq, C, device=q.device, dtype=torch.bfloat16)
+    _need(out, torch.bfloat16, "attention_sparse.out")
+    if vt.shape[1] != C or k.shape[2] != C or k.shape[0] != B or vt.shape[0] != B:
+        raise ValueError("attention_sparse: q/k/vt shapes disagree")
+    scale = softmax_scale if softmax_scale is not None else 1.0 / math.sqrt(head_dim)
+    _lib.check(_lib.load().wan_attention_fwd_sparse(_p(q), q.stride(1), q.stride(0), _p(k), k.stride(1), k.stride(0),
+                                                    _p(vt), vt.stride(1), vt.stride(0), _p(out), out.stride(1), out.stride(0),
+                                                    B, Lq, Lk, plan._handle, num_heads, head_dim, float(scale),
+                                                    _lib.ATTN_Q_PRESCALED if q_prescaled else 0, _stream()), "wan_attention_fwd_sparse")
     return out
 
 

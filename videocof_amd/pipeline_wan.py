@@ -338,6 +338,12 @@ class WanPipeline:
         # counts tiles.  The default overlap is a guess: no real checkpoint has been run with it.  Opt-in and lossy; no quality claim.
         spatial_window = switches.pop("spatial_window", None)
         spatial_overlap = switches.pop("spatial_overlap", (96, 128))
+        # `local_attention=None, local_attention_from_step=0`: self-attention over a neighbourhood instead of every token (DESIGN.md
+        # 13.3; WanTransformer3DModel.enable_local_attention).  A (window_frames, window_rows) pair or a dict of that method's
+        # arguments; steps before `local_attention_from_step` run dense.  Opt-in and lossy; no quality claim.  The model's own
+        # setting is restored when the call returns.
+        local_attention = switches.pop("local_attention", None)
+        local_from = switches.pop("local_attention_from_step", 0)
         if switches:
             raise TypeError(f"__call__() got an unexpected keyword argument {next(iter(switches))!r}")
         compare_source = None
@@ -467,6 +473,32 @@ class WanPipeline:
         forward = self.transformer
         if capture_graph not in (False, True, "step", "loop"):
             raise ValueError(f"capture_graph={capture_graph!r}: False, True / 'step' (one hipGraph per forward) or 'loop' (the whole loop)")
+        local_cfg = None
+        if local_attention is not None:
+            if isinstance(local_attention, dict):
+                local_cfg = dict(local_attention)
+            elif isinstance(local_attention, (tuple, list)) and len(local_attention) == 2:
+                local_cfg = dict(zip(("window_frames", "window_rows"), local_attention))
+            else:
+                local_cfg = {}
+            if set(local_cfg) - {"window_frames", "window_rows", "sink_frames", "dense_layers"} or not {"window_frames", "window_rows"} <= set(local_cfg):
+                raise ValueError(f"local_attention={local_attention!r}: a (window_frames, window_rows) pair or a dict of the "
+                                 "enable_local_attention arguments")
+            if isinstance(local_from, bool) or not isinstance(local_from, int) or local_from < 0:
+                raise ValueError(f"local_attention_from_step={local_from!r}: a step index >= 0")
+            if capture_graph == "loop":
+                raise NotImplementedError("local_attention with capture_graph='loop': the recorded loop does not hold the key-tile "
+                                          "plans (use capture_graph='step')")
+        prev_local = getattr(self.transformer, "local_attention", None)
+
+        def local_step(i):
+            """Step i of a `local_attention` call: dense before `local_attention_from_step`, local from there on."""
+            if local_cfg is None:
+                return
+            if i >= local_from:
+                self.transformer.enable_local_attention(**local_cfg)
+            else:
+                self.transformer.disable_local_attention()
         if capture_graph in (True, "step"):
             # one hipGraph per call shape, kept across calls (videocof_amd/graph.py): step 0 of the first call runs
             # eagerly, step 1 is captured, every later step (and call) is a replay -- bit-identical latents
@@ -485,6 +517,7 @@ class WanPipeline:
                 self.transformer.current_steps = i
                 if self._interrupt:
                     continue
+                local_step(i)
                 # A step the model's cfg_skip rule halves (enable_cfg_skip; cfg_optimization.py:5-38) returns the conditional
                 # prediction twice, and guidance on two equal halves is that prediction itself: nu + g * (nt - nu) = nu + g * 0 = nu.
                 # So such a step calls the model with the conditional sample and embeddings only -- no doubled batch, no guidance
@@ -562,6 +595,7 @@ class WanPipeline:
                 self.transformer.current_steps = i
                 if self._interrupt:
                     continue
+                local_step(i)
                 state = state.contiguous()
                 nB = state.shape[0]
                 preds = None
@@ -648,6 +682,11 @@ class WanPipeline:
                 self.transformer.skip_source_frames = prev_skip
             if prev_mask is not None:
                 self.transformer.mask_source_frames = prev_mask
+            if local_cfg is not None:
+                if prev_local is None:
+                    self.transformer.disable_local_attention()
+                else:
+                    self.transformer.enable_local_attention(**prev_local)
             if self.release_workspaces_after_denoise and hasattr(self.transformer, "release_workspaces"):
                 # opt-in: 7 GB of activation buffers at 14B / 67k tokens handed back before the VAE decode (for hosts that share
                 # the device); the sets a captured graph replays from stay.  Off by default: 288 GB of HBM do not need it, every call

@@ -221,6 +221,13 @@ class WanTransformer3DModel(nn.Module):
         self._attn_events = None            # bench.py: list collecting (start, end) HIP events per self-attn launch
         self._last_attn_rows = 0
         self._last_attn_variant = 0
+        # local self-attention (opt-in, lossy; enable_local_attention / DESIGN.md 13.3): the settings, the key-tile plans by call
+        # shape (device lists, created outside any capture; a captured graph holds a reference to the one it reads) and the plan
+        # the block being run attends through (None: dense)
+        self._local_attn = None
+        self._local_plans = {}
+        self._local_plan_last = None
+        self._local_now = None
 
     # ------------------------------------------------------------------ properties
     @property
@@ -827,6 +834,54 @@ class WanTransformer3DModel(nn.Module):
             ev[2].record()
             self._comm_events.append(ev)
 
+    # ------------------------------------------------------------------ local self-attention
+    def enable_local_attention(self, window_frames: int, window_rows: int, sink_frames: int = 1, dense_layers=()):
+        """OPT-IN and LOSSY (the reference attends densely; no quality claim): every self-attention query attends a neighbourhood of
+        +-``window_frames`` latent frames (inside its segment, and the corresponding frames of the other one) and +-``window_rows``
+        token rows, plus the grounding frames and the first ``sink_frames`` frames of each segment (videocof_amd/local_attention.py
+        states the rule); the kernel never touches the key tiles outside it.  Layers named in ``dense_layers`` keep the dense call.
+        While enabled the forward takes the per-kernel block path (self-attention from Python, ``wan_dit_block_tail_forward`` behind
+        it).  TeaCache, ``cfg_skip`` and the context windows sit in front of the token path and work unchanged; the last block's
+        suffix form under ``skip_source_frames`` keeps its dense call.  Ulysses sequence parallelism, the fp8 'attn' / 'attn_pv'
+        modes and ``capture_graph='loop'`` raise NotImplementedError; ``GraphedForward`` works (its eager warm-up call builds the plan)."""
+        from .local_attention import _check_windows
+        _check_windows(window_frames, window_rows, sink_frames)
+        layers = frozenset(int(i) for i in dense_layers)
+        if any(i < 0 or i >= self.num_layers for i in layers):
+            raise ValueError(f"dense_layers={sorted(layers)}: the model has layers 0..{self.num_layers - 1}")
+        self._local_attn = dict(window_frames=int(window_frames), window_rows=int(window_rows), sink_frames=int(sink_frames),
+                                dense_layers=layers)
+
+    def disable_local_attention(self):
+        self._local_attn = None
+
+    @property
+    def local_attention(self):
+        """The arguments of the ``enable_local_attention`` call in force (a dict), or None."""
+        if self._local_attn is None:
+            return None
+        return dict(self._local_attn, dense_layers=tuple(sorted(self._local_attn["dense_layers"])))
+
+    def _local_plan(self, grid, frame_split_indices, ground_frame_indices, Ll, L):
+        """The key-tile plan of this call shape on the device, cached per (grid, split, ground, window): host arithmetic and one
+        synchronous upload the first time -- outside any capture (a captured forward has had its eager warm-up call)."""
+        from .local_attention import _one, local_attention_plan
+        la = self._local_attn
+        key = (tuple(grid), _one(frame_split_indices, "frame_split_indices"), _one(ground_frame_indices, "ground_frame_indices"),
+               la["window_frames"], la["window_rows"], la["sink_frames"], int(Ll), int(L), str(self._device))
+        plan = self._local_plans.get(key)
+        if plan is None:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("local attention: this call shape has no plan yet and a stream capture is running; run the shape "
+                                   "eagerly once before capturing it")
+            host = local_attention_plan(grid, key[1], key[2], la["window_frames"], la["window_rows"], la["sink_frames"], q_len=Ll)
+            plan = ops.AttnSparsePlan(host.row_ptr, host.tiles, Ll, L, self._device)
+            if len(self._local_plans) >= 16:                 # (a graph that reads an evicted plan keeps it alive: GraphedForward)
+                self._local_plans.pop(next(iter(self._local_plans)))
+            self._local_plans[key] = plan
+        self._local_plan_last = plan
+        return plan
+
     def _rope_map(self, grid, frame_split_indices, ground_frame_indices, token_offset, rows):
         """The temporal position map of rope_apply_qk (:160-179) as kernel parameters."""
         mode, f_src, g_end = 0, 0, 0
@@ -1015,6 +1070,8 @@ class WanTransformer3DModel(nn.Module):
                                  workspace=self._ws_self)
         elif "attn" in f8:
             ops.attention_fwd_qk8(bufs.q8.view(B, Ll, C), bufs.k8.view(B, Ll, C), vt, H, qe, ke, k_len=L, out=att, workspace=self._ws_self)
+        elif self._local_now is not None:
+            ops.attention_fwd_sparse(bufs.qk3[:, :, :C], bufs.qk3[:, :, C:], vt, H, self._local_now, k_len=L, out=att, q_prescaled=True)
         else:
             ops.attention_fwd(bufs.qk3[:, :, :C], bufs.qk3[:, :, C:], vt, H, k_len=L, out=att, q_prescaled=True, workspace=self._ws_self)
         self._event_done(ev, B * Ll)
@@ -1176,7 +1233,7 @@ class WanTransformer3DModel(nn.Module):
         """One WanAttentionBlock (:464-515) in place on the fp32 residual stream xs [B*Ll, C].
         em: [6, B, C] = modulation + e0 (:495); ctx_kv: (k [B,512,C], v^T [B,C,512]) of the text tokens."""
         composite = not blk.f8 and self._attn_events is None and self.use_block_composite
-        if composite and not self._usp:
+        if composite and not self._usp and self._local_now is None:
             # the same launch sequence as below, enqueued by ONE C call (wan_dit_block_forward): 1 FFI crossing instead of 15
             self._block_composite(blk, em, xs, bufs, ctx_kv, rp, B, Ll, L)
             return
@@ -1430,11 +1487,20 @@ class WanTransformer3DModel(nn.Module):
             ctx = self._text_embed(context)
             ctx_kv = [None] * self.num_layers
 
+        local_plan = None
+        if self._local_attn is not None:
+            if usp:
+                raise NotImplementedError("local attention with Ulysses sequence parallelism: the lists describe whole heads of one "
+                                          "device's full sequence; the exchanged layout has no sparse form")
+            if any(m in self._fp8 for m in ("attn", "attn_pv")):
+                raise NotImplementedError("local attention with the fp8 'attn' / 'attn_pv' modes: the listed-tiles kernel is a bf16 "
+                                          "lazy-reference form only")
+            local_plan = self._local_plan(grid, frame_split_indices, ground_frame_indices, Ll, L)
         r0 = 0          # rows whose output is needed after the last block start here (non-zero only with skip_source_frames)
         if self.skip_source_frames and B == 1 and not usp:
             r0 = min(int(self.skip_source_frames), grid[0]) * grid[1] * grid[2]
         if (not usp and self.use_block_composite and self.use_forward_composite and not self._fp8 and self.teacache is None
-                and self._probe_layer is None and self._attn_events is None and r0 == 0
+                and self._probe_layer is None and self._attn_events is None and r0 == 0 and local_plan is None
                 and dtype in (torch.float32, torch.bfloat16)):
             kvs = ctx_kv if ctx_kv[0] is not None else [self._context_kv(blk, ctx, B) for blk in self.blocks]
             rp = self._rope_map(grid, frame_split_indices, ground_frame_indices, 0, Ll)
@@ -1471,9 +1537,14 @@ class WanTransformer3DModel(nn.Module):
             if self._probe_layer == li:
                 self._probe = xs.clone()
             if r0 and li == self.num_layers - 1:
-                self._last_block_suffix(blk, emod[li], xs, bufs, kv, rp, r0, L)
+                self._last_block_suffix(blk, emod[li], xs, bufs, kv, rp, r0, L)        # (its suffix-query launch stays dense)
                 break
-            self._run_block(blk, emod[li], xs, bufs, kv, rp, B, Ll, L, seq_len)
+            # local attention: this layer's self-attention runs from Python through the plan, the token-local rest behind it
+            self._local_now = local_plan if local_plan is not None and li not in self._local_attn["dense_layers"] else None
+            try:
+                self._run_block(blk, emod[li], xs, bufs, kv, rp, B, Ll, L, seq_len)
+            finally:
+                self._local_now = None
         if ori_x is not None:
             if cond_flag:
                 self.teacache.previous_residual_cond = xs - ori_x
