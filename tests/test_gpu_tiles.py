@@ -1,7 +1,7 @@
 """-m gpu: spatial context windows -- wan_tile_gather / wan_tile_blend against their torch float32 definitions (bit for bit, with
-guard bands) and against the temporal pair where every frame is one tile, and the tiled denoise loop of WanPipeline against a loop
-composed from the CPU oracle, against a loop composed from the model's own single-tile forwards, and against today's paths where
-the frame fits one tile.  Bounds and observed values: docs/TEST_BOUNDS.md, "Spatial context windows"."""
+guard bands) and, where every frame is one tile, against the temporal pair and the temporal definition, and the tiled denoise
+loop of WanPipeline against a loop composed from the CPU oracle, against a loop composed from the model's own single-tile forwards,
+and against today's paths where the frame fits one tile.  Bounds and observed values: docs/TEST_BOUNDS.md, "Spatial context windows"."""
 import ctypes
 import math
 
@@ -11,7 +11,7 @@ import torch
 
 from oracle import wan_oracle as O
 from videocof_amd import (FlowDPMSolverMultistepScheduler, FlowUniPCMultistepScheduler, TilePlan, WanPipeline, WanTransformer3DModel, _lib,
-                          ops, reference_tile_blend, reference_tile_gather, window_plan)
+                          ops, reference_tile_blend, reference_tile_gather, reference_window_blend, reference_window_gather, window_plan)
 from videocof_amd.weights import deterministic_dit_state_dict, det_uniform
 
 pytestmark = pytest.mark.gpu
@@ -58,7 +58,12 @@ SHAPES = [(5, 7, 4, 4, 2, 2, 64),        # odd pitch: element form
           (8, 16, 4, 8, 2, 4, 64),       # 16-byte form in fp32, 8-byte in bf16
           (8, 32, 4, 16, 2, 8, 64),      # 16-byte form in both dtypes
           (8, 32, 4, 16, 2, 8, 3),       # the same behind a 3-element guard band: misaligned base, the form falls back
-          (24, 88, 16, 48, 4, 8, 64)]    # several workgroups per row
+          (24, 88, 16, 48, 4, 8, 64),    # several workgroups per row
+          # an axis with ONE window (weight 1.0f everywhere) beside a tiled one
+          (6, 8, 4, 8, 2, 0, 64),        # y tiled, x whole: the rows of a tile are contiguous in the state
+          (6, 7, 4, 7, 2, 0, 64),        # the same at an odd pitch
+          (4, 8, 4, 4, 0, 2, 64),        # x tiled, y whole
+          (24, 88, 16, 88, 4, 0, 3)]     # y tiled, x whole, behind a misaligned base, several row passes
 B, C = 2, 3
 
 
@@ -78,8 +83,12 @@ def _tables(p):
 @pytest.mark.parametrize("H,W,th,tw,oy,ox,pad", SHAPES)
 def test_a_tile_gather_equals_the_torch_definition(H, W, th, tw, oy, ox, pad, dtype):
     p = _tile_plan(H, W, th, tw, oy, ox)
-    if (H, W) == (6, 8):
+    if (H, W, tw) == (6, 8, 4):
         assert p.x.starts == (0, 2, 4)
+    if ox == 0:
+        assert (p.Ky, p.Kx) == (2, 1) and bool((p.x.alpha == 1).all())         # y tiled, x whole
+    if oy == 0:
+        assert (p.Ky, p.Kx) == (1, 3) and bool((p.y.alpha == 1).all())         # x tiled, y whole
     K, (n, _, _), Fs = p.K, p.shape, p.extent[0]
     for G in (0, 1):
         shape = (B, C, 2 * Fs + p.Kt * G, H, W)
@@ -127,15 +136,17 @@ def test_b_one_tile_per_spatial_axis_equals_the_window_kernels(H, W, dtype):
     assert (p.Ky, p.Kx) == (1, 1) and p.shape == (4, H, W)
     K, n, Fs = p.K, 4, 7
     alpha = torch.from_numpy(T_PLAN.alpha).to(DEV)
+    bits = lambda t: t.view(torch.int32 if dtype == torch.float32 else torch.int16)        # signed zeros included
     for G in (0, 1):
         state = _values(f"tile.one.state{G}", (B, C, 2 * Fs + K * G, H, W), dtype).to(DEV)
         for k0, k1, rep in ((0, K, 1), (1, K, 2), (1, 2, 2)):
-            assert torch.equal(ops.tile_gather(state, _starts(p), p.shape, G, k0, k1, rep),
-                               ops.window_gather(state, T_PLAN.starts, n, G, k0, k1, rep))
+            got = ops.tile_gather(state, _starts(p), p.shape, G, k0, k1, rep)
+            assert torch.equal(got, ops.window_gather(state, T_PLAN.starts, n, G, k0, k1, rep))
+            assert torch.equal(bits(got), bits(reference_window_gather(state, T_PLAN, n, G, k0, k1, rep)))      # the temporal definition
         pred = _values(f"tile.one.pred{G}", (K * B, C, 2 * n + G, H, W), dtype).to(DEV)
         got, want = ops.tile_blend(pred, _tables(p), _starts(p), p.extent, G), ops.window_blend(pred, alpha, T_PLAN.starts, Fs, G)
-        assert torch.equal(got.view(torch.int32 if dtype == torch.float32 else torch.int16),
-                           want.view(torch.int32 if dtype == torch.float32 else torch.int16))      # the bits, signed zeros included
+        assert torch.equal(bits(got), bits(want))
+        assert torch.equal(bits(got), bits(reference_window_blend(pred, T_PLAN, G)))                             # the temporal definition
 
 
 def test_c_invalid_arguments_return_wan_err_invalid():
