@@ -681,6 +681,41 @@ wan_status_t wan_tile_blend(void* out, const void* pred, int dtype, const float*
                             const int* t_starts, const int* y_starts, const int* x_starts, int Kt, int Ky, int Kx, int B, int C,
                             int Fs, int H, int W, int n, int th, int tw, int G, void* stream);
 
+/* a17e  Edit inside a mask: the denoising loop itself keeps the clip outside a caller's mask on its source.
+ *      replaces: nothing in the reference, whose loop repaints the whole target segment; callers composite in pixels afterwards.
+ *      wan_latent_mask_u8: alpha uint8 [B, T, H, W] (a pixel mask, any base alignment) -> weights uint8 [B, Fl, H/8, W/8],
+ *          Fl = 1 + ceil((T - 1) / 4), in integers (videocof_amd/video_io.py: reference_latent_edit_mask restates it in numpy int64 and
+ *          equals the kernels byte for byte):
+ *              p = the maximum of alpha over the pixel frames of latent frame j (frame 0 for j = 0, frames 4j-3 .. min(4j, T-1) for
+ *                  j >= 1) and over rows 8y .. 8y+7, columns 8x .. 8x+7
+ *              g = the maximum of p over the (2 grow + 1)^2 cells and the latent frames j - grow_t .. j + grow_t around a cell;
+ *                  positions outside the frame or outside the sample's Fl frames are ignored
+ *              weights = (2 S + m) / (2 m),   S = sum of g over the (2 feather + 1)^2 cells with clamped indices, m = (2 feather + 1)^2
+ *          (floor).  feather <= grow is what makes a cell that holds a 255 pixel keep weight 255.  ratio_s / ratio_t: the VAE's
+ *          compression ratios, 8 and 4 (what the kernels are built for; anything else is WAN_ERR_INVALID).  grow <=
+ *          WAN_LATENT_MASK_MAX_GROW, grow_t <= WAN_LATENT_MASK_MAX_GROW_T, feather <= grow, none negative; H % 8 == 0 and W % 8 == 0;
+ *          at most 2^31 - 1 mask bytes; `workspace`: device memory of wan_latent_mask_workspace_bytes(B, T, H, W) bytes (the p and g
+ *          planes) -> else WAN_ERR_INVALID before anything is enqueued.  Enqueues three kernels on `stream`; never synchronises.
+ *      wan_masked_prediction: in place on `pred`, the prediction for the loop state.  pred, sample: [B, C, F, hw] of one dtype (0 fp32,
+ *          1 bf16), sample = the state [source | grounding | target] the prediction was made for; weights uint8 [Bm, Fs, hw], Bm in
+ *          {1, B}, shared by the channels.  For every b, c, f < Fs and cell, with a = the weight, v = pred[.., target_frame0 + f, ..],
+ *          xt = sample[.., target_frame0 + f, ..], s = sample[.., f, ..], every operation rounded to float32 on its own:
+ *              w = a / 255.0f,   d = xt - s,   r = d / sigma,   out = (w * v) + ((1 - w) * r)
+ *          -- never a fused multiply-add, IEEE division, one final round-to-nearest-even to `dtype`.  r is the prediction whose
+ *          x0 = xt - sigma * r is the source.  Where a == 255 the element is not written (v's bits stay); where a == 0 the result is
+ *          round(r).  Frames of pred outside [target_frame0, target_frame0 + Fs) are never written.  sigma: this step's sigma_i > 0
+ *          (host float).  The access unit is the largest of 16, 8, 4 bytes or one element that divides (in bytes) Fs * hw, F * hw,
+ *          target_frame0 * hw and the bases (the weights' base by its count of elements).  A null tensor, another dtype, sigma <= 0 or
+ *          not finite, Bm not in {1, B}, target_frame0 < Fs or target_frame0 + Fs > F, a count of 2^31 or more -> WAN_ERR_INVALID
+ *          before anything is enqueued.  Enqueues one kernel on `stream`; never synchronises. */
+#define WAN_LATENT_MASK_MAX_GROW 4
+#define WAN_LATENT_MASK_MAX_GROW_T 2
+int64_t wan_latent_mask_workspace_bytes(int B, int T, int H, int W);
+wan_status_t wan_latent_mask_u8(const void* alpha_u8, void* weights_u8, int B, int T, int H, int W, int ratio_s, int ratio_t, int grow,
+                                int grow_t, int feather, void* workspace, int64_t workspace_bytes, void* stream);
+wan_status_t wan_masked_prediction(void* pred, const void* sample, int dtype, const void* weights_u8, int B, int Bm, int C, int F,
+                                   int Fs, int target_frame0, int64_t hw, float sigma, void* stream);
+
 /* ===========================================================================
  * WanVAE (videox_fun/models/wan_vae.py).  Activations are CHANNELS-LAST bf16 [T, H, W, C].
  * ------------------------------------------------------------------------- */

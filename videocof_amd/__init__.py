@@ -30,6 +30,8 @@ from .wan_text_encoder import WanT5EncoderModel  # noqa: F401
 from .video_io import frames_to_video, video_to_frames, load_video_frames  # noqa: F401
 from .video_io import FitPlan, fit_size, fit_plan, fit_frames, restore_frames, reference_fit_frames  # noqa: F401
 from .video_io import change_mask, composite_frames, keep_unedited, reference_change_mask, reference_composite_frames  # noqa: F401
+from .video_io import (fit_mask, latent_edit_mask, reference_fit_mask, reference_latent_edit_mask,  # noqa: F401
+                       reference_masked_prediction)
 from .video_io import ClipStats, clip_stats, reference_clip_stats, vae_roundtrip_frames  # noqa: F401
 from .video_io import grid_frames, compare_frames, reference_grid_frames, reference_compare_frames  # noqa: F401
 from .video_io import yuv_matrix, yuv_to_frames, frames_to_yuv, reference_yuv_to_frames, reference_frames_to_yuv  # noqa: F401

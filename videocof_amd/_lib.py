@@ -236,6 +236,9 @@ SIGNATURES = {
                                 + [c_int64, c_void_p]),
     "wan_tile_blend": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, POINTER(c_int), POINTER(c_int),
                                POINTER(c_int)] + [c_int] * 12 + [c_void_p]),
+    "wan_latent_mask_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
+    "wan_latent_mask_u8": (c_int, [c_void_p, c_void_p] + [c_int] * 9 + [c_void_p, c_int64, c_void_p]),
+    "wan_masked_prediction": (c_int, [c_void_p, c_void_p, c_int, c_void_p] + [c_int] * 6 + [c_int64, c_float, c_void_p]),
     "wan_gemm_bf16_batched": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64,
                                       c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "wan_embedding_rows": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p]),

@@ -1598,6 +1598,66 @@ def tile_blend(pred: torch.Tensor, tables, starts, extent, ground: int, out: Opt
 
 
 # ------------------------------------------------------------------ umT5 text encoder rows
+# ------------------------------------------------------------------ edit inside a mask
+LATENT_MASK_MAX_GROW, LATENT_MASK_MAX_GROW_T = 4, 2          # WAN_LATENT_MASK_MAX_* of include/wan_hip.h
+LATENT_MASK_RATIOS = (8, 4)                                   # pixels per latent cell, pixel frames per latent frame
+
+
+@_on_tensor_device
+def latent_mask(alpha: torch.Tensor, grow: int, grow_t: int, feather: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """A pixel mask uint8 [B,T,H,W] -> latent-cell weights uint8 [B, 1 + ceil((T-1)/4), H/8, W/8] (``wan_latent_mask_u8``,
+    include/wan_hip.h: three launches, integer arithmetic).  ``out``: a contiguous uint8 tensor of that shape, every byte of which
+    is overwritten.  The two intermediate planes live in a workspace allocated here."""
+    _need(alpha, torch.uint8, "latent_mask.alpha")
+    if alpha.dim() != 4:
+        raise ValueError(f"latent_mask.alpha: expected [B, T, H, W], got {tuple(alpha.shape)}")
+    alpha = alpha.contiguous()
+    B, T, H, W = (int(v) for v in alpha.shape)
+    rs, rt = LATENT_MASK_RATIOS
+    shape = (B, 1 + (max(T, 1) - 1 + rt - 1) // rt, H // rs, W // rs)
+    if out is None:
+        out = torch.empty(shape, device=alpha.device, dtype=torch.uint8)
+    elif out.dtype != torch.uint8 or tuple(out.shape) != shape or out.device != alpha.device or not out.is_contiguous():
+        raise ValueError(f"latent_mask.out: expected contiguous uint8 {shape} on {alpha.device}, got {out.dtype} {tuple(out.shape)} on "
+                         f"{out.device}")
+    lib = _lib.load()
+    nws = int(lib.wan_latent_mask_workspace_bytes(B, T, H, W))
+    ws = torch.empty(max(nws, 1), device=alpha.device, dtype=torch.uint8)
+    _lib.check(lib.wan_latent_mask_u8(_p(alpha), _p(out), B, T, H, W, rs, rt, int(grow), int(grow_t), int(feather), _p(ws), nws,
+                                      _stream()), "wan_latent_mask_u8")
+    return out
+
+
+@_on_tensor_device
+def masked_prediction_(pred: torch.Tensor, sample: torch.Tensor, weights: torch.Tensor, Fs: int, target_frame0: int,
+                       sigma: float) -> torch.Tensor:
+    """IN PLACE on ``pred``, the prediction for the loop state ``sample`` = [B, C, F, h, w] = [source | grounding | target]: outside
+    the mask the target's prediction becomes the one whose x0 is the source (``wan_masked_prediction``).  Per element of the target
+    frames [target_frame0, target_frame0 + Fs): ``w * v + (1 - w) * ((x_t - s) / sigma)`` with ``w = weights / 255``, float32 with
+    every operation rounded on its own; weight 255 leaves the element unwritten.  ``weights``: uint8 [Bm, Fs, h, w], Bm in {1, B},
+    shared by the channels.  fp32 or bf16, ``pred`` and ``sample`` alike.  Returns ``pred``."""
+    if pred.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"masked_prediction_: dtype {pred.dtype} not supported (fp32 or bf16)")
+    _need(pred, pred.dtype, "masked_prediction_.pred")
+    _need(sample, pred.dtype, "masked_prediction_.sample")
+    _need(weights, torch.uint8, "masked_prediction_.weights")
+    if pred.dim() != 5 or not pred.is_contiguous():
+        raise ValueError(f"masked_prediction_.pred: a contiguous [B, C, F, h, w] tensor (it is written in place), got {tuple(pred.shape)}")
+    if sample.shape != pred.shape or sample.device != pred.device:
+        raise ValueError(f"masked_prediction_.sample: {tuple(sample.shape)} on {sample.device} for the prediction's {tuple(pred.shape)} "
+                         f"on {pred.device}")
+    B, C, F, h, w = (int(v) for v in pred.shape)
+    Fs = int(Fs)
+    if weights.dim() != 4 or tuple(weights.shape[1:]) != (Fs, h, w) or int(weights.shape[0]) not in (1, B) or weights.device != pred.device:
+        raise ValueError(f"masked_prediction_.weights: expected uint8 [1 or {B}, {Fs}, {h}, {w}] on {pred.device}, got "
+                         f"{tuple(weights.shape)} on {weights.device}")
+    sample, weights = sample.contiguous(), weights.contiguous()
+    _lib.check(_lib.load().wan_masked_prediction(_p(pred), _p(sample), 0 if pred.dtype == torch.float32 else 1, _p(weights), B,
+                                                 int(weights.shape[0]), C, F, Fs, int(target_frame0), h * w, float(sigma), _stream()),
+               "wan_masked_prediction")
+    return pred
+
+
 def _avail(t: torch.Tensor) -> int:
     """Elements from t's first element to the end of its storage."""
     return t.untyped_storage().nbytes() // t.element_size() - t.storage_offset()

@@ -344,8 +344,36 @@ class WanPipeline:
         # setting is restored when the call returns.
         local_attention = switches.pop("local_attention", None)
         local_from = switches.pop("local_attention_from_step", 0)
+        # `edit_mask=None, edit_mask_grow=(1, 0), edit_mask_feather=1`: where the edit may happen.  uint8 [T, H, W] or
+        # [B, T, H, W] with T = source_frames and H x W = height x width, host or device; 255 = edit freely, 0 = keep the source.  Every
+        # step the target's prediction outside the mask is replaced by the one whose x0 is the source (wan_masked_prediction), so that
+        # region ends on the source latents to rounding.  `edit_mask_grow` = (latent cells, latent frames) of margin, `edit_mask_feather`
+        # = latent cells of soft edge (video_io.latent_edit_mask); the defaults are guesses.  Opt-in, changes outputs by design; no
+        # quality claim.
+        edit_mask = switches.pop("edit_mask", None)
+        edit_mask_grow = switches.pop("edit_mask_grow", (1, 0))
+        edit_mask_feather = switches.pop("edit_mask_feather", 1)
         if switches:
             raise TypeError(f"__call__() got an unexpected keyword argument {next(iter(switches))!r}")
+        mask_args = None
+        if edit_mask is not None:
+            from . import video_io
+            if video is None and source_latents is None and latents is None:
+                raise ValueError("edit_mask: outside the mask the clip is kept on its source; this call has none "
+                                 "(no `video`, `source_latents` or `latents`)")
+            if not isinstance(edit_mask_grow, (tuple, list)) or len(edit_mask_grow) != 2:
+                raise ValueError(f"edit_mask_grow={edit_mask_grow!r}: a (latent cells, latent frames) pair")
+            mask_args = video_io._latent_mask_args("edit_mask", edit_mask_grow[0], edit_mask_grow[1], edit_mask_feather)
+            want = f"uint8 [{source_frames}, {height}, {width}] or [B, {source_frames}, {height}, {width}]"
+            try:
+                edit_mask = video_io._as_mask(edit_mask, "edit_mask")
+            except ValueError as e:
+                raise ValueError(f"{e}; expected {want}") from None
+            if tuple(edit_mask.shape[-3:]) != (source_frames, height, width):
+                raise ValueError(f"edit_mask: expected {want} (source_frames, height, width of this call), got {tuple(edit_mask.shape)}")
+            if capture_graph == "loop":
+                raise NotImplementedError("edit_mask with capture_graph='loop': the recorded loop does not hold the mask's weights or "
+                                          "the per-step sigma of the replacement (use capture_graph='step')")
         compare_source = None
         if compare:
             if output_type != "uint8":
@@ -418,6 +446,19 @@ class WanPipeline:
         self._stage("vae_encode", t_stage)
         B, _, Ftot, hl, wl = latents.shape
         ps = self.transformer.config.patch_size
+        mask_weights = None          # edit inside a mask: the latent-cell weights uint8 [1 or B, Fs, hl, wl], made once
+        if mask_args is not None:
+            lead = 1 if edit_mask.dim() == 3 else int(edit_mask.shape[0])
+            cells = (height // video_io.LATENT_CELL, width // video_io.LATENT_CELL)
+            if Ftot != 2 * condition_count + ground_latent_count or (hl, wl) != cells or lead not in (1, B):
+                raise ValueError(f"edit_mask: a mask {tuple(edit_mask.shape)} for latents of {B} samples, {Ftot} frames of {hl} x {wl} "
+                                 f"cells; expected [source | grounding | target] = [{condition_count} | {ground_latent_count} | "
+                                 f"{condition_count}] frames of {cells[0]} x {cells[1]} cells and a mask for 1 or {B} samples")
+            mask_weights = video_io.latent_edit_mask((edit_mask if edit_mask.dim() == 4 else edit_mask.unsqueeze(0)).to(latents.device),
+                                                     grow=mask_args[0], grow_t=mask_args[1], feather=mask_args[2])
+            if mask_weights.shape[1] != condition_count:
+                raise ValueError(f"edit_mask: {source_frames} mask frames are {mask_weights.shape[1]} latent frames; the source "
+                                 f"segment has {condition_count}")
         plan = None                  # temporal context windows: None = the clip fits one window (or the option is off): today's path
         if window_latents is not None:
             if Ftot != 2 * condition_count + ground_latent_count:
@@ -511,6 +552,16 @@ class WanPipeline:
 
         cfg_skip_now = getattr(self.transformer, "cfg_skip_now", None)
 
+        def masked(noise_pred, sample, target_frame0, i):
+            """Edit inside a mask, step i: outside the mask the target's prediction becomes the one whose x0 is the
+            source block of `sample`, (x_t - s) / sigma_i -- in place on the step's prediction, after guidance (and after the window
+            blend).  The multistep history then holds the source there, the SDE variants keep their noise term, and the last step
+            (sigma_next = 0) lands the region on the source latents to rounding; inside the mask nothing changes."""
+            from . import ops
+            dt = torch.promote_types(noise_pred.dtype, sample.dtype)      # (both samplers widen to it themselves: an exact cast)
+            return ops.masked_prediction_(noise_pred.to(dt).contiguous(), sample.to(dt), mask_weights, condition_count, target_frame0,
+                                          float(self.scheduler.sigmas[i]))
+
         def denoise(latents, embeds):
             """The loop of :694-740 on `latents` with the prompt embeddings `embeds`; eager, or recorded into a hipGraph."""
             for i, t in enumerate(timesteps):                                                   # :694
@@ -556,6 +607,8 @@ class WanPipeline:
                 if prev_mask is None:
                     noise_pred[:, :, :condition_count] = 0                                      # :736
                 # else: already zero -- written by wan_unpatchify(zero_frames); CFG keeps it (0 + s * (0 - 0))
+                if mask_weights is not None:
+                    noise_pred = masked(noise_pred, latents, condition_count + ground_latent_count, i)
                 latents = self.scheduler.step(noise_pred, t, latents, **extra_step_kwargs, return_dict=False)[0]   # :740
                 if callback_on_step_end is not None:
                     # :742-750 -- the tensors named in callback_on_step_end_tensor_inputs; only `latents` coming back has an effect
@@ -630,6 +683,8 @@ class WanPipeline:
                             preds = torch.empty((K * nB,) + tuple(noise_pred.shape[1:]), device=noise_pred.device, dtype=noise_pred.dtype)
                         preds[k0 * nB:k1 * nB].copy_(noise_pred)
                 noise_pred = blend(preds.contiguous())
+                if mask_weights is not None:
+                    noise_pred = masked(noise_pred, state, condition_count + Kt * G, i)
                 state = self.scheduler.step(noise_pred, t, state, **extra_step_kwargs, return_dict=False)[0]
                 if callback_on_step_end is not None:
                     vals = {"latents": state, "prompt_embeds": prompt_embeds, "negative_prompt_embeds": negative_prompt_embeds}

@@ -27,6 +27,12 @@ into the ORIGINAL frames under that mask, ``keep_unedited`` does both (``wan_cha
 ``wan_frames_u8_composite``).  Nothing in the reference does this; the definition is ours, in integers:
 ``reference_change_mask`` / ``reference_composite_frames`` state it in numpy and are what the kernels equal byte for byte.
 
+Edit inside a mask: the other half of ``keep_unedited``, before the fact.  A caller who knows where the edit may happen passes that
+mask to ``WanPipeline.__call__(edit_mask=...)`` and the denoising loop itself pins the rest of the clip to its source every step
+(DESIGN.md 13.4).  ``fit_mask`` brings the mask of the original clip to the fitted size (``wan_plane_u8_resample``),
+``latent_edit_mask`` turns it into per-cell weights (``wan_latent_mask_u8``); ``reference_latent_edit_mask``,
+``reference_masked_prediction`` and ``reference_fit_mask`` state the definitions on the host and are what the kernels equal bit for bit.
+
 How far is clip A from clip B: ``clip_stats`` is one pass of integer kernels over two uint8 clips (``wan_clip_stats``) that yields, per
 frame and split by a mask, the histogram of byte differences, the histogram of ``change_mask``'s smoothed difference and the sums of
 x264's 8-bit SSIM; ``ClipStats`` turns those into PSNR, MAE, quantiles, SSIM and the ``threshold`` for ``change_mask`` on the host.
@@ -58,6 +64,7 @@ from . import ops
 __all__ = ["frames_to_video", "video_to_frames", "load_video_frames", "reference_frames_to_video", "reference_video_to_frames",
            "fit_size", "fit_plan", "FitPlan", "fit_frames", "restore_frames", "reference_fit_frames",
            "change_mask", "composite_frames", "keep_unedited", "reference_change_mask", "reference_composite_frames",
+           "latent_edit_mask", "fit_mask", "reference_latent_edit_mask", "reference_masked_prediction", "reference_fit_mask",
            "ClipStats", "clip_stats", "reference_clip_stats", "vae_roundtrip_frames",
            "grid_layout", "grid_frames", "compare_frames", "reference_grid_frames", "reference_compare_frames",
            "select_frame_indices", "yuv_matrix", "chroma_shape", "yuv_to_frames", "frames_to_yuv", "reference_yuv_to_frames",
@@ -496,6 +503,162 @@ def keep_unedited(original_u8, source_u8, edit_u8, plan: Optional[FitPlan] = Non
     ``source_u8``, ``plan``: what ``fit_frames`` made of it (``plan=None`` when the clip ran at its own size: then ``source_u8`` is
     ``original_u8``); ``edit_u8``: ``out.edit_videos``."""
     return composite_frames(original_u8, edit_u8, change_mask(source_u8, edit_u8, **mask_args), plan, out)
+
+
+# ---------------------------------------------------------------------------------------------- edit inside a mask (DESIGN.md 13.4)
+LATENT_MASK_MAX_GROW, LATENT_MASK_MAX_GROW_T = 4, 2                 # WAN_LATENT_MASK_MAX_* of include/wan_hip.h
+LATENT_CELL, LATENT_FRAMES = 8, 4                                   # pixels per latent cell, pixel frames per latent frame
+
+
+def _latent_mask_args(what: str, grow, grow_t, feather) -> Tuple[int, int, int]:
+    for name, v in (("grow", grow), ("grow_t", grow_t), ("feather", feather)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{what}: {name}={v!r} is not an integer")
+    grow, grow_t, feather = int(grow), int(grow_t), int(feather)
+    if not (0 <= grow <= LATENT_MASK_MAX_GROW and 0 <= grow_t <= LATENT_MASK_MAX_GROW_T and 0 <= feather <= grow):
+        raise ValueError(f"{what}: grow={grow} (0..{LATENT_MASK_MAX_GROW} latent cells) grow_t={grow_t} "
+                         f"(0..{LATENT_MASK_MAX_GROW_T} latent frames) feather={feather} (0..grow)")
+    return grow, grow_t, feather
+
+
+def _as_mask(alpha_u8, what: str, cells: bool = True) -> torch.Tensor:
+    """A uint8 [T, H, W] or [B, T, H, W] mask as a tensor where it is (host or device); ``cells``: H and W are multiples of 8."""
+    a = torch.from_numpy(alpha_u8) if isinstance(alpha_u8, np.ndarray) else alpha_u8
+    if not torch.is_tensor(a) or a.dtype != torch.uint8 or a.dim() not in (3, 4) or min(a.shape, default=0) < 1:
+        raise ValueError(f"{what}: expected a uint8 [T, H, W] or [B, T, H, W] mask, got {getattr(a, 'dtype', type(a))} "
+                         f"{tuple(getattr(a, 'shape', ()))}")
+    if cells and (a.shape[-2] % LATENT_CELL or a.shape[-1] % LATENT_CELL):
+        raise ValueError(f"{what}: a mask of {a.shape[-2]} x {a.shape[-1]} pixels is no whole number of {LATENT_CELL} x {LATENT_CELL} "
+                         "latent cells")
+    return a
+
+
+def _dilate(x: np.ndarray, radius: int, axis: int) -> np.ndarray:
+    """The maximum over the ``2 * radius + 1`` window along ``axis``; positions outside the array count nothing."""
+    n = x.shape[axis]
+    out = x.copy()
+    for d in range(1, min(radius, n - 1) + 1):
+        lo, hi = [slice(None)] * x.ndim, [slice(None)] * x.ndim
+        lo[axis], hi[axis] = slice(0, n - d), slice(d, n)
+        lo, hi = tuple(lo), tuple(hi)
+        out[lo] = np.maximum(out[lo], x[hi])
+        out[hi] = np.maximum(out[hi], x[lo])
+    return out
+
+
+def reference_latent_edit_mask(alpha_u8, *, grow: int = 1, grow_t: int = 0, feather: int = 1) -> torch.Tensor:
+    """The definition of ``latent_edit_mask`` in numpy int64 on the host: a pixel mask uint8 ``[T, H, W]`` or
+    ``[B, T, H, W]`` -> latent-cell weights uint8 ``[Fl, H/8, W/8]`` / ``[B, Fl, H/8, W/8]``, ``Fl = 1 + ceil((T - 1) / 4)``.  What the
+    kernels equal byte for byte; never called by the product path."""
+    grow, grow_t, feather = _latent_mask_args("reference_latent_edit_mask", grow, grow_t, feather)
+    t = _as_mask(alpha_u8, "reference_latent_edit_mask").cpu()
+    a = (t if t.dim() == 4 else t.unsqueeze(0)).numpy().astype(np.int64)
+    B, T, H, W = a.shape
+    h, w = H // LATENT_CELL, W // LATENT_CELL
+    Fl = 1 + (T - 1 + LATENT_FRAMES - 1) // LATENT_FRAMES
+    cell = a.reshape(B, T, h, LATENT_CELL, w, LATENT_CELL).max(axis=(3, 5))
+    p = np.empty((B, Fl, h, w), dtype=np.int64)                                 # 1. the maximum over a cell's pixels and pixel frames:
+    p[:, 0] = cell[:, 0]                                                        #    latent frame 0 is pixel frame 0,
+    for j in range(1, Fl):                                                      #    latent frame j >= 1 is frames 4j-3 .. min(4j, T-1)
+        p[:, j] = cell[:, LATENT_FRAMES * j - (LATENT_FRAMES - 1):min(LATENT_FRAMES * j, T - 1) + 1].max(axis=1)
+    g = _dilate(_dilate(p, grow, -1), grow, -2)                                 # 2. grey-scale dilation: nothing outside the frame,
+    g = _dilate(g, grow_t, -3)                                                  #    nothing outside the sample's Fl frames
+    m = (2 * feather + 1) ** 2
+    out = (2 * _box_sum(g, feather, (-1, -2), True) + m) // (2 * m)             # 3. change_mask's step 5 at cell resolution
+    out = torch.from_numpy(np.ascontiguousarray(out.astype(np.uint8)))
+    return out if t.dim() == 4 else out[0]
+
+
+def latent_edit_mask(alpha_u8, *, grow: int = 1, grow_t: int = 0, feather: int = 1) -> torch.Tensor:
+    """Where may the edit happen, in the latents' terms: a pixel mask as the per-cell weights ``WanPipeline.__call__(edit_mask=...)``
+    blends the prediction with, on the device (``wan_latent_mask_u8``; the definition is ``reference_latent_edit_mask``).
+
+    ``alpha_u8``: uint8 ``[T, H, W]`` or ``[B, T, H, W]`` at the size the pipeline runs at (``fit_mask`` brings the mask of the original
+    clip there), host or device; 255 = edit freely, 0 = keep the source.  Returns uint8 ``[Fl, H/8, W/8]`` / ``[B, Fl, H/8, W/8]`` on
+    the device: per latent cell the largest mask value of its 8 x 8 pixels and its pixel frames, grown by ``grow`` cells and ``grow_t``
+    latent frames (within a sample), the edge softened over ``2 * feather + 1`` cells.  Limits: ``grow <= 4``, ``grow_t <= 2``,
+    ``feather <= grow`` (so that a cell holding a 255 pixel keeps weight 255), ``H`` and ``W`` multiples of 8, else ``ValueError``.
+
+    The defaults are guesses: one cell (8 pixels) of margin and of feather around the mask.  No real checkpoint has been run with
+    them and no quality is claimed; ``clip_stats`` of the result against the source, split by the mask, is the tool for judging
+    them on yours."""
+    args = _latent_mask_args("latent_edit_mask", grow, grow_t, feather)
+    a = _as_mask(alpha_u8, "latent_edit_mask")
+    if not a.is_cuda:
+        a = a.to(torch.device("cuda", torch.cuda.current_device()))              # bytes over the host link, as they are
+    out = ops.latent_mask(a if a.dim() == 4 else a.unsqueeze(0), *args)
+    return out if a.dim() == 4 else out[0]
+
+
+def reference_masked_prediction(pred, sample, weights, Fs: int, target_frame0: int, sigma: float) -> torch.Tensor:
+    """The definition of ``ops.masked_prediction_`` in torch float32 on the host, one operation per line: returns the
+    new prediction (nothing is changed in place).  ``pred``, ``sample``: ``[B, C, F, h, w]`` of one dtype (fp32 or bf16), ``weights``:
+    uint8 ``[Bm, Fs, h, w]`` with ``Bm`` in {1, B}.  What the kernel equals bit for bit; never called by the product path."""
+    p, x, a = (torch.as_tensor(t).cpu() for t in (pred, sample, weights))
+    Fs, t0 = int(Fs), int(target_frame0)
+    if p.dtype not in (torch.float32, torch.bfloat16) or x.dtype != p.dtype or p.dim() != 5 or x.shape != p.shape:
+        raise ValueError(f"reference_masked_prediction: expected two [B, C, F, h, w] tensors of one dtype (fp32 or bf16), got {p.dtype} "
+                         f"{tuple(p.shape)} and {x.dtype} {tuple(x.shape)}")
+    B, _, F, h, w = p.shape
+    if a.dtype != torch.uint8 or a.dim() != 4 or tuple(a.shape[1:]) != (Fs, h, w) or a.shape[0] not in (1, B):
+        raise ValueError(f"reference_masked_prediction: expected uint8 weights [1 or {B}, {Fs}, {h}, {w}], got {a.dtype} {tuple(a.shape)}")
+    if Fs < 1 or t0 < Fs or t0 + Fs > F:
+        raise ValueError(f"reference_masked_prediction: Fs={Fs} source frames and the target at [{t0}, {t0} + {Fs}) do not fit {F} frames")
+    sig = torch.tensor(float(sigma), dtype=torch.float32)
+    if not bool(sig > 0) or not bool(torch.isfinite(sig)):
+        raise ValueError(f"reference_masked_prediction: sigma={sigma} (a finite value above 0)")
+    a = a[:, None]                                                               # shared by the channels
+    v = p[:, :, t0:t0 + Fs].float()
+    xt = x[:, :, t0:t0 + Fs].float()
+    s = x[:, :, :Fs].float()
+    wgt = a.float() / torch.tensor(255.0, dtype=torch.float32)
+    d = xt - s
+    r = d / sig                                                                  # the prediction whose x0 = xt - sigma * r is the source
+    inside = wgt * v
+    rest = 1.0 - wgt
+    outside = rest * r
+    new = (inside + outside).to(p.dtype)                                         # one rounding to the tensors' dtype (nearest even)
+    out = p.clone()
+    out[:, :, t0:t0 + Fs] = torch.where(a == 255, p[:, :, t0:t0 + Fs], new)      # weight 255: not written
+    return out
+
+
+def _check_fit_mask(what: str, a: torch.Tensor, plan: FitPlan) -> None:
+    if not isinstance(plan, FitPlan):
+        raise ValueError(f"{what}: `plan` is the FitPlan fit_frames returned, got {type(plan).__name__}")
+    if tuple(a.shape[-2:]) != (plan.height, plan.width):
+        raise ValueError(f"{what}: the plan fits {plan.height} x {plan.width} to {plan.out_height} x {plan.out_width}; got a mask of "
+                         f"{tuple(a.shape[-2:])} (expected [.., T, {plan.height}, {plan.width}])")
+
+
+def reference_fit_mask(alpha_u8, plan: FitPlan) -> torch.Tensor:
+    """The definition of ``fit_mask`` in numpy int64 on the host: ``reference_fit_frames``' two passes and tables (horizontal first, the
+    intermediate rounded to a byte, the plan's crop window) on a one-channel plane.  Never called by the product path."""
+    t = _as_mask(alpha_u8, "reference_fit_mask", cells=False).cpu()
+    _check_fit_mask("reference_fit_mask", t, plan)
+    a = t.numpy().astype(np.int64)
+    a = _resample_axis(a, -1, resample_axis_table(plan.width, plan.new_width, plan.x0, plan.out_width))
+    a = _resample_axis(a, -2, resample_axis_table(plan.height, plan.new_height, plan.y0, plan.out_height))
+    return torch.from_numpy(np.ascontiguousarray(a.astype(np.uint8)))
+
+
+def fit_mask(alpha_u8, plan: FitPlan) -> torch.Tensor:
+    """The mask of the ORIGINAL clip at the size ``fit_frames`` brought the clip to, on the device: the same crop window, tables and two
+    passes as the frames, as a one-channel plane (``wan_plane_u8_resample``; the definition is ``reference_fit_mask``).  ``alpha_u8``:
+    uint8 ``[T, plan.height, plan.width]`` or ``[B, T, ..]``, host or device; ``plan``: what ``fit_frames`` returned.  The result
+    (``[.., T, plan.out_height, plan.out_width]``) is the mask both ``WanPipeline.__call__(edit_mask=...)`` and the final
+    ``composite_frames(original, edit, alpha, plan)`` take.  A mask already at the target is returned as it is: nothing is launched."""
+    a = _as_mask(alpha_u8, "fit_mask", cells=False)
+    _check_fit_mask("fit_mask", a, plan)
+    if not a.is_cuda:
+        a = a.to(torch.device("cuda", torch.cuda.current_device()))
+    if (plan.out_height, plan.out_width) == (plan.height, plan.width):
+        return a
+    dev = str(a.device)
+    xtab, kx = _device_table(plan.width, plan.new_width, plan.x0, plan.out_width, dev)
+    ytab, ky = _device_table(plan.height, plan.new_height, plan.y0, plan.out_height, dev)
+    out = ops.plane_u8_resample(a.reshape(-1, plan.height, plan.width), plan.out_height, plan.out_width, xtab, kx, ytab, ky)
+    return out.view(tuple(a.shape[:-2]) + (plan.out_height, plan.out_width))
 
 
 # ---------------------------------------------------------------------------------------------- how far is clip A from clip B
