@@ -23,7 +23,9 @@ Prompts: with a ``tokenizer`` (a HuggingFace tokenizer object, e.g. ``AutoTokeni
 from __future__ import annotations
 
 import math
+from contextlib import contextmanager
 from dataclasses import dataclass
+from types import SimpleNamespace
 from typing import Callable, Optional, Union
 
 import numpy as np
@@ -42,6 +44,36 @@ class WanPipelineOutput:
     edit_videos: Optional[Union[torch.Tensor, np.ndarray]] = None
     latents: Optional[torch.Tensor] = None          # extension: final latents (output_type="latent")
     compare_videos: Optional[Union[torch.Tensor, np.ndarray]] = None   # extension: source | edit side by side (compare=True)
+
+
+def _require_source(has_source: bool, why: str) -> None:
+    if not has_source:
+        raise ValueError(f"{why}; this call has none (no `video`, `source_latents` or `latents`)")
+
+
+def _has_layout(frames: int, cc: int, G: int) -> bool:
+    """The one statement of the CoF layout of `frames` latent frames; _LAYOUT.format(cc, G) describes it in a message."""
+    return frames == 2 * cc + G
+
+
+_LAYOUT = "[source | grounding | target] = [{0} | {1} | {0}]"
+
+
+def _local_attention_args(local_attention, local_from, capture_graph) -> Optional[dict]:
+    """The `local_attention` option as the arguments of ``enable_local_attention`` (None: the option is off)."""
+    if local_attention is None:
+        return None
+    pair = isinstance(local_attention, (tuple, list)) and len(local_attention) == 2
+    cfg = dict(local_attention) if isinstance(local_attention, dict) else dict(zip(("window_frames", "window_rows"), local_attention)) if pair else {}
+    if set(cfg) - {"window_frames", "window_rows", "sink_frames", "dense_layers"} or not {"window_frames", "window_rows"} <= set(cfg):
+        raise ValueError(f"local_attention={local_attention!r}: a (window_frames, window_rows) pair or a dict of the "
+                         "enable_local_attention arguments")
+    if isinstance(local_from, bool) or not isinstance(local_from, int) or local_from < 0:
+        raise ValueError(f"local_attention_from_step={local_from!r}: a step index >= 0")
+    if capture_graph == "loop":
+        raise NotImplementedError("local_attention with capture_graph='loop': the recorded loop does not hold the key-tile "
+                                  "plans (use capture_graph='step')")
+    return cfg
 
 
 class WanPipeline:
@@ -308,7 +340,373 @@ class WanPipeline:
         torch.cuda.current_stream(frames.device).synchronize()
         return out.numpy()
 
-    # -------------------------------------------------------------- __call__ (:516-799)
+    # -------------------------------------------------------------- __call__ (:516-799): its stages, in the order it runs them
+    def _parse_switches(self, switches, video, has_source, source_frames, height, width, output_type, capture_graph):
+        """The keywords of ``__call__`` that travel in `switches` (as `as_uint8` is decode_latents': the named parameters stay the
+        reference's plus the extensions tests/test_oracle_vs_reference.py lists), and every check of them that needs no device."""
+        o = SimpleNamespace(
+            mask_args=None, compare_source=None,         # set below: (grow, grow_t, feather) checked; the uint8 source frames of compare=True
+            # compare=True: also return the reference's compare clip (save_side_by_side, fast_infer.py:183-206, as its writer's bytes) in
+            # `compare_videos`, composed on the device from the uint8 source frames and the edit segment (video_io.compare_frames)
+            compare=bool(switches.pop("compare", False)),
+            # `temporal_window=None, temporal_overlap=16, window_batch=None` (PIXEL frames; window_batch in windows): denoise a clip longer
+            # than `temporal_window` as overlapping windows of that length, blended every step -- see `_windowed_form` below
+            temporal_window=switches.pop("temporal_window", None), temporal_overlap=switches.pop("temporal_overlap", 16), window_batch=switches.pop("window_batch", None),
+            # `spatial_window=None, spatial_overlap=(96, 128)` ((rows, columns) in PIXELS): denoise frames larger than `spatial_window` as
+            # overlapping tiles of that size, blended every step (DESIGN.md 13.2); combines with `temporal_window`, `window_batch` then
+            # counts tiles.  The default overlap is a guess: no real checkpoint has been run with it.  Opt-in and lossy; no quality claim.
+            spatial_window=switches.pop("spatial_window", None), spatial_overlap=switches.pop("spatial_overlap", (96, 128)),
+            # `local_attention=None, local_attention_from_step=0`: self-attention over a neighbourhood instead of every token (DESIGN.md
+            # 13.3; WanTransformer3DModel.enable_local_attention).  A (window_frames, window_rows) pair or a dict of that method's
+            # arguments; steps before `local_attention_from_step` run dense.  Opt-in and lossy; no quality claim.  The model's own
+            # setting is restored when the call returns.
+            local_attention=switches.pop("local_attention", None), local_from=switches.pop("local_attention_from_step", 0),
+            # `edit_mask=None, edit_mask_grow=(1, 0), edit_mask_feather=1`: where the edit may happen (DESIGN.md 13.4).  uint8 [T, H, W] or
+            # [B, T, H, W] with T = source_frames and H x W = height x width, host or device; 255 = edit freely, 0 = keep the source.  Every
+            # step the target's prediction outside the mask is replaced by the one whose x0 is the source (wan_masked_prediction), so that
+            # region ends on the source latents to rounding.  `edit_mask_grow` = (latent cells, latent frames) of margin, `edit_mask_feather`
+            # = latent cells of soft edge (video_io.latent_edit_mask); the defaults are guesses.  Opt-in, changes outputs by design; no
+            # quality claim.
+            edit_mask=switches.pop("edit_mask", None), edit_mask_grow=switches.pop("edit_mask_grow", (1, 0)), edit_mask_feather=switches.pop("edit_mask_feather", 1))
+        if switches:
+            raise TypeError(f"__call__() got an unexpected keyword argument {next(iter(switches))!r}")
+        if o.edit_mask is not None:
+            from . import video_io
+            _require_source(has_source, "edit_mask: outside the mask the clip is kept on its source")
+            if not isinstance(o.edit_mask_grow, (tuple, list)) or len(o.edit_mask_grow) != 2:
+                raise ValueError(f"edit_mask_grow={o.edit_mask_grow!r}: a (latent cells, latent frames) pair")
+            o.mask_args = video_io._latent_mask_args("edit_mask", o.edit_mask_grow[0], o.edit_mask_grow[1], o.edit_mask_feather)
+            want = f"uint8 [{source_frames}, {height}, {width}] or [B, {source_frames}, {height}, {width}]"
+            try:
+                o.edit_mask = video_io._as_mask(o.edit_mask, "edit_mask")
+            except ValueError as e:
+                raise ValueError(f"{e}; expected {want}") from None
+            if tuple(o.edit_mask.shape[-3:]) != (source_frames, height, width):
+                raise ValueError(f"edit_mask: expected {want} (source_frames, height, width of this call), got {tuple(o.edit_mask.shape)}")
+            if capture_graph == "loop":
+                raise NotImplementedError("edit_mask with capture_graph='loop': the recorded loop does not hold the mask's weights or "
+                                          "the per-step sigma of the replacement (use capture_graph='step')")
+        if o.compare:
+            if output_type != "uint8":
+                raise ValueError(f"compare=True composes the compare clip from uint8 frames on the device: it needs "
+                                 f"output_type='uint8', not {output_type!r}")
+            src = o.compare_source = torch.from_numpy(video) if isinstance(video, np.ndarray) else video
+            if not torch.is_tensor(src) or src.dtype != torch.uint8 or src.dim() not in (4, 5) or src.shape[-1] != 3:
+                raise ValueError("compare=True needs the uint8 source frames as `video` ([T, H, W, 3] or [B, T, H, W, 3]), got "
+                                 f"{getattr(src, 'dtype', type(src))} {tuple(getattr(src, 'shape', ()))}")
+        return o
+
+    def _set_timesteps(self, num_inference_steps, shift, device):
+        if isinstance(self.scheduler, FlowUniPCMultistepScheduler):
+            self.scheduler.set_timesteps(num_inference_steps, device=device, shift=shift)       # :613-615
+            return self.scheduler.timesteps
+        if isinstance(self.scheduler, FlowDPMSolverMultistepScheduler):
+            return retrieve_timesteps(self.scheduler, device=device, sigmas=get_sampling_sigmas(num_inference_steps, shift))[0]   # :616-621
+        raise NotImplementedError(f"{type(self.scheduler).__name__}: the schedulers built are FlowUniPCMultistepScheduler and "
+                                  "FlowDPMSolverMultistepScheduler (fast_infer.py:328-337)")
+
+    def _window_sizes(self, o, ratio, has_source):
+        """The window options in latent cells: (temporal (n, overlap) or None, spatial ((th, tw), (oy, ox)) or None), checked."""
+        window_latents = tile_cells = None
+        if o.temporal_window is not None:
+            from .windows import window_latent_frames
+            window_latents = window_latent_frames(o.temporal_window, o.temporal_overlap, ratio)
+        if o.spatial_window is not None:
+            from .windows import spatial_window_cells
+            tile_cells = spatial_window_cells(o.spatial_window, o.spatial_overlap, getattr(getattr(self.vae, "config", None),
+                                              "spatial_compression_ratio", 8), self.transformer.config.patch_size[1])
+        wb = o.window_batch
+        for name, option in (("temporal_window", o.temporal_window), ("spatial_window", o.spatial_window)):
+            if option is None:
+                continue
+            if wb is not None and (isinstance(wb, bool) or not isinstance(wb, int) or wb < 1):
+                raise ValueError(f"window_batch={wb!r}: None (all windows in one forward) or a window count >= 1")
+            _require_source(has_source, f"{name}={option}: the windows are cut from a source clip")
+        return window_latents, tile_cells
+
+    def _mask_weights(self, o, latents, cc, G, source_frames, height, width):
+        """Edit inside a mask: the latent-cell weights uint8 [1 or B, Fs, hl, wl], made once (None without a mask)."""
+        if o.mask_args is None:
+            return None
+        from . import video_io
+        B, _, Ftot, hl, wl = latents.shape
+        lead = 1 if o.edit_mask.dim() == 3 else int(o.edit_mask.shape[0])
+        cells = (height // video_io.LATENT_CELL, width // video_io.LATENT_CELL)
+        if not _has_layout(Ftot, cc, G) or (hl, wl) != cells or lead not in (1, B):
+            raise ValueError(f"edit_mask: a mask {tuple(o.edit_mask.shape)} for latents of {B} samples, {Ftot} frames of {hl} x {wl} "
+                             f"cells; expected {_LAYOUT.format(cc, G)} frames of {cells[0]} x {cells[1]} cells and a mask for 1 or {B} samples")
+        weights = video_io.latent_edit_mask((o.edit_mask if o.edit_mask.dim() == 4 else o.edit_mask.unsqueeze(0)).to(latents.device),
+                                            grow=o.mask_args[0], grow_t=o.mask_args[1], feather=o.mask_args[2])
+        if weights.shape[1] != cc:
+            raise ValueError(f"edit_mask: {source_frames} mask frames are {weights.shape[1]} latent frames; the source segment has {cc}")
+        return weights
+
+    def _plan_windows(self, o, sizes, shape, cc, G, capture_graph):
+        """(plan, tiles) of a clip of latent `shape`: the temporal WindowPlan, or None where the clip fits one window (or the option
+        is off); the TilePlan of the spatial windows, or None where every frame fits one tile (or the option is off)."""
+        (window_latents, tile_cells), (_, _, Ftot, hl, wl) = sizes, shape
+        plan = tiles = None
+        for name, size in (("temporal_window", window_latents), ("spatial_window", tile_cells)):
+            if size is not None and not _has_layout(Ftot, cc, G):
+                raise ValueError(f"{name}={getattr(o, name)}: latents of {Ftot} frames are not {_LAYOUT.format(cc, G)}")
+        if window_latents is not None:
+            from .windows import window_plan
+            plan = window_plan(cc, *window_latents)
+            plan = plan if plan.K > 1 else None
+        if tile_cells is not None:
+            from .windows import TilePlan, window_plan
+            (tile_h, tile_w), (over_h, over_w) = tile_cells
+            plan_y, plan_x = window_plan(hl, tile_h, over_h), window_plan(wl, tile_w, over_w)
+            if plan_y.K * plan_x.K > 1:
+                # the t axis: the temporal windows, or one window of the whole clip without them
+                tiles = TilePlan(plan if plan is not None else window_plan(cc, max(cc, 2), 0), plan_y, plan_x)
+        if plan is not None or tiles is not None:
+            option = "spatial_window" if tiles is not None else "temporal_window"
+            if capture_graph == "loop":
+                raise NotImplementedError(f"{option} with capture_graph='loop': the windowed loop is not recorded as one graph "
+                                          "(use capture_graph='step')")
+            if getattr(self.transformer, "teacache", None) is not None:
+                raise NotImplementedError(f"{option} with TeaCache: it keeps one residual per call and counts calls, and a "
+                                          "windowed step is several windows (and possibly several calls)")
+        return plan, tiles
+
+    @contextmanager
+    def _transformer_settings(self, cache_context, skip_frames, mask_frames, local_cfg):
+        """What a call sets on the transformer for the loop and puts back however the loop ends: `cache_context` (the prompt is fixed across
+        steps; the context cache is cleared on both sides), `skip_source_frames`, `mask_source_frames`, the local-attention setting (if the
+        call switches it), opt-in the workspaces.  Yields whether the loop must zero a prediction's source frames itself (:736)."""
+        tr = self.transformer
+        prev_cache, prev_skip = getattr(tr, "cache_context", False), getattr(tr, "skip_source_frames", 0)
+        prev_mask, prev_local = getattr(tr, "mask_source_frames", None), getattr(tr, "local_attention", None)
+        try:
+            if hasattr(tr, "cache_context"):
+                tr.cache_context = cache_context
+            if hasattr(tr, "clear_context_cache"):
+                tr.clear_context_cache()            # never reuse another call's text K/V
+            if hasattr(tr, "skip_source_frames"):
+                tr.skip_source_frames = skip_frames   # noise_pred[:, :, :condition_count] is zeroed (:736): the last block need not produce it
+            if prev_mask is not None:
+                tr.mask_source_frames = mask_frames
+            yield prev_mask is None
+        finally:
+            if hasattr(tr, "cache_context"):
+                tr.cache_context = prev_cache
+            if hasattr(tr, "clear_context_cache"):
+                tr.clear_context_cache()            # releases the hoisted K/V^T and the prompt embeddings
+            if hasattr(tr, "skip_source_frames"):
+                tr.skip_source_frames = prev_skip
+            if prev_mask is not None:
+                tr.mask_source_frames = prev_mask
+            if local_cfg is not None:
+                if prev_local is None:
+                    tr.disable_local_attention()
+                else:
+                    tr.enable_local_attention(**prev_local)
+            if self.release_workspaces_after_denoise and hasattr(tr, "release_workspaces"):
+                # opt-in: 7 GB of activation buffers at 14B / 67k tokens handed back before the VAE decode (for hosts that share the
+                # device); the sets a captured graph replays from stay.  Off by default: every call would re-allocate and zero-fill the
+                # set, and a capture_graph='loop' capture call would allocate (and record the zero-fill of) its workspaces inside the graph.
+                tr.release_workspaces(keep_pinned=True)
+
+    def _guided_forward(self, forward, do_cfg, seq_len, fsi, gfi):
+        """A call's `guided(build, n, neg, pos, t, windows)`: the prediction for `n` samples at timestep `t`, guidance applied -- the ONE
+        place that decides about cfg_skip, calls the model and combines the halves.  `build(rep)` makes the model input, `rep` copies of
+        the samples one after the other; `neg` / `pos` are the samples' prompts; `windows`: they are windows of a clip, not a clip each.
+        A step the model's cfg_skip rule halves (enable_cfg_skip; cfg_optimization.py:5-38) returns the conditional prediction twice, and
+        guidance on two equal halves is that prediction itself: such a step calls the model with the conditional samples and prompts only.
+        `_cfg_skip_literal` keeps the reference's literal order (doubled batch through the model's rule, then guidance) reachable; both
+        give the same latents (tests/test_gpu_cfg_skip.py)."""
+        cfg_skip_now = getattr(self.transformer, "cfg_skip_now", None)
+        can_suspend = hasattr(self.transformer, "_cfg_skip_suspended")
+        def guided(build, n, neg, pos, t, windows):
+            half = do_cfg and cfg_skip_now is not None and cfg_skip_now(2 * n)
+            doubled = do_cfg and not (half and not self._cfg_skip_literal)
+            x = self.scheduler.scale_model_input(build(2 if doubled else 1), t)                     # :700
+            nb = x.shape[0]
+            # The model's own rule is suspended for a halved step's single batch (it already IS the conditional half) and left alone for
+            # its literal doubled one.  On any other step it halves ANY batch of two or more: a batch of windows is none of its business,
+            # a batch of whole clips stays its own (what an unguided B >= 2 call gets from a model with cfg_skip on is the model's affair).
+            suspend = ((not doubled) if half else windows) and can_suspend
+            if suspend:
+                self.transformer._cfg_skip_suspended = True
+            try:
+                noise_pred = forward(x=x, context=(neg + pos) if doubled else pos, t=t.expand(nb), seq_len=seq_len,    # :705, :721-728
+                                     frame_split_indices=fsi and [fsi] * nb, ground_frame_indices=gfi and [gfi] * nb)  # :713, :716-718
+            finally:
+                if suspend:
+                    self.transformer._cfg_skip_suspended = False
+            if doubled:
+                nu, nt = noise_pred.chunk(2)
+                noise_pred = nu + self.guidance_scale * (nt - nu)                                   # :731-733
+            return noise_pred
+        return guided
+
+    def _whole_clip_form(self, guided, cc, G, zero_source):
+        """The loop's `predict` for a clip that is one model input (:700-736): `cat([latents] * 2)` or the latents themselves, one
+        forward, guidance, the CoF mask.  Returns (predict, the target's first frame in the loop state, the state -> latents cut)."""
+        def predict(latents, neg, pos, i, t):
+            noise_pred = guided(lambda rep: torch.cat([latents] * 2) if rep == 2 else latents, latents.shape[0], neg, pos, t, False)
+            if zero_source:
+                noise_pred[:, :, :cc] = 0                                                       # :736
+            # else: already zero -- written by wan_unpatchify(zero_frames); CFG keeps it (0 + s * (0 - 0))
+            return noise_pred
+        return predict, cc + G, lambda latents: latents
+
+    def _windowed_form(self, guided, latents, plan, tiles, window_batch, cc, G):
+        """The loop's `predict` for a clip longer than the window (DESIGN.md "Temporal context windows").  The loop state is
+        [source | ground_0 .. ground_{K-1} | target]: every temporal window owns a grounding block (all start as the same noise: the
+        random stream of the call is unchanged), the target is shared.  A step gathers the K windows
+        [source[a:a+n] | ground_k | target[a:a+n]] out of it (wan_window_gather, which also writes the doubled batch of a guided
+        step), runs them as ONE forward of K * B samples (`window_batch` windows per forward if set), applies guidance per forward and
+        blends the K predictions into one for the state (wan_window_blend: CoF mask, each window's grounding, the weighted target);
+        the loop then steps the sampler ONCE on the whole state, and its callback receives the state in this windowed layout.  With spatial
+        context windows the windows are the K = Kt * Ky * Kx tiles of `tiles`, cut and blended by wan_tile_gather /
+        wan_tile_blend; the state has one grounding block per TEMPORAL window, shared by its spatial tiles.
+        Returns (the state made of `latents`, predict, the target's first frame in it, the cut back to [source | ground_0 | target])."""
+        from . import ops
+        if tiles is None:
+            K, Kt = plan.K, plan.K
+            alpha = torch.from_numpy(plan.alpha).to(latents.device)
+            gather = lambda s, k0, k1, rep: ops.window_gather(s, plan.starts, plan.window, G, k0, k1, rep=rep)
+            blend = lambda p: ops.window_blend(p, alpha, plan.starts, plan.frames, G)
+        else:
+            K, Kt = tiles.K, tiles.Kt
+            starts = (tiles.t.starts, tiles.y.starts, tiles.x.starts)
+            tables = tuple(torch.from_numpy(axis.alpha).to(latents.device) for axis in (tiles.t, tiles.y, tiles.x))
+            gather = lambda s, k0, k1, rep: ops.tile_gather(s, starts, tiles.shape, G, k0, k1, rep=rep)
+            blend = lambda p: ops.tile_blend(p, tables, starts, tiles.extent, G)
+        per_call = K if window_batch is None else min(int(window_batch), K)
+        def predict(state, neg, pos, i, t):
+            state = state.contiguous()
+            nB = state.shape[0]
+            preds = None
+            for k0 in range(0, K, per_call):
+                k1 = min(k0 + per_call, K)
+                nk = k1 - k0
+                noise_pred = guided(lambda rep: gather(state, k0, k1, rep), nk * nB, neg * nk, pos * nk, t, True)
+                if nk == K:
+                    preds = noise_pred
+                else:
+                    if preds is None:
+                        preds = torch.empty((K * nB,) + tuple(noise_pred.shape[1:]), device=noise_pred.device, dtype=noise_pred.dtype)
+                    preds[k0 * nB:k1 * nB].copy_(noise_pred)
+            return blend(preds.contiguous())
+        state = torch.cat([latents[:, :, :cc]] + [latents[:, :, cc:cc + G]] * Kt + [latents[:, :, cc + G:]], dim=2)
+        return state, predict, cc + Kt * G, lambda state: torch.cat([state[:, :, :cc + G], state[:, :, cc + Kt * G:]], dim=2)
+
+    def _denoise(self, latents, embeds, do_cfg, timesteps, predict, local, mask, step_kwargs, callback):
+        """THE step loop (:694-750), eager or recorded into a hipGraph: `predict(latents, neg, pos, i, t)` is one of the two forms above.
+        `local` = (enable_local_attention arguments, first local step) or None; `mask` = (weights, source frames, the target's first
+        frame) or None; `callback` = (callback_on_step_end, the names it wants, {name: prompt embeddings}) or None."""
+        neg, pos = (embeds[:len(embeds) // 2], embeds[len(embeds) // 2:]) if do_cfg else ([], embeds)    # [uncond | cond] under guidance (:605-608)
+        for i, t in enumerate(timesteps):                                                       # :694
+            self.transformer.current_steps = i
+            if self._interrupt:
+                continue
+            if local is not None:        # dense before `local_attention_from_step`, local from there on
+                if i >= local[1]:
+                    self.transformer.enable_local_attention(**local[0])
+                else:
+                    self.transformer.disable_local_attention()
+            noise_pred = predict(latents, neg, pos, i, t)
+            if mask is not None:
+                # Edit inside a mask (DESIGN.md 13.4): outside the mask the target's prediction becomes the one whose x0 is the source
+                # block of the state, (x_t - s) / sigma_i -- in place on the step's prediction, after guidance (and after the window
+                # blend).  The multistep history then holds the source there, the SDE variants keep their noise term, and the last step
+                # (sigma_next = 0) lands the region on the source latents to rounding; inside the mask nothing changes.
+                from . import ops
+                dt = torch.promote_types(noise_pred.dtype, latents.dtype)      # (both samplers widen to it themselves: an exact cast)
+                noise_pred = ops.masked_prediction_(noise_pred.to(dt).contiguous(), latents.to(dt), mask[0], mask[1], mask[2],
+                                                    float(self.scheduler.sigmas[i]))
+            latents = self.scheduler.step(noise_pred, t, latents, **step_kwargs, return_dict=False)[0]   # :740
+            if callback is not None:
+                # :742-750 -- the tensors named in callback_on_step_end_tensor_inputs; only `latents` coming back has an effect
+                # (there as here: the embeddings of the loop were concatenated before it started, :605-608)
+                callback_on_step_end, names, embeddings = callback
+                out = callback_on_step_end(self, i, t, {k: {"latents": latents, **embeddings}[k] for k in (names or ())})
+                if out:
+                    latents = out.pop("latents", latents)
+        return latents
+
+    def _denoise_as_one_graph(self, key, loop, latents, embeds, timesteps, has_callback):
+        """capture_graph='loop': `loop(latents, embeds)` as ONE hipGraph (videocof_amd.GraphedLoop): the first call of a signature runs
+        eagerly, the second captures, later ones replay.  `key`: what of this call is baked into the recorded launches."""
+        if has_callback:
+            raise NotImplementedError("capture_graph='loop' replays all steps in one launch: no per-step callback")
+        if not getattr(self.transformer, "cache_context", False):
+            raise NotImplementedError("capture_graph='loop' needs cache_context (the text K/V are part of the graph)")
+        cfg = self.scheduler.config
+        if cfg.get("algorithm_type") == "sde-dpmsolver++":
+            raise NotImplementedError("capture_graph='loop' with sde-dpmsolver++: the host generator's noise draws cannot be "
+                                      "recorded into a graph (use capture_graph='step')")
+        if self._graphed_loop is None or self._graphed_loop.model is not self.transformer:
+            from .graph import GraphedLoop
+            self._graphed_loop = GraphedLoop(self.transformer)
+        self.scheduler.set_begin_index(0)       # no device round trip (index_for_timestep) inside a capture
+        key = key + (int(cfg.solver_order), bool(cfg.lower_order_final), type(self.scheduler).__name__, cfg.get("algorithm_type"),
+                     cfg.get("solver_type"), bool(cfg.get("euler_at_final", False)),
+                     # which steps run on the conditional half only (enable_cfg_skip) is baked into the captured loop
+                     getattr(self.transformer, "cfg_skip_ratio", None), getattr(self.transformer, "num_inference_steps", None),
+                     bool(self._cfg_skip_literal))
+        def loop_fn(lat, emb):
+            self.scheduler._reset()
+            self.scheduler.set_begin_index(0)
+            return loop(lat, emb)
+        return self._graphed_loop(key, latents, embeds, loop_fn, keep=(timesteps, self.scheduler.sigmas))
+
+    def _decode_outputs(self, latents, output_type, cot, cc, G, compare_source, return_dict):
+        """:757-790 -- decode only the grounding and edit segments: (videos, ground_videos, edit_videos, compare_videos)."""
+        ground_video = edit_video = video_out = compare_out = None
+        if output_type == "latent":
+            return video_out, ground_video, edit_video, compare_out
+        if output_type not in ("numpy", "uint8"):
+            raise ValueError(f"output_type {output_type!r} not supported ('numpy', 'uint8' or 'latent')")
+        if self.vae is None:
+            raise ValueError(f"output_type={output_type!r} needs a VAE; use output_type='latent'")
+        Ftot, u8 = latents.shape[2], output_type == "uint8"    # uint8 [B, T, H, W, 3] frames (wan_video_to_frames_u8), not float32 [B, 3, T, H, W]
+        edit_dev = [] if compare_source is not None else None     # the edit segment's device frames, kept for the compare clip only
+        if cot:
+            g0, g1 = cc, cc + G
+            # grounding | edit frames side by side in ONE page-locked clip (what the reference builds with np.concatenate, :786): each
+            # segment is decoded straight into its frame slice, `ground_videos` / `edit_videos` are views of `videos`.  As bytes, the
+            # kernel first writes both into their frames of ONE device clip; one contiguous run per segment and sample is copied from it
+            tcr, scr = self.vae.config.temporal_compression_ratio, self.vae.config.spatial_compression_ratio
+            nfr = lambda n: 1 + tcr * (n - 1) if n > 0 else 0
+            ng = nfr(g1 - g0) if (g1 > g0 and g0 < Ftot) else 0
+            ne = nfr(Ftot - g1) if g1 < Ftot else 0
+            B, H, W = latents.shape[0], latents.shape[3] * scr, latents.shape[4] * scr
+            clip = dev_clip = None
+            if ng + ne > 0 and (u8 or latents.is_cuda):
+                shape, dtype = ((B, ng + ne, H, W, 3), torch.uint8) if u8 else ((B, 3, ng + ne, H, W), torch.float32)
+                clip = torch.empty(shape, dtype=dtype, pin_memory=True)
+                dev_clip = torch.empty(clip.shape, dtype=torch.uint8, device=latents.device) if u8 else None
+
+            def segment(lat, a, b, keep=None):      # latent frames `lat` decoded into frames [a, b) of the clip
+                if u8:
+                    return self._decode_frames_u8(lat, clip[:, a:b], dev_clip, a, keep)
+                return self.decode_latents(lat, None if clip is None else clip[:, :, a:b])
+            if ng:
+                ground_video = segment(latents[:, :, g0:g1], 0, ng)
+            if ne:
+                edit_video = segment(latents[:, :, g1:], ng, ng + ne, edit_dev)
+            if clip is not None:
+                video_out = clip.numpy()
+            elif not u8:
+                video_out = np.concatenate([v for v in (ground_video, edit_video) if v is not None], axis=2)
+        elif cc < Ftot:
+            video_out = edit_video = (self._decode_frames_u8(latents[:, :, cc:], None, keep=edit_dev) if edit_dev is not None
+                                      else self.decode_latents(latents[:, :, cc:], as_uint8=u8))
+        if edit_dev:
+            from . import video_io
+            src = (compare_source if compare_source.dim() == 5 else compare_source.unsqueeze(0)).to(edit_dev[0].device)
+            T, H, W = (min(int(a), int(b)) for a, b in zip(src.shape[1:4], edit_dev[0].shape[1:4]))
+            pinned = torch.empty((edit_dev[0].shape[0], T, H, 2 * W, 3), dtype=torch.uint8, pin_memory=True)
+            compare_out = video_io.compare_frames(src, edit_dev[0], out=pinned).numpy()
+        if not return_dict:
+            video_out, ground_video, edit_video, compare_out = (torch.from_numpy(v) if isinstance(v, np.ndarray) else v
+                                                                for v in (video_out, ground_video, edit_video, compare_out))
+        return video_out, ground_video, edit_video, compare_out
+
     @torch.no_grad()
     def __call__(self, video: Optional[torch.Tensor] = None, prompt=None, negative_prompt=None,
                  height: int = 480, width: int = 720, num_frames: int = 49, source_frames: int = 33,
@@ -324,115 +722,32 @@ class WanPipeline:
                  source_latents: Optional[torch.Tensor] = None, device=None,
                  weight_dtype: torch.dtype = torch.bfloat16, cache_context: bool = True,
                  skip_source_prediction: bool = True, capture_graph=False, **switches):
-        # `compare=False` is the one keyword in `switches` (as `as_uint8` is decode_latents'): the named parameters stay the reference's
-        # plus the extensions tests/test_oracle_vs_reference.py lists.  compare=True: also return the reference's compare clip (save_side_by_side, fast_infer.py:183-206, as its writer's bytes) in
-        # `compare_videos`, composed on the device from the uint8 source frames and the edit segment (video_io.compare_frames)
-        compare = bool(switches.pop("compare", False))
-        # `temporal_window=None, temporal_overlap=16, window_batch=None` (PIXEL frames; window_batch in windows): denoise a clip longer
-        # than `temporal_window` as overlapping windows of that length, blended every step -- see `denoise_windows` below
-        temporal_window = switches.pop("temporal_window", None)
-        temporal_overlap = switches.pop("temporal_overlap", 16)
-        window_batch = switches.pop("window_batch", None)
-        # `spatial_window=None, spatial_overlap=(96, 128)` ((rows, columns) in PIXELS): denoise frames larger than `spatial_window` as
-        # overlapping tiles of that size, blended every step; combines with `temporal_window`, `window_batch` then
-        # counts tiles.  The default overlap is a guess: no real checkpoint has been run with it.  Opt-in and lossy; no quality claim.
-        spatial_window = switches.pop("spatial_window", None)
-        spatial_overlap = switches.pop("spatial_overlap", (96, 128))
-        # `local_attention=None, local_attention_from_step=0`: self-attention over a neighbourhood instead of every token (DESIGN.md
-        # 13.3; WanTransformer3DModel.enable_local_attention).  A (window_frames, window_rows) pair or a dict of that method's
-        # arguments; steps before `local_attention_from_step` run dense.  Opt-in and lossy; no quality claim.  The model's own
-        # setting is restored when the call returns.
-        local_attention = switches.pop("local_attention", None)
-        local_from = switches.pop("local_attention_from_step", 0)
-        # `edit_mask=None, edit_mask_grow=(1, 0), edit_mask_feather=1`: where the edit may happen.  uint8 [T, H, W] or
-        # [B, T, H, W] with T = source_frames and H x W = height x width, host or device; 255 = edit freely, 0 = keep the source.  Every
-        # step the target's prediction outside the mask is replaced by the one whose x0 is the source (wan_masked_prediction), so that
-        # region ends on the source latents to rounding.  `edit_mask_grow` = (latent cells, latent frames) of margin, `edit_mask_feather`
-        # = latent cells of soft edge (video_io.latent_edit_mask); the defaults are guesses.  Opt-in, changes outputs by design; no
-        # quality claim.
-        edit_mask = switches.pop("edit_mask", None)
-        edit_mask_grow = switches.pop("edit_mask_grow", (1, 0))
-        edit_mask_feather = switches.pop("edit_mask_feather", 1)
-        if switches:
-            raise TypeError(f"__call__() got an unexpected keyword argument {next(iter(switches))!r}")
-        mask_args = None
-        if edit_mask is not None:
-            from . import video_io
-            if video is None and source_latents is None and latents is None:
-                raise ValueError("edit_mask: outside the mask the clip is kept on its source; this call has none "
-                                 "(no `video`, `source_latents` or `latents`)")
-            if not isinstance(edit_mask_grow, (tuple, list)) or len(edit_mask_grow) != 2:
-                raise ValueError(f"edit_mask_grow={edit_mask_grow!r}: a (latent cells, latent frames) pair")
-            mask_args = video_io._latent_mask_args("edit_mask", edit_mask_grow[0], edit_mask_grow[1], edit_mask_feather)
-            want = f"uint8 [{source_frames}, {height}, {width}] or [B, {source_frames}, {height}, {width}]"
-            try:
-                edit_mask = video_io._as_mask(edit_mask, "edit_mask")
-            except ValueError as e:
-                raise ValueError(f"{e}; expected {want}") from None
-            if tuple(edit_mask.shape[-3:]) != (source_frames, height, width):
-                raise ValueError(f"edit_mask: expected {want} (source_frames, height, width of this call), got {tuple(edit_mask.shape)}")
-            if capture_graph == "loop":
-                raise NotImplementedError("edit_mask with capture_graph='loop': the recorded loop does not hold the mask's weights or "
-                                          "the per-step sigma of the replacement (use capture_graph='step')")
-        compare_source = None
-        if compare:
-            if output_type != "uint8":
-                raise ValueError(f"compare=True composes the compare clip from uint8 frames on the device: it needs "
-                                 f"output_type='uint8', not {output_type!r}")
-            compare_source = torch.from_numpy(video) if isinstance(video, np.ndarray) else video
-            if not torch.is_tensor(compare_source) or compare_source.dtype != torch.uint8 or compare_source.dim() not in (4, 5) \
-                    or compare_source.shape[-1] != 3:
-                raise ValueError("compare=True needs the uint8 source frames as `video` ([T, H, W, 3] or [B, T, H, W, 3]), got "
-                                 f"{getattr(compare_source, 'dtype', type(compare_source))} "
-                                 f"{tuple(getattr(compare_source, 'shape', ()))}")
+        # -- the switches (see _parse_switches for what they are), checked before anything runs
+        has_source = video is not None or source_latents is not None or latents is not None
+        opt = self._parse_switches(switches, video, has_source, source_frames, height, width, output_type, capture_graph)
         # `timesteps`: with either scheduler built here the reference never looks at it (pipeline_wan.py:613-621: UniPC takes
         # set_timesteps(num_inference_steps, device=, shift=), DPM++ the sigmas of get_sampling_sigmas); accepted and ignored here too.
         del timesteps
-        num_videos_per_prompt = 1                  # :561 -- the reference overrides the argument at the top of __call__, whatever was passed
         self.check_inputs(prompt, height, width, negative_prompt, callback_on_step_end_tensor_inputs, prompt_embeds, negative_prompt_embeds)
-        self._guidance_scale = guidance_scale
+        self._guidance_scale, self._interrupt = guidance_scale, False
         self._attention_kwargs = attention_kwargs                                               # :575 (stored, read by nothing, as there)
-        self._interrupt = False
         device = torch.device(device) if device is not None else self.transformer.device
         do_cfg = guidance_scale > 1.0                                                           # :592
+        # -- the prompt
         t_stage = self._stage("text_encoder")
         prompt_embeds, negative_prompt_embeds = self.encode_prompt(
-            prompt, negative_prompt, do_cfg, num_videos_per_prompt=num_videos_per_prompt, prompt_embeds=prompt_embeds,
-            negative_prompt_embeds=negative_prompt_embeds, max_sequence_length=max_sequence_length, device=device)
+            prompt, negative_prompt, do_cfg, num_videos_per_prompt=1, prompt_embeds=prompt_embeds,       # (1: the reference overrides the
+            negative_prompt_embeds=negative_prompt_embeds, max_sequence_length=max_sequence_length, device=device)   # argument, :561)
         self._stage("text_encoder", t_stage)
         in_prompt_embeds = (negative_prompt_embeds + prompt_embeds) if do_cfg else prompt_embeds   # :605-608
-
-        if isinstance(self.scheduler, FlowUniPCMultistepScheduler):
-            self.scheduler.set_timesteps(num_inference_steps, device=device, shift=shift)       # :613-615
-            timesteps = self.scheduler.timesteps
-        elif isinstance(self.scheduler, FlowDPMSolverMultistepScheduler):
-            timesteps, _ = retrieve_timesteps(self.scheduler, device=device,
-                                              sigmas=get_sampling_sigmas(num_inference_steps, shift))   # :616-621
-        else:
-            raise NotImplementedError(f"{type(self.scheduler).__name__}: the schedulers built are FlowUniPCMultistepScheduler and "
-                                      "FlowDPMSolverMultistepScheduler (fast_infer.py:328-337)")
+        # -- the timesteps
+        timesteps = self._set_timesteps(num_inference_steps, shift, device)
         extra_step_kwargs = self.prepare_extra_step_kwargs(generator, eta)                       # :682
         self._num_timesteps = len(timesteps)
-
+        # -- the latents [source | grounding | target]
         ratio = getattr(self.vae, "temporal_compression_ratio", 4)
         condition_count = 1 if source_frames == 1 else (source_frames - 1) // ratio + 1         # :630-631
-        window_latents = tile_cells = None
-        if temporal_window is not None:
-            from .windows import window_latent_frames, window_plan
-            window_latents = window_latent_frames(temporal_window, temporal_overlap, ratio)
-        if spatial_window is not None:
-            from .windows import TilePlan, spatial_window_cells, window_plan
-            tile_cells = spatial_window_cells(spatial_window, spatial_overlap,
-                                              getattr(getattr(self.vae, "config", None), "spatial_compression_ratio", 8),
-                                              self.transformer.config.patch_size[1])
-        for name, option in (("temporal_window", temporal_window), ("spatial_window", spatial_window)):
-            if option is None:
-                continue
-            if window_batch is not None and (isinstance(window_batch, bool) or not isinstance(window_batch, int) or window_batch < 1):
-                raise ValueError(f"window_batch={window_batch!r}: None (all windows in one forward) or a window count >= 1")
-            if video is None and source_latents is None and latents is None:
-                raise ValueError(f"{name}={option}: the windows are cut from a source clip; this call has none "
-                                 "(no `video`, `source_latents` or `latents`)")
+        window_sizes = self._window_sizes(opt, ratio, has_source)
         ground_latent_count = 0
         t_stage = self._stage("vae_encode")
         if cot:
@@ -444,373 +759,56 @@ class WanPipeline:
             latents = self.prepare_video_latents_new(video, dtype=weight_dtype, device=device, generator=generator,
                                                      condition_count=condition_count, latents=latents, source_latents=source_latents)
         self._stage("vae_encode", t_stage)
-        B, _, Ftot, hl, wl = latents.shape
-        ps = self.transformer.config.patch_size
-        mask_weights = None          # edit inside a mask: the latent-cell weights uint8 [1 or B, Fs, hl, wl], made once
-        if mask_args is not None:
-            lead = 1 if edit_mask.dim() == 3 else int(edit_mask.shape[0])
-            cells = (height // video_io.LATENT_CELL, width // video_io.LATENT_CELL)
-            if Ftot != 2 * condition_count + ground_latent_count or (hl, wl) != cells or lead not in (1, B):
-                raise ValueError(f"edit_mask: a mask {tuple(edit_mask.shape)} for latents of {B} samples, {Ftot} frames of {hl} x {wl} "
-                                 f"cells; expected [source | grounding | target] = [{condition_count} | {ground_latent_count} | "
-                                 f"{condition_count}] frames of {cells[0]} x {cells[1]} cells and a mask for 1 or {B} samples")
-            mask_weights = video_io.latent_edit_mask((edit_mask if edit_mask.dim() == 4 else edit_mask.unsqueeze(0)).to(latents.device),
-                                                     grow=mask_args[0], grow_t=mask_args[1], feather=mask_args[2])
-            if mask_weights.shape[1] != condition_count:
-                raise ValueError(f"edit_mask: {source_frames} mask frames are {mask_weights.shape[1]} latent frames; the source "
-                                 f"segment has {condition_count}")
-        plan = None                  # temporal context windows: None = the clip fits one window (or the option is off): today's path
-        if window_latents is not None:
-            if Ftot != 2 * condition_count + ground_latent_count:
-                raise ValueError(f"temporal_window={temporal_window}: latents of {Ftot} frames are not [source | grounding | target] = "
-                                 f"[{condition_count} | {ground_latent_count} | {condition_count}]")
-            plan = window_plan(condition_count, *window_latents)
-            plan = plan if plan.K > 1 else None
-        tiles = None                 # spatial context windows: None = every frame fits one tile (or the option is off): the path above
-        if tile_cells is not None:
-            if Ftot != 2 * condition_count + ground_latent_count:
-                raise ValueError(f"spatial_window={spatial_window}: latents of {Ftot} frames are not [source | grounding | target] = "
-                                 f"[{condition_count} | {ground_latent_count} | {condition_count}]")
-            (tile_h, tile_w), (over_h, over_w) = tile_cells
-            plan_y, plan_x = window_plan(hl, tile_h, over_h), window_plan(wl, tile_w, over_w)
-            if plan_y.K * plan_x.K > 1:
-                # the t axis: the temporal windows, or one window of the whole clip without them
-                tiles = TilePlan(plan if plan is not None else window_plan(condition_count, max(condition_count, 2), 0), plan_y, plan_x)
-        windows = tiles if tiles is not None else plan
-        if windows is not None:
-            option = "spatial_window" if tiles is not None else "temporal_window"
-            if capture_graph == "loop":
-                raise NotImplementedError(f"{option} with capture_graph='loop': the windowed loop is not recorded as one graph "
-                                          "(use capture_graph='step')")
-            if getattr(self.transformer, "teacache", None) is not None:
-                raise NotImplementedError(f"{option} with TeaCache: it keeps one residual per call and counts calls, and a "
-                                          "windowed step is several windows (and possibly several calls)")
-            # the loop state [source | ground_0 .. ground_{Kt-1} | target]: every temporal window owns a grounding block (all start as
-            # the same noise: the random stream of the call is unchanged; the spatial tiles of a temporal window share its block),
-            # the target is shared
-            cc, g1 = condition_count, condition_count + ground_latent_count
-            blocks = tiles.Kt if tiles is not None else plan.K
-            latents = torch.cat([latents[:, :, :cc]] + [latents[:, :, cc:g1]] * blocks + [latents[:, :, g1:]], dim=2)
-        win_n = None if windows is None else tiles.t.window if tiles is not None else plan.window       # source frames of one window
-        win_frames = Ftot if windows is None else 2 * win_n + ground_latent_count                # frames of one forward
-        win_cc = condition_count if windows is None else win_n                                   # its source frames
-        win_hw = hl * wl if tiles is None else tiles.y.window * tiles.x.window                   # its latent cells per frame
-        seq_len = math.ceil(win_hw / (ps[1] * ps[2]) * win_frames)                               # :686-689
+        # -- the mask and the windows; what one forward holds: the whole clip, or one window of `win_n` source frames and `win_hw` cells
+        mask_weights = self._mask_weights(opt, latents, condition_count, ground_latent_count, source_frames, height, width)
+        plan, tiles = self._plan_windows(opt, window_sizes, latents.shape, condition_count, ground_latent_count, capture_graph)
+        windowed = plan is not None or tiles is not None
+        win_n = condition_count if not windowed else tiles.t.window if tiles is not None else plan.window
+        win_hw = latents.shape[3] * latents.shape[4] if tiles is None else tiles.y.window * tiles.x.window
+        win_frames = latents.shape[2] if not windowed else 2 * win_n + ground_latent_count
+        seq_len = math.ceil(win_hw / math.prod(self.transformer.config.patch_size[1:]) * win_frames)     # :686-689
         self.transformer.num_inference_steps = num_inference_steps
-        prev_cache = getattr(self.transformer, "cache_context", False)
-        if hasattr(self.transformer, "cache_context"):
-            self.transformer.cache_context = cache_context    # the prompt is fixed across steps
-        if hasattr(self.transformer, "clear_context_cache"):
-            self.transformer.clear_context_cache()            # never reuse another call's text K/V
-        prev_skip = getattr(self.transformer, "skip_source_frames", 0)
-        if hasattr(self.transformer, "skip_source_frames"):
-            # noise_pred[:, :, :condition_count] is zeroed below (:736): the last block need not produce it
-            self.transformer.skip_source_frames = win_cc if skip_source_prediction else 0
-
-        # the CoF mask of :736 on the device: the unpatchify kernel writes zeros for the source frames
-        prev_mask = getattr(self.transformer, "mask_source_frames", None)
-        if prev_mask is not None:
-            self.transformer.mask_source_frames = win_cc
-        forward = self.transformer
         if capture_graph not in (False, True, "step", "loop"):
             raise ValueError(f"capture_graph={capture_graph!r}: False, True / 'step' (one hipGraph per forward) or 'loop' (the whole loop)")
-        local_cfg = None
-        if local_attention is not None:
-            if isinstance(local_attention, dict):
-                local_cfg = dict(local_attention)
-            elif isinstance(local_attention, (tuple, list)) and len(local_attention) == 2:
-                local_cfg = dict(zip(("window_frames", "window_rows"), local_attention))
-            else:
-                local_cfg = {}
-            if set(local_cfg) - {"window_frames", "window_rows", "sink_frames", "dense_layers"} or not {"window_frames", "window_rows"} <= set(local_cfg):
-                raise ValueError(f"local_attention={local_attention!r}: a (window_frames, window_rows) pair or a dict of the "
-                                 "enable_local_attention arguments")
-            if isinstance(local_from, bool) or not isinstance(local_from, int) or local_from < 0:
-                raise ValueError(f"local_attention_from_step={local_from!r}: a step index >= 0")
-            if capture_graph == "loop":
-                raise NotImplementedError("local_attention with capture_graph='loop': the recorded loop does not hold the key-tile "
-                                          "plans (use capture_graph='step')")
-        prev_local = getattr(self.transformer, "local_attention", None)
-
-        def local_step(i):
-            """Step i of a `local_attention` call: dense before `local_attention_from_step`, local from there on."""
-            if local_cfg is None:
-                return
-            if i >= local_from:
-                self.transformer.enable_local_attention(**local_cfg)
-            else:
-                self.transformer.disable_local_attention()
-        if capture_graph in (True, "step"):
-            # one hipGraph per call shape, kept across calls (videocof_amd/graph.py): step 0 of the first call runs
-            # eagerly, step 1 is captured, every later step (and call) is a replay -- bit-identical latents
-            if self._graphed is None or self._graphed.model is not self.transformer:
-                from .graph import GraphedForward
-                self._graphed = GraphedForward(self.transformer)
-            forward = self._graphed
-
-        use_rope_map = repeat_rope and (video is not None or source_latents is not None or latents is not None)
-
-        cfg_skip_now = getattr(self.transformer, "cfg_skip_now", None)
-
-        def masked(noise_pred, sample, target_frame0, i):
-            """Edit inside a mask, step i: outside the mask the target's prediction becomes the one whose x0 is the
-            source block of `sample`, (x_t - s) / sigma_i -- in place on the step's prediction, after guidance (and after the window
-            blend).  The multistep history then holds the source there, the SDE variants keep their noise term, and the last step
-            (sigma_next = 0) lands the region on the source latents to rounding; inside the mask nothing changes."""
-            from . import ops
-            dt = torch.promote_types(noise_pred.dtype, sample.dtype)      # (both samplers widen to it themselves: an exact cast)
-            return ops.masked_prediction_(noise_pred.to(dt).contiguous(), sample.to(dt), mask_weights, condition_count, target_frame0,
-                                          float(self.scheduler.sigmas[i]))
-
-        def denoise(latents, embeds):
-            """The loop of :694-740 on `latents` with the prompt embeddings `embeds`; eager, or recorded into a hipGraph."""
-            for i, t in enumerate(timesteps):                                                   # :694
-                self.transformer.current_steps = i
-                if self._interrupt:
-                    continue
-                local_step(i)
-                # A step the model's cfg_skip rule halves (enable_cfg_skip; cfg_optimization.py:5-38) returns the conditional
-                # prediction twice, and guidance on two equal halves is that prediction itself: nu + g * (nt - nu) = nu + g * 0 = nu.
-                # So such a step calls the model with the conditional sample and embeddings only -- no doubled batch, no guidance
-                # arithmetic.  `_cfg_skip_literal` keeps the reference's literal order (doubled batch through the model's rule, then
-                # guidance) reachable; both give the same latents (tests/test_gpu_cfg_skip.py).
-                half = do_cfg and cfg_skip_now is not None and cfg_skip_now(2 * latents.shape[0])
-                short = half and not self._cfg_skip_literal
-                step_embeds = embeds[len(embeds) // 2:] if short else embeds
-                latent_model_input = torch.cat([latents] * 2) if do_cfg and not short else latents   # :700
-                latent_model_input = self.scheduler.scale_model_input(latent_model_input, t)
-                timestep = t.expand(latent_model_input.shape[0])                                # :705
-                nb = latent_model_input.shape[0]
-                fsi = gfi = None
-                # :713 is `if repeat_rope and video is not None`, and the reference cannot run without `video` at all
-                # (`video.to(...)` at :397 precedes the `latents` short-cut), so on every call the reference accepts
-                # the condition is just `repeat_rope`.  Here `video` may be omitted when `latents` (reference argument)
-                # or `source_latents` (extension) carry the encoded source: such calls are treated like the reference
-                # treats the same call WITH its video; a call with none of the three has no source segment and keeps
-                # plain T2V positions.  Documented in INTEGRATION.md section B.
-                if use_rope_map:
-                    fsi = [condition_count] * nb                                                # :713
-                    if cot:
-                        gfi = [(condition_count, condition_count + ground_latent_count)] * nb  # :716-718
-                if short:
-                    self.transformer._cfg_skip_suspended = True       # this call already is the conditional half
-                try:
-                    noise_pred = forward(x=latent_model_input, context=step_embeds, t=timestep,
-                                         seq_len=seq_len, frame_split_indices=fsi,
-                                         ground_frame_indices=gfi)                              # :721-728
-                finally:
-                    if short:
-                        self.transformer._cfg_skip_suspended = False
-                if do_cfg and not short:
-                    nu, nt = noise_pred.chunk(2)
-                    noise_pred = nu + self.guidance_scale * (nt - nu)                           # :731-733
-                if prev_mask is None:
-                    noise_pred[:, :, :condition_count] = 0                                      # :736
-                # else: already zero -- written by wan_unpatchify(zero_frames); CFG keeps it (0 + s * (0 - 0))
-                if mask_weights is not None:
-                    noise_pred = masked(noise_pred, latents, condition_count + ground_latent_count, i)
-                latents = self.scheduler.step(noise_pred, t, latents, **extra_step_kwargs, return_dict=False)[0]   # :740
-                if callback_on_step_end is not None:
-                    # :742-750 -- the tensors named in callback_on_step_end_tensor_inputs; only `latents` coming back has an effect
-                    # (there as here: the embeddings of the loop were concatenated before it started, :605-608)
-                    vals = {"latents": latents, "prompt_embeds": prompt_embeds, "negative_prompt_embeds": negative_prompt_embeds}
-                    out = callback_on_step_end(self, i, t, {k: vals[k] for k in (callback_on_step_end_tensor_inputs or ())})
-                    if out:
-                        latents = out.pop("latents", latents)
-            return latents
-
-        def denoise_windows(state, embeds):
-            """The same loop over a clip longer than the window (DESIGN.md "Temporal context windows").  `state` is
-            [source | ground_0 .. ground_{K-1} | target]; a step gathers the K windows [source[a:a+n] | ground_k | target[a:a+n]]
-            out of it (wan_window_gather, which also writes the doubled batch of a guided step), runs them as ONE forward of
-            K * B samples (`window_batch` windows per forward if set), applies guidance per window, blends the K predictions into
-            one for the state (wan_window_blend: CoF mask, each window's grounding, the weighted target) and steps the sampler
-            ONCE on the whole state.  The callback receives the state in this windowed layout.
-            With spatial context windows the windows are the K = Kt * Ky * Kx tiles of `tiles`, cut and blended by
-            wan_tile_gather / wan_tile_blend; the state has one grounding block per TEMPORAL window."""
-            from . import ops
-            G = ground_latent_count
-            if tiles is None:
-                K, Kt, n = plan.K, plan.K, plan.window
-                alpha = torch.from_numpy(plan.alpha).to(state.device)
-                gather = lambda s, k0, k1, rep: ops.window_gather(s, plan.starts, n, G, k0, k1, rep=rep)
-                blend = lambda p: ops.window_blend(p, alpha, plan.starts, plan.frames, G)
-            else:
-                K, Kt, n = tiles.K, tiles.Kt, tiles.t.window
-                starts = (tiles.t.starts, tiles.y.starts, tiles.x.starts)
-                tables = tuple(torch.from_numpy(axis.alpha).to(state.device) for axis in (tiles.t, tiles.y, tiles.x))
-                gather = lambda s, k0, k1, rep: ops.tile_gather(s, starts, tiles.shape, G, k0, k1, rep=rep)
-                blend = lambda p: ops.tile_blend(p, tables, starts, tiles.extent, G)
-            per_call = K if window_batch is None else min(int(window_batch), K)
-            neg, pos = (embeds[:len(embeds) // 2], embeds[len(embeds) // 2:]) if do_cfg else ([], embeds)
-            can_suspend = hasattr(self.transformer, "_cfg_skip_suspended")
-            for i, t in enumerate(timesteps):
-                self.transformer.current_steps = i
-                if self._interrupt:
-                    continue
-                local_step(i)
-                state = state.contiguous()
-                nB = state.shape[0]
-                preds = None
-                for k0 in range(0, K, per_call):
-                    k1 = min(k0 + per_call, K)
-                    nk = k1 - k0
-                    # cfg_skip as in `denoise`: a halved step runs the conditional windows only.  The model's own rule halves ANY
-                    # batch of two or more samples, which a batch of windows is: it stays suspended unless the literal order is asked for
-                    half = do_cfg and cfg_skip_now is not None and cfg_skip_now(2 * nk * nB)
-                    doubled = do_cfg and not (half and not self._cfg_skip_literal)
-                    x = gather(state, k0, k1, 2 if doubled else 1)
-                    x = self.scheduler.scale_model_input(x, t)
-                    nb = x.shape[0]
-                    fsi = [n] * nb if use_rope_map else None
-                    gfi = [(n, n + G)] * nb if use_rope_map and cot else None
-                    suspend = can_suspend and not (half and doubled)
-                    if suspend:
-                        self.transformer._cfg_skip_suspended = True
-                    try:
-                        noise_pred = forward(x=x, context=(neg * nk + pos * nk) if doubled else pos * nk, t=t.expand(nb),
-                                             seq_len=seq_len, frame_split_indices=fsi, ground_frame_indices=gfi)
-                    finally:
-                        if suspend:
-                            self.transformer._cfg_skip_suspended = False
-                    if doubled:
-                        nu, nt = noise_pred.chunk(2)
-                        noise_pred = nu + self.guidance_scale * (nt - nu)
-                    if nk == K:
-                        preds = noise_pred
-                    else:
-                        if preds is None:
-                            preds = torch.empty((K * nB,) + tuple(noise_pred.shape[1:]), device=noise_pred.device, dtype=noise_pred.dtype)
-                        preds[k0 * nB:k1 * nB].copy_(noise_pred)
-                noise_pred = blend(preds.contiguous())
-                if mask_weights is not None:
-                    noise_pred = masked(noise_pred, state, condition_count + Kt * G, i)
-                state = self.scheduler.step(noise_pred, t, state, **extra_step_kwargs, return_dict=False)[0]
-                if callback_on_step_end is not None:
-                    vals = {"latents": state, "prompt_embeds": prompt_embeds, "negative_prompt_embeds": negative_prompt_embeds}
-                    out = callback_on_step_end(self, i, t, {k: vals[k] for k in (callback_on_step_end_tensor_inputs or ())})
-                    if out:
-                        state = out.pop("latents", state)
-            # [source | ground_0 | target]: the shape a whole-clip call returns
-            Fs = condition_count
-            return torch.cat([state[:, :, :Fs + G], state[:, :, Fs + Kt * G:]], dim=2)
-
+        local_cfg = _local_attention_args(opt.local_attention, opt.local_from, capture_graph)
+        # :713 is `if repeat_rope and video is not None`, and the reference cannot run without `video` at all (`video.to(...)` at :397 precedes
+        # the `latents` short-cut), so on every call the reference accepts the condition is just `repeat_rope`.  Here `video` may be omitted
+        # when `latents` (reference argument) or `source_latents` (extension) carry the encoded source: such calls are treated like the reference
+        # treats the same call WITH its video; a call with none of the three has no source segment and keeps plain T2V positions.
+        use_rope_map = repeat_rope and has_source
+        # -- denoise
         t_stage = self._stage("denoise_loop")
-        try:
-            if windows is not None:
-                latents = denoise_windows(latents, in_prompt_embeds)
-            elif capture_graph == "loop":
-                # the whole loop as ONE hipGraph (videocof_amd.GraphedLoop): first call of a signature eager, second captures
-                if callback_on_step_end is not None:
-                    raise NotImplementedError("capture_graph='loop' replays all steps in one launch: no per-step callback")
-                if not getattr(self.transformer, "cache_context", False):
-                    raise NotImplementedError("capture_graph='loop' needs cache_context (the text K/V are part of the graph)")
-                if self.scheduler.config.get("algorithm_type") == "sde-dpmsolver++":
-                    raise NotImplementedError("capture_graph='loop' with sde-dpmsolver++: the host generator's noise draws cannot be "
-                                              "recorded into a graph (use capture_graph='step')")
-                if self._graphed_loop is None or self._graphed_loop.model is not self.transformer:
-                    from .graph import GraphedLoop
-                    self._graphed_loop = GraphedLoop(self.transformer)
-                self.scheduler.set_begin_index(0)       # no device round trip (index_for_timestep) inside a capture
-                key = (int(num_inference_steps), float(shift), bool(do_cfg), float(guidance_scale) if do_cfg else 0.0,
-                       int(condition_count), int(ground_latent_count), bool(cot), bool(use_rope_map), int(seq_len),
-                       int(self.scheduler.config.solver_order), bool(self.scheduler.config.lower_order_final),
-                       type(self.scheduler).__name__, self.scheduler.config.get("algorithm_type"), self.scheduler.config.get("solver_type"),
-                       bool(self.scheduler.config.get("euler_at_final", False)),
-                       # which steps run on the conditional half only (enable_cfg_skip) is baked into the captured loop
-                       getattr(self.transformer, "cfg_skip_ratio", None), getattr(self.transformer, "num_inference_steps", None),
-                       bool(self._cfg_skip_literal))
-
-                def loop_fn(lat, embeds):
-                    self.scheduler._reset()
-                    self.scheduler.set_begin_index(0)
-                    return denoise(lat, embeds)
-                latents = self._graphed_loop(key, latents, in_prompt_embeds, loop_fn, keep=(timesteps, self.scheduler.sigmas))
+        with self._transformer_settings(cache_context, win_n if skip_source_prediction else 0, win_n, local_cfg) as zero_source:
+            forward = self.transformer
+            if capture_graph in (True, "step"):
+                # one hipGraph per call shape, kept across calls (videocof_amd/graph.py): step 0 of the first call runs
+                # eagerly, step 1 is captured, every later step (and call) is a replay -- bit-identical latents
+                if self._graphed is None or self._graphed.model is not self.transformer:
+                    from .graph import GraphedForward
+                    self._graphed = GraphedForward(self.transformer)
+                forward = self._graphed
+            guided = self._guided_forward(forward, do_cfg, seq_len, win_n if use_rope_map else None,
+                             (win_n, win_n + ground_latent_count) if use_rope_map and cot else None)
+            if windowed:
+                latents, predict, target_frame0, cut = self._windowed_form(guided, latents, plan, tiles, opt.window_batch,
+                                                                           condition_count, ground_latent_count)
             else:
-                latents = denoise(latents, in_prompt_embeds)
-        finally:
-            if hasattr(self.transformer, "cache_context"):
-                self.transformer.cache_context = prev_cache
-            if hasattr(self.transformer, "clear_context_cache"):
-                self.transformer.clear_context_cache()        # releases the hoisted K/V^T and the prompt embeddings
-            if hasattr(self.transformer, "skip_source_frames"):
-                self.transformer.skip_source_frames = prev_skip
-            if prev_mask is not None:
-                self.transformer.mask_source_frames = prev_mask
-            if local_cfg is not None:
-                if prev_local is None:
-                    self.transformer.disable_local_attention()
-                else:
-                    self.transformer.enable_local_attention(**prev_local)
-            if self.release_workspaces_after_denoise and hasattr(self.transformer, "release_workspaces"):
-                # opt-in: 7 GB of activation buffers at 14B / 67k tokens handed back before the VAE decode (for hosts that share
-                # the device); the sets a captured graph replays from stay.  Off by default: 288 GB of HBM do not need it, every call
-                # would re-allocate and zero-fill the set, and in capture_graph='loop' mode the capture call would then allocate
-                # (and record the zero-fill of) its workspaces inside the graph.
-                self.transformer.release_workspaces(keep_pinned=True)
+                predict, target_frame0, cut = self._whole_clip_form(guided, condition_count, ground_latent_count, zero_source)
+            callback = None if callback_on_step_end is None else (callback_on_step_end, callback_on_step_end_tensor_inputs, {
+                "prompt_embeds": prompt_embeds, "negative_prompt_embeds": negative_prompt_embeds})
+            loop = lambda lat, embeds: cut(self._denoise(
+                lat, embeds, do_cfg, timesteps, predict, None if local_cfg is None else (local_cfg, opt.local_from),
+                None if mask_weights is None else (mask_weights, condition_count, target_frame0), extra_step_kwargs, callback))
+            if capture_graph == "loop":
+                key = (int(num_inference_steps), float(shift), bool(do_cfg), float(guidance_scale) if do_cfg else 0.0,
+                       int(condition_count), int(ground_latent_count), bool(cot), bool(use_rope_map), int(seq_len))
+                latents = self._denoise_as_one_graph(key, loop, latents, in_prompt_embeds, timesteps, callback is not None)
+            else:
+                latents = loop(latents, in_prompt_embeds)
         self._stage("denoise_loop", t_stage)
-
         # -- decode (:757-790)
         t_stage = self._stage("vae_decode")
-        ground_video = edit_video = video_out = compare_out = None
-        edit_dev = [] if compare else None         # the edit segment's device frames, kept for the compare clip only
-        if output_type in ("numpy", "uint8"):
-            u8 = output_type == "uint8"      # uint8 [B, T, H, W, 3] frames (wan_video_to_frames_u8) instead of float32 [B, 3, T, H, W]
-            if self.vae is None:
-                raise ValueError(f"output_type={output_type!r} needs a VAE; use output_type='latent'")
-            if cot:
-                g0, g1 = condition_count, condition_count + ground_latent_count
-                # grounding | edit frames side by side in ONE page-locked clip (what the reference builds with np.concatenate, :786):
-                # each segment is decoded straight into its frame slice, `ground_videos` / `edit_videos` are views of `videos`
-                tcr = self.vae.config.temporal_compression_ratio
-                nfr = lambda n: 1 + tcr * (n - 1) if n > 0 else 0
-                ng = nfr(g1 - g0) if (g1 > g0 and g0 < Ftot) else 0
-                ne = nfr(Ftot - g1) if g1 < Ftot else 0
-                scr = self.vae.config.spatial_compression_ratio
-                clip = None
-                if u8 and ng + ne > 0:
-                    # the same clip as bytes: both segments are written by the kernel into their frames of ONE device clip and
-                    # copied, one contiguous run per segment and sample, into their frames of ONE page-locked clip
-                    shape = (latents.shape[0], ng + ne, latents.shape[3] * scr, latents.shape[4] * scr, 3)
-                    clip = torch.empty(shape, dtype=torch.uint8, pin_memory=True)
-                    dev_clip = torch.empty(shape, dtype=torch.uint8, device=latents.device)
-                    if ng:
-                        ground_video = self._decode_frames_u8(latents[:, :, g0:g1], clip[:, :ng], dev_clip, 0)
-                    if ne:
-                        edit_video = self._decode_frames_u8(latents[:, :, g1:], clip[:, ng:], dev_clip, ng, edit_dev)
-                    video_out = clip.numpy()
-                elif not u8:
-                    if latents.is_cuda and ng + ne > 0:
-                        clip = torch.empty((latents.shape[0], 3, ng + ne, latents.shape[3] * scr, latents.shape[4] * scr),
-                                           dtype=torch.float32, pin_memory=True)
-                    parts = []
-                    if ng:
-                        ground_video = self.decode_latents(latents[:, :, g0:g1], None if clip is None else clip[:, :, :ng])
-                        parts.append(ground_video)
-                    if ne:
-                        edit_video = self.decode_latents(latents[:, :, g1:], None if clip is None else clip[:, :, ng:])
-                        parts.append(edit_video)
-                    video_out = clip.numpy() if clip is not None else np.concatenate(parts, axis=2)
-            else:
-                if condition_count < Ftot:
-                    if compare:
-                        edit_video = self._decode_frames_u8(latents[:, :, condition_count:], None, keep=edit_dev)
-                    else:
-                        edit_video = self.decode_latents(latents[:, :, condition_count:], as_uint8=u8)
-                video_out = edit_video
-            if edit_dev:
-                from . import video_io
-                src = (compare_source if compare_source.dim() == 5 else compare_source.unsqueeze(0)).to(edit_dev[0].device)
-                T, H, W = (min(int(a), int(b)) for a, b in zip(src.shape[1:4], edit_dev[0].shape[1:4]))
-                pinned = torch.empty((edit_dev[0].shape[0], T, H, 2 * W, 3), dtype=torch.uint8, pin_memory=True)
-                compare_out = video_io.compare_frames(src, edit_dev[0], out=pinned).numpy()
-            if not return_dict:
-                video_out = torch.from_numpy(video_out) if isinstance(video_out, np.ndarray) else video_out
-                ground_video = torch.from_numpy(ground_video) if isinstance(ground_video, np.ndarray) else ground_video
-                edit_video = torch.from_numpy(edit_video) if isinstance(edit_video, np.ndarray) else edit_video
-                compare_out = torch.from_numpy(compare_out) if isinstance(compare_out, np.ndarray) else compare_out
-        elif output_type != "latent":
-            raise ValueError(f"output_type {output_type!r} not supported ('numpy', 'uint8' or 'latent')")
+        videos, ground, edit, compared = self._decode_outputs(latents, output_type, cot, condition_count, ground_latent_count,
+                                                              opt.compare_source, return_dict)
         self._stage("vae_decode", t_stage)
-        return WanPipelineOutput(videos=video_out, ground_videos=ground_video, edit_videos=edit_video, latents=latents,
-                                 compare_videos=compare_out)
+        return WanPipelineOutput(videos=videos, ground_videos=ground, edit_videos=edit, latents=latents, compare_videos=compared)
