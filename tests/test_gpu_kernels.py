@@ -1055,8 +1055,10 @@ def test_sp_wire_layout_kernels(rope_dev, P, T, B, Cl):
 
 def test_row_kernels_rows_per_workgroup_are_bitwise_the_one_row_kernels(rope_dev):
     """LN-modulate and RMSNorm+RoPE with 2 (default) or 4 token rows per workgroup -- the per-column parameters fetched once per group --
-    against the one-row kernels: same arithmetic, same summation order, so every output form must agree BITWISE; row counts that
-    leave a ragged last group, samples whose boundary falls inside a group, strided rows, the wire and e4m3 output forms."""
+    against one row per workgroup: same arithmetic, same summation order, so every output form must agree BITWISE; row counts that
+    leave a ragged last group, samples whose boundary falls inside a group, strided rows, the wire and e4m3 output forms.
+    (The three are instantiations of one kernel body, R = 1, 2, 4, not separately written kernels: what this pins is that nothing in
+    the body depends on R.  The comparison with independently written one-row kernels is test_gpu_row_kernels_parent.py.)"""
     g = torch.Generator().manual_seed(5)
     for dim, rows_per_batch, B in ((5120, 37, 2), (1536, 50, 1), (256, 9, 3)):
         rows = rows_per_batch * B
@@ -1087,6 +1089,24 @@ def test_row_kernels_rows_per_workgroup_are_bitwise_the_one_row_kernels(rope_dev
         for R in (2, 4):
             for i, (u, v) in enumerate(zip(res[1], res[R])):
                 assert torch.equal(u, v), (dim, R, i)
+
+
+def test_rmsnorm_rope_sp_and_fp8_reject_a_malformed_rope_table(rope_dev):
+    """The kernel indexes the cos/sin tables by position and pair: a cos table whose width is not head_dim / 2 raises in the wire
+    and e4m3 forms as it does in place, and nothing is launched (the outputs keep their fill)."""
+    x, w = torch.ones(8, 256, device=DEV, dtype=torch.bfloat16), torch.ones(256, device=DEV)
+    rp = RopeParams(2, 2, 2, 0, 0, 0, 0, 8, 1024)
+    bad = (rope_dev[0][:, :32].contiguous(), rope_dev[1])
+    wire = torch.full((8 * 256,), 7.0, device=DEV, dtype=torch.bfloat16)
+    q8 = torch.full((8, 256), 7.0, device=DEV).to(ops.FP8)
+    with pytest.raises(ValueError, match="cos/sin"):
+        ops.rmsnorm_rope_sp(x, w, None, None, 128, 1e-6, bad, rp, wire, None, 2, 1)
+    with pytest.raises(ValueError, match="cos/sin"):
+        ops.rmsnorm_rope_fp8(x, w, None, None, 128, 1e-6, bad, rp, q8, None)
+    with pytest.raises(ValueError, match="cos/sin"):
+        ops.rmsnorm_rope_(x, w, None, None, 128, 1e-6, bad, rp)
+    torch.cuda.synchronize()
+    assert bool((wire == 7.0).all()) and bool((q8.float() == 7.0).all()) and bool((x == 1.0).all())
 
 
 def test_attention_debug_check_catches_non_finite_vt_padding():

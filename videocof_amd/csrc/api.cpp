@@ -73,7 +73,7 @@ const TuningKey kTuningKeys[WAN_TUNE_COUNT] = {
     {"gemm_pk_min_units", "WAN_GEMM_PK_MIN_UNITS", 0},  // smallest stream-K range in units of two K tiles (0 = a quarter of the tile's K range)
     {"gemm_pk_order", "WAN_GEMM_PK_ORDER", 0},          // 1 = whole tiles in lockstep order instead of by per-XCD ticket (developer A/B)
     {"gemm_pk_form", "WAN_GEMM_PK_FORM", 29},           // epilogues of the persistent GEMM, one bit per WAN_EPI_* value: 1 = from row-permuted operand tiles (a lane's accumulators contiguous in the output), 0 = the round-4 form (developer A/B)
-    {"row_group", "WAN_ROW_GROUP", 2},                  // LN-modulate / RMSNorm+RoPE: token rows per workgroup (2 or 4: per-column parameters fetched once per group; 1 = the one-row kernels)
+    {"row_group", "WAN_ROW_GROUP", 2},                  // LN-modulate / RMSNorm+RoPE: token rows per workgroup (2 or 4: per-column parameters fetched once per group; 1 = one row per workgroup)
     {"sp_inline", "WAN_SP_INLINE", 0},                  // library communicator: 1 = every collective on the caller's stream itself (no side stream); 0 = only while that stream is being captured
     {"gemm_splitk", "WAN_GEMM_SPLITK", 1},              // split-K form of the 128^2 GEMM for small shapes that bring a workspace: 1 = by shape, 0 = never, 2..8 = force that many pieces (developer A/B)
     {"conv_mfma", "WAN_CONV_MFMA", 0},                  // matrix instruction of the VAE's LDS-patch convolution: 0 = by the per-frame plane (16x16x32 when four frames of it fill the chip; never by frame count -- chunked decodes stay bit-identical), 32 = v_mfma_f32_32x32x16_bf16, 16 = v_mfma_f32_16x16x32_bf16

@@ -87,20 +87,60 @@ def round_up(x: int, m: int) -> int:
 
 
 # ---------------------------------------------------------------------------------------------
+def _ln_modulate_args(who: str, x: torch.Tensor, scale: Optional[torch.Tensor], shift: Optional[torch.Tensor],
+                      rows_per_batch: int) -> Tuple[int, int]:
+    """The input checks of ``ln_modulate`` and ``ln_modulate_fp8`` (``who``, for the messages) -> (rows, dim)."""
+    _need(x, torch.float32, who + ".x")
+    if not x.is_contiguous() or x.dim() != 2:
+        raise ValueError(f"{who}.x must be a contiguous [rows, dim] tensor")
+    rows, dim = x.shape
+    for nm, t in (("scale", scale), ("shift", shift)):
+        if t is not None:
+            _need(t, torch.float32, f"{who}.{nm}")
+            if not t.is_contiguous() or t.shape[-1] != dim or t.numel() * rows_per_batch < rows * dim:
+                raise ValueError(f"{who}.{nm}: shape {tuple(t.shape)} does not cover {rows} rows of {dim}")
+    return rows, dim
+
+
+def _rmsnorm_rope_args(who: str, x0: torch.Tensor, w0: torch.Tensor, x1: Optional[torch.Tensor], w1: Optional[torch.Tensor],
+                       head_dim: int, rope, rope_params, outs=(), out_dtype=None):
+    """The argument checks of ``rmsnorm_rope_``, ``rmsnorm_rope_sp`` and ``rmsnorm_rope_fp8`` (``who``, for the messages).
+    ``outs``: (name, tensor) of the outputs of the two forms that write elsewhere, x0's then x1's.
+    -> (rows, dim, ld, cos, sin, reference to rope_params or None)."""
+    _need(x0, torch.bfloat16, who + ".x0")
+    _need(w0, torch.float32, who + ".w0")
+    rows, dim = x0.shape
+    ld = x0.stride(0)
+    for nm, t in outs:
+        if t is not None:
+            _need(t, out_dtype, f"{who}.{nm}")
+            if not t.is_contiguous() or t.numel() < rows * dim:
+                raise ValueError(f"{who}.{nm} must be contiguous with >= rows * dim elements")
+    if x1 is not None:
+        _need(x1, torch.bfloat16, who + ".x1")
+        _need(w1, torch.float32, who + ".w1")
+        if x1.shape != x0.shape or x1.stride(0) != ld:
+            raise ValueError(f"{who}: x0 and x1 must have the same shape and row stride")
+        if outs and outs[1][1] is None:
+            raise ValueError(f"{who}: x1 needs {outs[1][0]}")
+    cos = sin = None
+    if rope is not None:
+        cos, sin = rope
+        _need(cos, torch.float32, who + ".cos")
+        _need(sin, torch.float32, who + ".sin")
+        if cos.shape != sin.shape or cos.shape[1] != head_dim // 2 or not (cos.is_contiguous() and sin.is_contiguous()):
+            raise ValueError(f"{who}: cos/sin must be contiguous [max_pos, head_dim/2]")
+        if rope_params is None:
+            raise ValueError(f"{who}: rope tables given without rope_params")
+    return rows, dim, ld, cos, sin, (ctypes.byref(rope_params) if rope_params is not None else None)
+
+
 @_on_tensor_device
 def ln_modulate(x: torch.Tensor, scale: Optional[torch.Tensor], shift: Optional[torch.Tensor],
                 add_one: bool, rows_per_batch: int, eps: float,
                 out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """x fp32 [rows, dim]; scale/shift fp32 [nbatch, dim] or None -> bf16 [rows, dim]."""
-    _need(x, torch.float32, "ln_modulate.x")
-    if not x.is_contiguous() or x.dim() != 2:
-        raise ValueError("ln_modulate.x must be a contiguous [rows, dim] tensor")
-    rows, dim = x.shape
-    for nm, t in (("scale", scale), ("shift", shift)):
-        if t is not None:
-            _need(t, torch.float32, "ln_modulate." + nm)
-            if not t.is_contiguous() or t.shape[-1] != dim or t.numel() * rows_per_batch < rows * dim:
-                raise ValueError(f"ln_modulate.{nm}: shape {tuple(t.shape)} does not cover {rows} rows of {dim}")
+    rows, dim = _ln_modulate_args("ln_modulate", x, scale, shift, rows_per_batch)
     if out is None:
         out = torch.empty(rows, dim, device=x.device, dtype=torch.bfloat16)
     _need(out, torch.bfloat16, "ln_modulate.out")
@@ -117,29 +157,10 @@ def rmsnorm_rope_(x0: torch.Tensor, w0: torch.Tensor, x1: Optional[torch.Tensor]
     """In-place RMSNorm(+RoPE) of one or two bf16 [rows, dim] views sharing a row stride.
     ``x0_scale`` multiplies the x0 result before its bf16 rounding (``q_prescale(softmax_scale)`` to
     feed ``attention_fwd(..., q_prescaled=True)``)."""
-    _need(x0, torch.bfloat16, "rmsnorm_rope.x0")
-    _need(w0, torch.float32, "rmsnorm_rope.w0")
-    rows, dim = x0.shape
-    ld = x0.stride(0)
-    if x1 is not None:
-        _need(x1, torch.bfloat16, "rmsnorm_rope.x1")
-        _need(w1, torch.float32, "rmsnorm_rope.w1")
-        if x1.shape != x0.shape or x1.stride(0) != ld:
-            raise ValueError("rmsnorm_rope: x0 and x1 must have the same shape and row stride")
-    cos = sin = None
-    if rope is not None:
-        cos, sin = rope
-        _need(cos, torch.float32, "rmsnorm_rope.cos")
-        _need(sin, torch.float32, "rmsnorm_rope.sin")
-        if cos.shape != sin.shape or cos.shape[1] != head_dim // 2 or not (cos.is_contiguous() and sin.is_contiguous()):
-            raise ValueError("rmsnorm_rope: cos/sin must be contiguous [max_pos, head_dim/2]")
-        if rope_params is None:
-            raise ValueError("rmsnorm_rope: rope tables given without rope_params")
+    rows, dim, ld, cos, sin, rp = _rmsnorm_rope_args("rmsnorm_rope", x0, w0, x1, w1, head_dim, rope, rope_params)
     lib = _lib.load()
     _lib.check(lib.wan_rmsnorm_rope(_p(x0), _p(w0), _p(x1), _p(w1), ld, rows, dim, head_dim, float(eps),
-                                    _p(cos), _p(sin),
-                                    ctypes.byref(rope_params) if rope_params is not None else None,
-                                    float(x0_scale), _stream()), "wan_rmsnorm_rope")
+                                    _p(cos), _p(sin), rp, float(x0_scale), _stream()), "wan_rmsnorm_rope")
 
 
 @_on_tensor_device
@@ -149,29 +170,16 @@ def rmsnorm_rope_sp(x0: torch.Tensor, w0: torch.Tensor, x1: Optional[torch.Tenso
     """``rmsnorm_rope_`` that leaves x0 / x1 untouched and writes the results into Ulysses token-major wire buffers
     ``[slabs][rows_per_batch][batch][dim / slabs]`` (include/wan_hip.h, a21).  ``split`` > 0: two head groups, channels [0, split) and
     [split, dim / slabs) of every slab, each a complete wire buffer, one behind the other (``wan_rmsnorm_rope_sp_split``)."""
-    _need(x0, torch.bfloat16, "rmsnorm_rope_sp.x0")
-    _need(w0, torch.float32, "rmsnorm_rope_sp.w0")
-    rows, dim = x0.shape
-    ld = x0.stride(0)
-    for nm, t in (("wire0", wire0), ("wire1", wire1)):
-        if t is not None:
-            _need(t, torch.bfloat16, "rmsnorm_rope_sp." + nm)
-            if not t.is_contiguous() or t.numel() < rows * dim:
-                raise ValueError(f"rmsnorm_rope_sp.{nm} must be contiguous with >= rows * dim elements")
-    if x1 is not None:
-        _need(x1, torch.bfloat16, "rmsnorm_rope_sp.x1")
-        _need(w1, torch.float32, "rmsnorm_rope_sp.w1")
-        if x1.shape != x0.shape or x1.stride(0) != ld or wire1 is None:
-            raise ValueError("rmsnorm_rope_sp: x0 / x1 must share shape and row stride, and x1 needs wire1")
-    cos, sin = rope
+    rows, dim, ld, cos, sin, rp = _rmsnorm_rope_args("rmsnorm_rope_sp", x0, w0, x1, w1, head_dim, rope, rope_params,
+                                                     (("wire0", wire0), ("wire1", wire1)), torch.bfloat16)
     lib = _lib.load()
     if split:
         _lib.check(lib.wan_rmsnorm_rope_sp_split(_p(x0), _p(w0), _p(x1), _p(w1), ld, rows, dim, head_dim, float(eps), _p(cos), _p(sin),
-                                                 ctypes.byref(rope_params), float(x0_scale), _p(wire0), _p(wire1), int(slabs), int(batch),
+                                                 rp, float(x0_scale), _p(wire0), _p(wire1), int(slabs), int(batch),
                                                  int(split), _stream()), "wan_rmsnorm_rope_sp_split")
         return
     _lib.check(lib.wan_rmsnorm_rope_sp(_p(x0), _p(w0), _p(x1), _p(w1), ld, rows, dim, head_dim, float(eps), _p(cos), _p(sin),
-                                       ctypes.byref(rope_params), float(x0_scale), _p(wire0), _p(wire1), int(slabs), int(batch),
+                                       rp, float(x0_scale), _p(wire0), _p(wire1), int(slabs), int(batch),
                                        _stream()), "wan_rmsnorm_rope_sp")
 
 
@@ -385,15 +393,7 @@ def ln_modulate_fp8(x: torch.Tensor, scale: Optional[torch.Tensor], shift: Optio
                     out_scale: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
     """``ln_modulate`` with per-token-row e4m3 quantisation fused in: returns (q [rows, dim] float8_e4m3fn, s fp32 [rows])
     with y ~= q * s[:, None]."""
-    _need(x, torch.float32, "ln_modulate_fp8.x")
-    if not x.is_contiguous() or x.dim() != 2:
-        raise ValueError("ln_modulate_fp8.x must be a contiguous [rows, dim] tensor")
-    rows, dim = x.shape
-    for nm, t in (("scale", scale), ("shift", shift)):
-        if t is not None:
-            _need(t, torch.float32, "ln_modulate_fp8." + nm)
-            if not t.is_contiguous() or t.shape[-1] != dim or t.numel() * rows_per_batch < rows * dim:
-                raise ValueError(f"ln_modulate_fp8.{nm}: shape {tuple(t.shape)} does not cover {rows} rows of {dim}")
+    rows, dim = _ln_modulate_args("ln_modulate_fp8", x, scale, shift, rows_per_batch)
     if out is None:
         out = torch.empty(rows, dim, device=x.device, dtype=FP8)
     if out_scale is None:
@@ -674,29 +674,11 @@ def rmsnorm_rope_fp8(x0: torch.Tensor, w0: torch.Tensor, x1: Optional[torch.Tens
                      out0: torch.Tensor, out1: Optional[torch.Tensor], x0_scale: float = 1.0, x1_scale: float = 1.0) -> None:
     """``rmsnorm_rope_`` that leaves x0 / x1 untouched and writes OCP e4m3 copies of the results (dense ``FP8`` [rows, dim]):
     ``out = e4m3(bf16(result * scale))`` -- the operands of ``attention_fwd_qk8`` (include/wan_hip.h, a9')."""
-    _need(x0, torch.bfloat16, "rmsnorm_rope_fp8.x0")
-    _need(w0, torch.float32, "rmsnorm_rope_fp8.w0")
-    rows, dim = x0.shape
-    ld = x0.stride(0)
-    for nm, t in (("out0", out0), ("out1", out1)):
-        if t is not None:
-            _need(t, FP8, "rmsnorm_rope_fp8." + nm)
-            if not t.is_contiguous() or t.numel() < rows * dim:
-                raise ValueError(f"rmsnorm_rope_fp8.{nm} must be contiguous with >= rows * dim bytes")
-    if x1 is not None:
-        _need(x1, torch.bfloat16, "rmsnorm_rope_fp8.x1")
-        _need(w1, torch.float32, "rmsnorm_rope_fp8.w1")
-        if x1.shape != x0.shape or x1.stride(0) != ld or out1 is None:
-            raise ValueError("rmsnorm_rope_fp8: x0 / x1 must share shape and row stride, and x1 needs out1")
-    cos = sin = None
-    if rope is not None:
-        cos, sin = rope
-        if rope_params is None:
-            raise ValueError("rmsnorm_rope_fp8: rope tables given without rope_params")
+    rows, dim, ld, cos, sin, rp = _rmsnorm_rope_args("rmsnorm_rope_fp8", x0, w0, x1, w1, head_dim, rope, rope_params,
+                                                     (("out0", out0), ("out1", out1)), FP8)
     lib = _lib.load()
     _lib.check(lib.wan_rmsnorm_rope_fp8(_p(x0), _p(w0), _p(x1), _p(w1), ld, rows, dim, head_dim, float(eps), _p(cos), _p(sin),
-                                        ctypes.byref(rope_params) if rope_params is not None else None, float(x0_scale),
-                                        float(x1_scale), _p(out0), _p(out1), _stream()), "wan_rmsnorm_rope_fp8")
+                                        rp, float(x0_scale), float(x1_scale), _p(out0), _p(out1), _stream()), "wan_rmsnorm_rope_fp8")
 
 
 @_on_tensor_device
