@@ -716,6 +716,34 @@ wan_status_t wan_latent_mask_u8(const void* alpha_u8, void* weights_u8, int B, i
 wan_status_t wan_masked_prediction(void* pred, const void* sample, int dtype, const void* weights_u8, int B, int Bm, int C, int F,
                                    int Fs, int target_frame0, int64_t hw, float sigma, void* stream);
 
+/* a17f  Edit region: run the loop only on the part of the clip the edit mask touches.  Three passes, each once per
+ *      call; videocof_amd/edit_region.py states each in plain torch (reference_mask_bounds, reference_region_crop,
+ *      reference_region_restore) and the kernels equal them bit for bit.
+ *      replaces: nothing in the reference, whose loop runs on whole frames.
+ *      Common to all three: a row of a frame is W elements, a row of the region wr elements at column x0; the access unit is the
+ *      largest of 16, 8, 4 bytes or one element that divides (in bytes) W, wr, x0 and the base addresses, so no unit straddles the
+ *      region's edge.  Everything is validated on the host before anything is enqueued; each enqueues ONE kernel on `stream` and never
+ *      synchronises.
+ *      wan_mask_bounds: weights uint8 [Bm, Fs, h, w] (wan_latent_mask_u8's) -> bounds int32 [Fs, 4] = (y_lo, y_hi, x_lo, x_hi) per
+ *          latent frame: the inclusive bounds of the non-zero weights over all Bm samples; a frame without one gives (h, -1, w, -1).
+ *          One workgroup per latent frame, reduced in registers and LDS: no atomics, no init pass, every output word written exactly
+ *          once.  A null tensor, a count below 1, 2^31 weights or more, bounds not 4-byte aligned -> WAN_ERR_INVALID.
+ *      wan_region_crop: in [R, H, W] (contiguous, elements of elem_bytes = 1, 2 or 4) -> out [R, hr, wr], out[r, y, x] =
+ *          in[r, y0 + y, x0 + x], bits unchanged.  Serves the loop state (R = B * C * F) and the weights (R = Bm * Fs, bytes).
+ *      wan_region_restore: source [B, C, cc, H, W] (the full-frame source block), region [B, C, cc + G + cc, hr, wr] (the loop's final
+ *          state on the region) -> out [B, C, cc + G + cc, H, W], bits unchanged:
+ *              source frame f            source[f]
+ *              grounding frame g         region[cc + g] inside the box, source[g] outside it       (hence 0 <= G <= cc)
+ *              target frame f            region[cc + G + f] inside the box, source[f] outside it
+ *          so outside the box the target IS the source, bit for bit.
+ *      For the last two: a null tensor, another element size, a box that does not lie inside the frame (y0, x0 >= 0; hr, wr >= 1;
+ *      y0 + hr <= H; x0 + wr <= W), G outside [0, cc], a frame count or H * W of 2^31 or more -> WAN_ERR_INVALID. */
+wan_status_t wan_mask_bounds(const void* weights_u8, void* bounds_i32, int Bm, int Fs, int h, int w, void* stream);
+wan_status_t wan_region_crop(void* out, const void* in, int elem_bytes, int64_t R, int H, int W, int y0, int x0, int hr, int wr,
+                             void* stream);
+wan_status_t wan_region_restore(void* out, const void* source, const void* region, int elem_bytes, int B, int C, int cc, int G, int H,
+                                int W, int y0, int x0, int hr, int wr, void* stream);
+
 /* ===========================================================================
  * WanVAE (videox_fun/models/wan_vae.py).  Activations are CHANNELS-LAST bf16 [T, H, W, C].
  * ------------------------------------------------------------------------- */

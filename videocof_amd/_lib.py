@@ -239,6 +239,9 @@ SIGNATURES = {
     "wan_latent_mask_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
     "wan_latent_mask_u8": (c_int, [c_void_p, c_void_p] + [c_int] * 9 + [c_void_p, c_int64, c_void_p]),
     "wan_masked_prediction": (c_int, [c_void_p, c_void_p, c_int, c_void_p] + [c_int] * 6 + [c_int64, c_float, c_void_p]),
+    "wan_mask_bounds": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
+    "wan_region_crop": (c_int, [c_void_p, c_void_p, c_int, c_int64] + [c_int] * 6 + [c_void_p]),
+    "wan_region_restore": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 11 + [c_void_p]),
     "wan_gemm_bf16_batched": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64,
                                       c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "wan_embedding_rows": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p]),

@@ -1,0 +1,246 @@
+// Edit region: run the denoise loop only where the edit mask is.  Three passes, each once per call:
+//   wan_mask_bounds      latent-cell weights uint8 [Bm, Fs, h, w] -> per latent frame the inclusive bounds of the non-zero weights
+//   wan_region_crop      the sub-box [y0, y0 + hr) x [x0, x0 + wr) of every frame of a contiguous [R, H, W] tensor -> [R, hr, wr]
+//   wan_region_restore   the full-frame source block and the region-sized final state -> the full-frame state, in one launch
+// All three are streams of rows at a pitch: the access unit is the widest of 16 / 8 / 4 bytes or one element that divides every length,
+// pitch, x origin and base address (region_unit_bytes below: the rule of tile_unit_bytes in window_kernels.hip), so all x arithmetic is
+// in whole units and no unit straddles the region's edge.  A workgroup is `rp` rows of `cw` lanes each (cw = min(units per row, 256),
+// rp = 256 / cw; lanes beyond rp * cw idle): which frame, which rows and where the region lies are per workgroup (scalar); a lane adds
+// its row and unit once.  Nothing is computed on an element: the copies move bits.
+#include <algorithm>
+#include <initializer_list>
+
+#include "common.hpp"
+
+namespace {
+
+constexpr int UNROLL = 4;                            // rows a lane keeps in flight together
+
+template <int BYTES> struct RawOf;                    // BYTES of memory as one load / store
+template <> struct RawOf<16> { typedef u32x4 type; };
+template <> struct RawOf<8> { typedef u32x2 type; };
+template <> struct RawOf<4> { typedef unsigned int type; };
+template <> struct RawOf<2> { typedef unsigned short type; };
+template <> struct RawOf<1> { typedef unsigned char type; };
+
+// ------------------------------------------------------------------------------------------------------------- the bounds
+// grid (latent frame).  `wu` = w / N units per row.  Every lane keeps its own four extremes over the rows and units it reads, of every
+// sample; the waves reduce them with shuffles, the workgroup through 16 words of LDS; lanes 0..3 write one word each.  No atomics, no
+// init pass: an empty frame leaves the extremes at their start values (h, -1, w, -1).
+template <int N>
+__global__ __launch_bounds__(256) void mask_bounds_kernel(int* __restrict__ bounds, const unsigned char* __restrict__ weights, int Bm,
+                                                          int Fs, int h, int w, int wu, int cw, int rp) {
+    typedef typename RawOf<N>::type U;
+    struct Bytes { unsigned char a[N]; };
+    __shared__ int red[4][4];
+    const int f = blockIdx.x;                         // < Fs
+    const int lr = threadIdx.x / cw, lu = threadIdx.x % cw;
+    int lo_y = h, hi_y = -1, lo_x = w, hi_x = -1;
+    if (lr < rp) {
+        for (int b = 0; b < Bm; ++b) {
+            const U* frame = (const U*)(weights + ((int64_t)b * Fs + f) * h * w);      // Bm * Fs * h * w < 2^31 (checked by the host)
+            for (int r0 = 0; r0 < h; r0 += UNROLL * rp)
+                for (int u = lu; u < wu; u += cw) {   // one pass unless a row is longer than 256 units
+                    U v[UNROLL];                      // UNROLL independent loads in flight per lane, then the comparisons
+#pragma unroll
+                    for (int j = 0; j < UNROLL; ++j) {
+                        const int y = r0 + j * rp + lr;
+                        if (y < h) v[j] = frame[(int64_t)y * wu + u];
+                    }
+#pragma unroll
+                    for (int j = 0; j < UNROLL; ++j) {
+                        const int y = r0 + j * rp + lr;
+                        if (y >= h) continue;
+                        const Bytes a = __builtin_bit_cast(Bytes, v[j]);
+#pragma unroll
+                        for (int i = 0; i < N; ++i)
+                            if (a.a[i] != 0) {
+                                const int x = u * N + i;
+                                lo_y = min(lo_y, y); hi_y = max(hi_y, y); lo_x = min(lo_x, x); hi_x = max(hi_x, x);
+                            }
+                    }
+                }
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        lo_y = min(lo_y, __shfl_xor(lo_y, o, 64)); hi_y = max(hi_y, __shfl_xor(hi_y, o, 64));
+        lo_x = min(lo_x, __shfl_xor(lo_x, o, 64)); hi_x = max(hi_x, __shfl_xor(hi_x, o, 64));
+    }
+    const int wid = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { red[wid][0] = lo_y; red[wid][1] = hi_y; red[wid][2] = lo_x; red[wid][3] = hi_x; }
+    __syncthreads();
+    if (threadIdx.x < 4) {                            // word 0 and 2: a minimum; 1 and 3: a maximum
+        const int t = threadIdx.x;
+        int r = red[0][t];
+#pragma unroll
+        for (int k = 1; k < 4; ++k) r = (t & 1) ? max(r, red[k][t]) : min(r, red[k][t]);
+        bounds[(int64_t)f * 4 + t] = r;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------- the crop
+// grid (frame, row chunk); `fu` = H * W, `pitch` = W, `ru` = wr, `org` = y0 * W + x0, all in units
+template <typename U>
+__global__ __launch_bounds__(256) void region_crop_kernel(U* __restrict__ out, const U* __restrict__ in, int64_t fu, int pitch,
+                                                          int64_t org, int hr, int ru, int cw, int rp) {
+    const U* src = in + (int64_t)blockIdx.x * fu + org;                 // frame < R (the grid); the box lies inside it (checked by the host)
+    U* dst = out + (int64_t)blockIdx.x * hr * ru;
+    const int lr = threadIdx.x / cw, lu = threadIdx.x % cw;
+    if (lr >= rp) return;
+    for (int r0 = blockIdx.y * UNROLL * rp; r0 < hr; r0 += gridDim.y * UNROLL * rp)
+        for (int u = lu; u < ru; u += cw) {           // one pass unless a region row is longer than 256 units
+            U v[UNROLL];                              // UNROLL independent loads in flight per lane, then the stores
+#pragma unroll
+            for (int j = 0; j < UNROLL; ++j) {
+                const int r = r0 + j * rp + lr;
+                if (r < hr) v[j] = src[(int64_t)r * pitch + u];
+            }
+#pragma unroll
+            for (int j = 0; j < UNROLL; ++j) {
+                const int r = r0 + j * rp + lr;
+                if (r < hr) dst[(int64_t)r * ru + u] = v[j];
+            }
+        }
+}
+
+// ------------------------------------------------------------------------------------------------------------- the restore
+// grid (output frame = (b * C + c) * (2 cc + G) + F, row chunk); `wu` = W, `x0u` = x0, `ru` = wr in units.  Which source frame stands
+// behind output frame F, and whether F takes the region at all, is per workgroup; a lane picks one of two addresses and loads once.
+template <typename U>
+__global__ __launch_bounds__(256) void region_restore_kernel(U* __restrict__ out, const U* __restrict__ source,
+                                                             const U* __restrict__ region, int cc, int G, int H, int wu, int y0,
+                                                             int x0u, int hr, int ru, int cw, int rp) {
+    const unsigned Ftot = (unsigned)(2 * cc + G);
+    const unsigned row = blockIdx.x;                  // < B * C * Ftot (the grid)
+    const int F = (int)(row % Ftot);
+    const int64_t bc = row / Ftot;
+    const int sf = F < cc ? F : F < cc + G ? F - cc : F - cc - G;       // < cc: G <= cc (checked by the host)
+    const bool mixed = F >= cc;                       // grounding and target frames take the region inside its box
+    const U* s = source + (bc * cc + sf) * H * wu;
+    const U* r = region + (int64_t)row * hr * ru;
+    U* o = out + (int64_t)row * H * wu;
+    const int lr = threadIdx.x / cw, lu = threadIdx.x % cw;
+    if (lr >= rp) return;
+    for (int r0 = blockIdx.y * UNROLL * rp; r0 < H; r0 += gridDim.y * UNROLL * rp)
+        for (int u = lu; u < wu; u += cw) {           // one pass unless a row is longer than 256 units
+            U v[UNROLL];
+#pragma unroll
+            for (int j = 0; j < UNROLL; ++j) {
+                const int y = r0 + j * rp + lr;
+                if (y >= H) continue;
+                const bool inside = mixed && y >= y0 && y < y0 + hr && u >= x0u && u < x0u + ru;
+                const U* p = inside ? r + (int64_t)(y - y0) * ru + (u - x0u) : s + (int64_t)y * wu + u;
+                v[j] = *p;
+            }
+#pragma unroll
+            for (int j = 0; j < UNROLL; ++j) {
+                const int y = r0 + j * rp + lr;
+                if (y < H) o[(int64_t)y * wu + u] = v[j];
+            }
+        }
+}
+
+// the largest of 16, 8, 4 bytes or one element that divides (in bytes) every length in `lens` (elements) and every address: a power of
+// two divides them all exactly when it divides their bitwise OR
+int region_unit_bytes(int64_t es, std::initializer_list<int64_t> lens, uintptr_t addresses) {
+    uint64_t m = (uint64_t)addresses;
+    for (int64_t l : lens) m |= (uint64_t)(l * es);
+    int ub = 16;
+    while (ub > es && (m & (uint64_t)(ub - 1)) != 0) ub /= 2;
+    return ub;
+}
+
+// workgroups along the rows: <= ~4096 in all, at most what the grid's second axis holds; the rest is a grid-stride loop
+unsigned row_chunks(int rows, int per_group, int64_t frames) {
+    const int64_t need = ((int64_t)rows + per_group - 1) / per_group;
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(need, 65535), 4096 / frames));
+}
+
+bool box_ok(int H, int W, int y0, int x0, int hr, int wr) {
+    return H >= 1 && W >= 1 && y0 >= 0 && x0 >= 0 && hr >= 1 && wr >= 1 && (int64_t)y0 + hr <= H && (int64_t)x0 + wr <= W;
+}
+
+}  // namespace
+
+extern "C" wan_status_t wan_mask_bounds(const void* weights_u8, void* bounds_i32, int Bm, int Fs, int h, int w, void* stream) {
+    WAN_REQUIRE(weights_u8 && bounds_i32, WAN_ERR_INVALID, "wan_mask_bounds: null tensor");
+    WAN_REQUIRE(Bm >= 1 && Fs >= 1 && h >= 1 && w >= 1, WAN_ERR_INVALID, "wan_mask_bounds: Bm=%d Fs=%d h=%d w=%d", Bm, Fs, h, w);
+    WAN_REQUIRE((int64_t)Bm * Fs * h * w <= 0x7fffffff, WAN_ERR_INVALID, "wan_mask_bounds: %lld weights (at most 2^31 - 1)",
+                (long long)((int64_t)Bm * Fs * h * w));
+    WAN_REQUIRE(((uintptr_t)bounds_i32 & 3) == 0, WAN_ERR_INVALID, "wan_mask_bounds: bounds are int32 words; the address is not a multiple of 4");
+    const int N = region_unit_bytes(1, {w}, (uintptr_t)weights_u8);
+    const int wu = w / N, cw = std::min(wu, 256), rp = 256 / cw;
+    hipStream_t s = (hipStream_t)stream;
+#define WAN_BOUNDS(N_)                                                                                                        \
+    hipLaunchKernelGGL(mask_bounds_kernel<N_>, dim3((unsigned)Fs), dim3(256), 0, s, (int*)bounds_i32,                          \
+                       (const unsigned char*)weights_u8, Bm, Fs, h, w, wu, cw, rp)
+    if (N == 16) WAN_BOUNDS(16); else if (N == 8) WAN_BOUNDS(8); else if (N == 4) WAN_BOUNDS(4); else if (N == 2) WAN_BOUNDS(2);
+    else WAN_BOUNDS(1);
+#undef WAN_BOUNDS
+    WAN_CHECK_LAUNCH("wan_mask_bounds");
+    return WAN_OK;
+}
+
+#define WAN_BY_UNIT(ub, LAUNCH)                                          \
+    do {                                                                 \
+        if ((ub) == 16) LAUNCH(u32x4);                                   \
+        else if ((ub) == 8) LAUNCH(u32x2);                               \
+        else if ((ub) == 4) LAUNCH(unsigned int);                        \
+        else if ((ub) == 2) LAUNCH(unsigned short);                      \
+        else LAUNCH(unsigned char);                                      \
+    } while (0)
+
+extern "C" wan_status_t wan_region_crop(void* out, const void* in, int elem_bytes, int64_t R, int H, int W, int y0, int x0, int hr,
+                                        int wr, void* stream) {
+    // (the box first: an empty region's output is an empty tensor, whose address is null)
+    WAN_REQUIRE(R >= 1 && box_ok(H, W, y0, x0, hr, wr), WAN_ERR_INVALID,
+                "wan_region_crop: the region [%d, %d + %d) x [%d, %d + %d) does not lie inside %lld frames of %d x %d", y0, y0, hr, x0, x0,
+                wr, (long long)R, H, W);
+    WAN_REQUIRE(out && in, WAN_ERR_INVALID, "wan_region_crop: null tensor");
+    WAN_REQUIRE(elem_bytes == 1 || elem_bytes == 2 || elem_bytes == 4, WAN_ERR_INVALID, "wan_region_crop: elements of %d bytes (1, 2 or 4)",
+                elem_bytes);
+    WAN_REQUIRE(R <= 0x7fffffff && (int64_t)H * W <= 0x7fffffff, WAN_ERR_INVALID,
+                "wan_region_crop: %lld frames of %lld elements (each at most 2^31 - 1)", (long long)R, (long long)((int64_t)H * W));
+    const int64_t es = elem_bytes;
+    const int ub = region_unit_bytes(es, {W, wr, x0}, (uintptr_t)out | (uintptr_t)in);
+    const int N = (int)(ub / es), ru = wr / N, cw = std::min(ru, 256), rp = 256 / cw;
+    const dim3 grid((unsigned)R, row_chunks(hr, UNROLL * rp, R));
+    hipStream_t s = (hipStream_t)stream;
+#define WAN_CROP(U)                                                                                                            \
+    hipLaunchKernelGGL(region_crop_kernel<U>, grid, dim3(256), 0, s, (U*)out, (const U*)in, (int64_t)H * W / N, W / N,         \
+                       ((int64_t)y0 * W + x0) / N, hr, ru, cw, rp)
+    WAN_BY_UNIT(ub, WAN_CROP);
+#undef WAN_CROP
+    WAN_CHECK_LAUNCH("wan_region_crop");
+    return WAN_OK;
+}
+
+extern "C" wan_status_t wan_region_restore(void* out, const void* source, const void* region, int elem_bytes, int B, int C, int cc,
+                                           int G, int H, int W, int y0, int x0, int hr, int wr, void* stream) {
+    WAN_REQUIRE(out && source && region, WAN_ERR_INVALID, "wan_region_restore: null tensor");
+    WAN_REQUIRE(elem_bytes == 1 || elem_bytes == 2 || elem_bytes == 4, WAN_ERR_INVALID,
+                "wan_region_restore: elements of %d bytes (1, 2 or 4)", elem_bytes);
+    WAN_REQUIRE(B >= 1 && C >= 1 && cc >= 1, WAN_ERR_INVALID, "wan_region_restore: B=%d C=%d cc=%d", B, C, cc);
+    WAN_REQUIRE(0 <= G && G <= cc, WAN_ERR_INVALID,
+                "wan_region_restore: G=%d grounding frames for cc=%d source frames (grounding frame g takes source frame g outside the "
+                "region: 0 <= G <= cc)", G, cc);
+    WAN_REQUIRE(box_ok(H, W, y0, x0, hr, wr), WAN_ERR_INVALID,
+                "wan_region_restore: the region [%d, %d + %d) x [%d, %d + %d) does not lie inside a frame of %d x %d", y0, y0, hr, x0, x0, wr,
+                H, W);
+    const int64_t frames = (int64_t)B * C * (2 * (int64_t)cc + G);
+    WAN_REQUIRE(frames <= 0x7fffffff && (int64_t)H * W <= 0x7fffffff, WAN_ERR_INVALID,
+                "wan_region_restore: %lld frames of %lld elements (each at most 2^31 - 1)", (long long)frames, (long long)((int64_t)H * W));
+    const int64_t es = elem_bytes;
+    const int ub = region_unit_bytes(es, {W, wr, x0}, (uintptr_t)out | (uintptr_t)source | (uintptr_t)region);
+    const int N = (int)(ub / es), wu = W / N, cw = std::min(wu, 256), rp = 256 / cw;
+    const dim3 grid((unsigned)frames, row_chunks(H, UNROLL * rp, frames));
+    hipStream_t s = (hipStream_t)stream;
+#define WAN_RESTORE(U)                                                                                                         \
+    hipLaunchKernelGGL(region_restore_kernel<U>, grid, dim3(256), 0, s, (U*)out, (const U*)source, (const U*)region, cc, G, H, wu, y0, \
+                       x0 / N, hr, wr / N, cw, rp)
+    WAN_BY_UNIT(ub, WAN_RESTORE);
+#undef WAN_RESTORE
+    WAN_CHECK_LAUNCH("wan_region_restore");
+    return WAN_OK;
+}

@@ -1,0 +1,153 @@
+"""Edit region: run the denoise loop only where the edit mask is.  The rule (host arithmetic, no GPU needed) and torch
+restatements of the three device passes.
+
+With ``edit_mask`` the loop already pins everything outside the mask to the source, so a call with ``edit_region=True`` crops the loop
+state once to a rectangle around the mask's non-zero latent weights, runs the ordinary loop on that smaller clip and puts the result
+back into the source latents once.  ``region_plan`` fixes the rectangle; ``reference_mask_bounds`` / ``reference_region_crop`` /
+``reference_region_restore`` state what ``wan_mask_bounds`` / ``wan_region_crop`` / ``wan_region_restore`` compute (ops.mask_bounds,
+ops.region_crop, ops.region_restore), bit for bit.  The time axis is never cropped: the first latent frame of the causal VAE is special,
+and a temporal crop would move it.
+"""
+from __future__ import annotations
+
+from typing import NamedTuple, Optional, Tuple
+
+import numpy as np
+import torch
+
+__all__ = ["RegionPlan", "region_plan", "region_margin_cells", "reference_mask_bounds", "reference_region_crop",
+           "reference_region_restore"]
+
+REGION_MARGIN_UNIT = 16         # pixels: the VAE's spatial ratio 8 times the patch 2 -- a margin keeps the region on the patch grid
+
+
+class RegionPlan(NamedTuple):
+    """The rectangle the loop runs on, in LATENT cells: rows [y0, y0 + h), columns [x0, x0 + w) of every frame."""
+    y0: int
+    x0: int
+    h: int
+    w: int
+
+    def pixels(self, ratio: int = 8) -> Tuple[int, int, int, int]:
+        """(y, x, h, w) in pixels."""
+        return self.y0 * ratio, self.x0 * ratio, self.h * ratio, self.w * ratio
+
+
+def _axis(lo: int, hi: int, F: int, m: int, T: Optional[int], p: int) -> Tuple[int, int, int]:
+    """One axis of the rule: (start, size, want)."""
+    lo_a, hi_a = lo // p * p, (hi // p + 1) * p                     # the bounds on the patch grid, [lo', hi')
+    want = min(F, hi_a - lo_a + 2 * m)
+    size = min(T, F) if T is not None and want <= T else want       # one tile, the trained size, with as much context as fits
+    start = lo_a - m - ((size - want) // (2 * p)) * p               # the spare context, half on either side, on the grid
+    return min(max(start, 0), F - size), size, want
+
+
+def region_plan(bounds, frame_cells, margin_cells, tile_cells=None, patch: int = 2) -> RegionPlan:
+    """The region of a mask whose non-zero latent weights have the inclusive ``bounds`` = (y_lo, y_hi, x_lo, x_hi) -- one such row, or one
+    per latent frame as ``mask_bounds`` returns them ([Fs, 4]; the union is taken, rows of an empty frame, (h, -1, w, -1), drop out).
+    Everything in LATENT cells: ``frame_cells`` = (H, W), ``margin_cells`` = (rows, columns) of context kept around the bounds,
+    ``tile_cells`` = the (rows, columns) of ``spatial_window`` or None, ``patch`` = the DiT's spatial patch.  Per axis, with lo, hi the
+    bounds, F the frame's extent, p the patch, m the margin and T the tile's extent or None:
+
+        lo' = lo // p * p,  hi' = (hi // p + 1) * p,  want = min(F, hi' - lo' + 2 m)
+        size  = min(T, F)  if T is given and want <= T  (one tile: the trained size, with as much context as fits)  else  want
+        start = clamp(lo' - m - ((size - want) // (2 p)) * p, 0, F - size)
+
+    Every region lies inside the frame and contains [lo' - m, hi' + m) clipped to the frame; m and T must be multiples of p, and where
+    F is one too (every frame the model takes whole) the region's sides are multiples of p and it lies on the frame's own patch grid.
+    (A frame of 135 rows, 1080 pixels, is none: it only runs as ``spatial_window`` tiles, which start anywhere, and so does a region
+    of it.)  An empty mask raises ``ValueError``."""
+    b = np.asarray(bounds.cpu() if torch.is_tensor(bounds) else bounds, dtype=np.int64).reshape(-1, 4)
+    p = int(patch)
+    if p < 1:
+        raise ValueError(f"region_plan: patch={patch!r} (>= 1)")
+    pairs = []
+    for name, v in (("frame_cells", frame_cells), ("margin_cells", margin_cells), ("tile_cells", tile_cells)):
+        if v is None and name == "tile_cells":
+            pairs.append((None, None))
+            continue
+        if isinstance(v, (str, bytes)) or not hasattr(v, "__len__") or len(v) != 2 or any(
+                isinstance(e, bool) or not isinstance(e, (int, np.integer)) for e in v):
+            raise ValueError(f"region_plan: {name}={v!r} is not a pair (rows, columns) of latent cell counts")
+        if name == "frame_cells":
+            if any(int(e) < 1 for e in v):
+                raise ValueError(f"region_plan: frame_cells={tuple(v)!r}: each at least 1")
+        elif any(int(e) < (0 if name == "margin_cells" else p) or int(e) % p for e in v):
+            raise ValueError(f"region_plan: {name}={tuple(v)!r}: each a {'non-negative' if name == 'margin_cells' else 'positive'} "
+                             f"multiple of the patch {p}")
+        pairs.append((int(v[0]), int(v[1])))
+    (H, W), (my, mx), (Ty, Tx) = pairs
+    b = b[(b[:, 1] >= b[:, 0]) & (b[:, 3] >= b[:, 2])]
+    if b.shape[0] == 0:
+        raise ValueError("edit_mask is empty (every latent weight is zero): there is no region to run the loop on")
+    y_lo, y_hi, x_lo, x_hi = int(b[:, 0].min()), int(b[:, 1].max()), int(b[:, 2].min()), int(b[:, 3].max())
+    if y_lo < 0 or y_hi >= H or x_lo < 0 or x_hi >= W:
+        raise ValueError(f"region_plan: bounds rows [{y_lo}, {y_hi}] x columns [{x_lo}, {x_hi}] leave a frame of {H} x {W} cells")
+    y0, h, _ = _axis(y_lo, y_hi, H, my, Ty, p)
+    x0, w, _ = _axis(x_lo, x_hi, W, mx, Tx, p)
+    return RegionPlan(y0, x0, h, w)
+
+
+def region_margin_cells(margin, ratio: int = 8) -> Tuple[int, int]:
+    """The pipeline's ``edit_region_margin`` = (rows, columns) in PIXELS as latent cells; each a non-negative multiple of 16 pixels (the
+    VAE's spatial ratio 8 times the patch 2), which keeps the region on the patch grid."""
+    if isinstance(margin, (str, bytes)) or not hasattr(margin, "__len__") or len(margin) != 2:
+        raise ValueError(f"edit_region_margin={margin!r} is not a pair (rows, columns) of pixel counts")
+    for e in margin:
+        if isinstance(e, bool) or not isinstance(e, (int, np.integer)):
+            raise ValueError(f"edit_region_margin={tuple(margin)!r}: {e!r} is not an integer pixel count")
+        if e < 0 or e % REGION_MARGIN_UNIT:
+            raise ValueError(f"edit_region_margin={tuple(margin)!r}: {e} must be a non-negative multiple of {REGION_MARGIN_UNIT} pixels "
+                             "(the VAE's spatial ratio 8 times the patch 2)")
+    return int(margin[0]) // ratio, int(margin[1]) // ratio
+
+
+# ------------------------------------------------------------------------------------------------ the device passes, in torch
+def reference_mask_bounds(weights: torch.Tensor) -> torch.Tensor:
+    """``wan_mask_bounds`` in torch: weights uint8 [Bm, Fs, h, w] -> int32 [Fs, 4] = (y_lo, y_hi, x_lo, x_hi) per latent frame, the
+    inclusive bounds of the non-zero weights over all samples; (h, -1, w, -1) for a frame without one."""
+    if weights.dim() != 4 or weights.dtype != torch.uint8:
+        raise ValueError(f"reference_mask_bounds: expected uint8 [Bm, Fs, h, w], got {weights.dtype} {tuple(weights.shape)}")
+    _, Fs, h, w = weights.shape
+    on = (weights != 0).any(dim=0)
+    out = torch.empty((Fs, 4), dtype=torch.int32)
+    for f in range(Fs):
+        ys, xs = on[f].any(dim=1).nonzero().flatten(), on[f].any(dim=0).nonzero().flatten()
+        out[f] = torch.tensor([int(ys[0]), int(ys[-1]), int(xs[0]), int(xs[-1])] if ys.numel() else [h, -1, w, -1], dtype=torch.int32)
+    return out
+
+
+def _box(region, H: int, W: int, who: str) -> Tuple[int, int, int, int]:
+    if len(region) != 4:
+        raise ValueError(f"{who}: region = (y0, x0, h, w) in cells, got {region!r}")
+    y0, x0, hr, wr = (int(v) for v in region)
+    if y0 < 0 or x0 < 0 or hr < 1 or wr < 1 or y0 + hr > H or x0 + wr > W:
+        raise ValueError(f"{who}: the region [{y0}, {y0} + {hr}) x [{x0}, {x0} + {wr}) does not lie inside a frame of {H} x {W}")
+    return y0, x0, hr, wr
+
+
+def reference_region_crop(x: torch.Tensor, region) -> torch.Tensor:
+    """``wan_region_crop`` in torch: the sub-box ``region`` = (y0, x0, h, w) of every frame of ``x`` [..., H, W], contiguous."""
+    if x.dim() < 2:
+        raise ValueError(f"reference_region_crop: expected [..., H, W], got {tuple(x.shape)}")
+    y0, x0, hr, wr = _box(region, x.shape[-2], x.shape[-1], "reference_region_crop")
+    return x[..., y0:y0 + hr, x0:x0 + wr].contiguous()
+
+
+def reference_region_restore(source: torch.Tensor, state: torch.Tensor, origin) -> torch.Tensor:
+    """``wan_region_restore`` in torch: ``source`` [B, C, cc, H, W] (the full-frame source block) and ``state`` [B, C, cc + G + cc, hr,
+    wr] (the loop's final state on the region whose corner is ``origin`` = (y0, x0)) -> the full-frame state [B, C, cc + G + cc, H, W]:
+    the source frames are the source; grounding frame g is source frame g outside the region and the region's grounding inside;
+    target frame f is source frame f outside the region and the region's target inside."""
+    if source.dim() != 5 or state.dim() != 5 or source.shape[:2] != state.shape[:2] or source.dtype != state.dtype:
+        raise ValueError(f"reference_region_restore: source {source.dtype} {tuple(source.shape)} and state {state.dtype} "
+                         f"{tuple(state.shape)}: expected [B, C, cc, H, W] and [B, C, cc + G + cc, hr, wr] of one dtype")
+    cc, G = source.shape[2], state.shape[2] - 2 * source.shape[2]
+    if not 0 <= G <= cc:
+        raise ValueError(f"reference_region_restore: {state.shape[2]} state frames for {cc} source frames: G={G} grounding frames "
+                         f"(0 <= G <= cc)")
+    y0, x0, hr, wr = _box((origin[0], origin[1], state.shape[3], state.shape[4]), source.shape[3], source.shape[4],
+                          "reference_region_restore")
+    out = torch.cat([source, source[:, :, :G], source], dim=2)
+    out[:, :, cc:, y0:y0 + hr, x0:x0 + wr] = state[:, :, cc:]
+    return out

@@ -1640,6 +1640,81 @@ def masked_prediction_(pred: torch.Tensor, sample: torch.Tensor, weights: torch.
     return pred
 
 
+# ------------------------------------------------------------------ edit region
+def _region_out(out: Optional[torch.Tensor], shape, like: torch.Tensor, name: str) -> torch.Tensor:
+    if out is None:
+        return torch.empty(shape, device=like.device, dtype=like.dtype)
+    if tuple(out.shape) != tuple(shape) or out.dtype != like.dtype or not out.is_contiguous() or out.device != like.device:
+        raise ValueError(f"{name}: {out.dtype} {tuple(out.shape)} on {out.device} for contiguous {like.dtype} {tuple(shape)} on {like.device}")
+    return out
+
+
+@_on_tensor_device
+def mask_bounds(weights: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Latent-cell weights uint8 [Bm, Fs, h, w] -> device int32 [Fs, 4] = (y_lo, y_hi, x_lo, x_hi) per latent frame: the inclusive bounds
+    of the non-zero weights over all samples, (h, -1, w, -1) for a frame without one (``wan_mask_bounds``: one workgroup per frame, no
+    atomics, every word written once).  Never synchronises: the caller copies the 16 * Fs bytes to the host."""
+    _need(weights, torch.uint8, "mask_bounds.weights")
+    if weights.dim() != 4 or not weights.is_contiguous():
+        raise ValueError(f"mask_bounds.weights: a contiguous uint8 [Bm, Fs, h, w] tensor, got {tuple(weights.shape)}")
+    Bm, Fs, h, w = (int(v) for v in weights.shape)
+    if out is None:
+        out = torch.empty((Fs, 4), device=weights.device, dtype=torch.int32)
+    elif tuple(out.shape) != (Fs, 4) or out.dtype != torch.int32 or not out.is_contiguous() or out.device != weights.device:
+        raise ValueError(f"mask_bounds.out: {out.dtype} {tuple(out.shape)} on {out.device} for contiguous int32 {(Fs, 4)} on {weights.device}")
+    _lib.check(_lib.load().wan_mask_bounds(_p(weights), _p(out), Bm, Fs, h, w, _stream()), "wan_mask_bounds")
+    return out
+
+
+def _region_box(region, name: str):
+    if len(region) != 4:
+        raise ValueError(f"{name}: region = (y0, x0, h, w) in cells, got {region!r}")
+    return tuple(int(v) for v in region)
+
+
+@_on_tensor_device
+def region_crop(x: torch.Tensor, region, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The sub-box ``region`` = (y0, x0, h, w) of every frame of a contiguous ``x`` [..., H, W] as a contiguous [..., h, w] tensor in
+    ONE launch (``wan_region_crop``); elements of 1, 2 or 4 bytes, bits unchanged.  Serves the loop state and the mask's weights."""
+    if not x.is_cuda:
+        raise RuntimeError(f"region_crop.x: tensor is on {x.device}; the HIP path has no CPU fallback")
+    if x.element_size() not in (1, 2, 4):
+        raise ValueError(f"region_crop: dtype {x.dtype} not supported (elements of 1, 2 or 4 bytes)")
+    if x.dim() < 2 or not x.is_contiguous():
+        raise ValueError(f"region_crop.x: a contiguous [..., H, W] tensor, got {tuple(x.shape)}")
+    y0, x0, hr, wr = _region_box(region, "region_crop")
+    H, W = int(x.shape[-2]), int(x.shape[-1])
+    R = int(math.prod(x.shape[:-2]))
+    out = _region_out(out, tuple(x.shape[:-2]) + (max(hr, 0), max(wr, 0)), x, "region_crop.out")
+    _lib.check(_lib.load().wan_region_crop(_p(out), _p(x), x.element_size(), R, H, W, y0, x0, hr, wr, _stream()), "wan_region_crop")
+    return out
+
+
+@_on_tensor_device
+def region_restore(source: torch.Tensor, state: torch.Tensor, origin, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The full-frame source block ``source`` [B, C, cc, H, W] and the loop's final state on the region ``state`` [B, C, cc + G + cc, hr,
+    wr], whose corner is ``origin`` = (y0, x0), as the full-frame state [B, C, cc + G + cc, H, W] in ONE launch
+    (``wan_region_restore``): source frames are the source; grounding frame g and target frame f are the region's inside its box and
+    source frames g and f outside it, so outside the box the target is the source bit for bit.  Elements of 1, 2 or 4 bytes."""
+    if not source.is_cuda or not state.is_cuda:
+        raise RuntimeError(f"region_restore: tensors are on {source.device} and {state.device}; the HIP path has no CPU fallback")
+    if source.element_size() not in (1, 2, 4):
+        raise ValueError(f"region_restore: dtype {source.dtype} not supported (elements of 1, 2 or 4 bytes)")
+    if source.dim() != 5 or state.dim() != 5 or source.shape[:2] != state.shape[:2] or source.dtype != state.dtype \
+            or source.device != state.device:
+        raise ValueError(f"region_restore: source {source.dtype} {tuple(source.shape)} on {source.device} and state {state.dtype} "
+                         f"{tuple(state.shape)} on {state.device}: expected [B, C, cc, H, W] and [B, C, cc + G + cc, hr, wr] of one dtype")
+    source, state = source.contiguous(), state.contiguous()
+    B, C, cc, H, W = (int(v) for v in source.shape)
+    Ftot, hr, wr = (int(v) for v in state.shape[2:])
+    if len(origin) != 2:
+        raise ValueError(f"region_restore: origin = (y0, x0) in cells, got {origin!r}")
+    out = _region_out(out, (B, C, Ftot, H, W), source, "region_restore.out")
+    _lib.check(_lib.load().wan_region_restore(_p(out), _p(source), _p(state), source.element_size(), B, C, cc, Ftot - 2 * cc, H, W,
+                                              int(origin[0]), int(origin[1]), hr, wr, _stream()), "wan_region_restore")
+    return out
+
+
 def _avail(t: torch.Tensor) -> int:
     """Elements from t's first element to the end of its storage."""
     return t.untyped_storage().nbytes() // t.element_size() - t.storage_offset()

@@ -44,6 +44,7 @@ class WanPipelineOutput:
     edit_videos: Optional[Union[torch.Tensor, np.ndarray]] = None
     latents: Optional[torch.Tensor] = None          # extension: final latents (output_type="latent")
     compare_videos: Optional[Union[torch.Tensor, np.ndarray]] = None   # extension: source | edit side by side (compare=True)
+    edit_region: Optional[tuple] = None             # extension: (y, x, h, w) in pixels, what the loop ran on (edit_region=True); None when off
 
 
 def _require_source(has_source: bool, why: str) -> None:
@@ -367,7 +368,15 @@ class WanPipeline:
             # region ends on the source latents to rounding.  `edit_mask_grow` = (latent cells, latent frames) of margin, `edit_mask_feather`
             # = latent cells of soft edge (video_io.latent_edit_mask); the defaults are guesses.  Opt-in, changes outputs by design; no
             # quality claim.
-            edit_mask=switches.pop("edit_mask", None), edit_mask_grow=switches.pop("edit_mask_grow", (1, 0)), edit_mask_feather=switches.pop("edit_mask_feather", 1))
+            edit_mask=switches.pop("edit_mask", None), edit_mask_grow=switches.pop("edit_mask_grow", (1, 0)), edit_mask_feather=switches.pop("edit_mask_feather", 1),
+            # `edit_region=False, edit_region_margin=(64, 64)` ((rows, columns) in PIXELS, multiples of 16): run the loop only on a rectangle
+            # around the mask's non-zero latent weights (edit_region.region_plan): the loop state and the weights are
+            # cropped once, the ordinary loop runs on the smaller clip -- one `spatial_window` tile where the margined box fits one, tiles
+            # inside the region where it does not -- and the region is put back into the source latents once.  Needs `edit_mask`.  The
+            # model sees the region only and positions start at its corner; `callback_on_step_end` sees the region-sized state, and the SDE
+            # sampler's per-step noise is drawn region-shaped.  The default margin is a guess.  Opt-in and lossy; no quality claim.
+            edit_region=bool(switches.pop("edit_region", False)), edit_region_margin=switches.pop("edit_region_margin", (64, 64)),
+            region_margin=None)                          # set below: the margin in latent cells, checked
         if switches:
             raise TypeError(f"__call__() got an unexpected keyword argument {next(iter(switches))!r}")
         if o.edit_mask is not None:
@@ -386,6 +395,11 @@ class WanPipeline:
             if capture_graph == "loop":
                 raise NotImplementedError("edit_mask with capture_graph='loop': the recorded loop does not hold the mask's weights or "
                                           "the per-step sigma of the replacement (use capture_graph='step')")
+        if o.edit_region:
+            from .edit_region import region_margin_cells
+            if o.edit_mask is None:
+                raise ValueError("edit_region=True: the region is where `edit_mask` is, and this call has no edit_mask")
+            o.region_margin = region_margin_cells(o.edit_region_margin)
         if o.compare:
             if output_type != "uint8":
                 raise ValueError(f"compare=True composes the compare clip from uint8 frames on the device: it needs "
@@ -440,6 +454,37 @@ class WanPipeline:
         if weights.shape[1] != cc:
             raise ValueError(f"edit_mask: {source_frames} mask frames are {weights.shape[1]} latent frames; the source segment has {cc}")
         return weights
+
+    def _crop_to_region(self, o, latents, weights, tile_cells, cc, G):
+        """Edit region, the first of its two stages: the bounds of the non-zero weights (wan_mask_bounds; their 16 bytes
+        per latent frame come to the host -- the ONE synchronisation the option adds to a call), the region (edit_region.region_plan,
+        with the tile of `spatial_window` if that is given), and the loop state and the weights cropped to it (wan_region_crop).
+        Returns (latents, weights, region): `region` is None with the option off -- nothing is launched then -- or (RegionPlan, the
+        full-frame source block to restore into; None where the region is the whole frame and nothing was cropped)."""
+        if not o.edit_region:
+            return latents, weights, None
+        from . import ops
+        from .edit_region import region_plan
+        if G > cc:
+            raise ValueError(f"edit_region: {G} grounding frames for {cc} source frames; outside the region grounding frame g is "
+                             "source frame g, so at most as many")
+        hl, wl = int(latents.shape[3]), int(latents.shape[4])
+        bounds = ops.mask_bounds(weights).cpu()
+        plan = region_plan(bounds, (hl, wl), o.region_margin, None if tile_cells is None else tile_cells[0],
+                           int(self.transformer.config.patch_size[1]))
+        if (plan.h, plan.w) == (hl, wl):
+            return latents, weights, (plan, None)
+        return ops.region_crop(latents.contiguous(), plan), ops.region_crop(weights, plan), (plan, latents[:, :, :cc])
+
+    @staticmethod
+    def _restore_region(latents, region):
+        """Edit region, the second stage: the loop's final state on the region put back into the source latents (wan_region_restore) --
+        outside the region the grounding and target frames are the source's bits."""
+        plan, source = region
+        if source is None:
+            return latents
+        from . import ops
+        return ops.region_restore(source.to(latents.dtype), latents, (plan.y0, plan.x0))
 
     def _plan_windows(self, o, sizes, shape, cc, G, capture_graph):
         """(plan, tiles) of a clip of latent `shape`: the temporal WindowPlan, or None where the clip fits one window (or the option
@@ -761,6 +806,7 @@ class WanPipeline:
         self._stage("vae_encode", t_stage)
         # -- the mask and the windows; what one forward holds: the whole clip, or one window of `win_n` source frames and `win_hw` cells
         mask_weights = self._mask_weights(opt, latents, condition_count, ground_latent_count, source_frames, height, width)
+        latents, mask_weights, region = self._crop_to_region(opt, latents, mask_weights, window_sizes[1], condition_count, ground_latent_count)
         plan, tiles = self._plan_windows(opt, window_sizes, latents.shape, condition_count, ground_latent_count, capture_graph)
         windowed = plan is not None or tiles is not None
         win_n = condition_count if not windowed else tiles.t.window if tiles is not None else plan.window
@@ -805,10 +851,14 @@ class WanPipeline:
                 latents = self._denoise_as_one_graph(key, loop, latents, in_prompt_embeds, timesteps, callback is not None)
             else:
                 latents = loop(latents, in_prompt_embeds)
+        if region is not None:
+            latents = self._restore_region(latents, region)
         self._stage("denoise_loop", t_stage)
         # -- decode (:757-790)
         t_stage = self._stage("vae_decode")
         videos, ground, edit, compared = self._decode_outputs(latents, output_type, cot, condition_count, ground_latent_count,
                                                               opt.compare_source, return_dict)
         self._stage("vae_decode", t_stage)
-        return WanPipelineOutput(videos=videos, ground_videos=ground, edit_videos=edit, latents=latents, compare_videos=compared)
+        return WanPipelineOutput(videos=videos, ground_videos=ground, edit_videos=edit, latents=latents, compare_videos=compared,
+                                 edit_region=None if region is None else region[0].pixels(
+                                     getattr(getattr(self.vae, "config", None), "spatial_compression_ratio", 8)))
