@@ -737,12 +737,31 @@ wan_status_t wan_masked_prediction(void* pred, const void* sample, int dtype, co
  *              target frame f            region[cc + G + f] inside the box, source[f] outside it
  *          so outside the box the target IS the source, bit for bit.
  *      For the last two: a null tensor, another element size, a box that does not lie inside the frame (y0, x0 >= 0; hr, wr >= 1;
- *      y0 + hr <= H; x0 + wr <= W), G outside [0, cc], a frame count or H * W of 2^31 or more -> WAN_ERR_INVALID. */
+ *      y0 + hr <= H; x0 + wr <= W), G outside [0, cc], a frame count or H * W of 2^31 or more -> WAN_ERR_INVALID.
+ *      The same two with a range of frames as well (`edit_region_time_margin`; reference_region_crop_frames and
+ *      reference_region_restore_frames state them), the same kernels behind them:
+ *      wan_region_crop_frames: in [R, F, H, W] -> out [R, Fo, hr, wr]: the box of the frames that `runs` lists.  `runs` is read on the
+ *          HOST: n_runs (1 to 3) pairs (start, count) of input frames, ascending, not overlapping, count >= 1, inside [0, F); Fo is the
+ *          sum of the counts and output frame k is the k-th listed frame.  The loop state takes R = B * C and the runs (t0, n),
+ *          (cc, G), (cc + G + t0, n) (the second left out where G = 0), the weights R = Bm and the run (t0, n).  One run (0, F) is
+ *          wan_region_crop on [R * F, H, W].  Also WAN_ERR_INVALID: null `runs`, n_runs outside 1..3, a run that is empty, descends,
+ *          overlaps its predecessor or leaves [0, F).
+ *      wan_region_restore_frames: source [B, C, cc, H, W], region [B, C, n + G + n, hr, wr] (the loop's final state on the source
+ *          frames [t0, t0 + n) and the box) -> out [B, C, cc + G + cc, H, W]:
+ *              source frame f            source[f]
+ *              grounding frame g         region[n + g] inside the box, source[g] outside it                  (hence 0 <= G <= cc)
+ *              target frame f            region[n + G + f - t0] where t0 <= f < t0 + n and inside the box, source[f] everywhere else
+ *          so outside the range and outside the box the target IS the source, bit for bit; (t0, n) = (0, cc) is wan_region_restore.
+ *          Also WAN_ERR_INVALID: t0 < 0, n < 1, t0 + n > cc. */
 wan_status_t wan_mask_bounds(const void* weights_u8, void* bounds_i32, int Bm, int Fs, int h, int w, void* stream);
 wan_status_t wan_region_crop(void* out, const void* in, int elem_bytes, int64_t R, int H, int W, int y0, int x0, int hr, int wr,
                              void* stream);
 wan_status_t wan_region_restore(void* out, const void* source, const void* region, int elem_bytes, int B, int C, int cc, int G, int H,
                                 int W, int y0, int x0, int hr, int wr, void* stream);
+wan_status_t wan_region_crop_frames(void* out, const void* in, int elem_bytes, int64_t R, int F, int H, int W, const int* runs,
+                                    int n_runs, int y0, int x0, int hr, int wr, void* stream);
+wan_status_t wan_region_restore_frames(void* out, const void* source, const void* region, int elem_bytes, int B, int C, int cc, int G,
+                                       int H, int W, int t0, int n, int y0, int x0, int hr, int wr, void* stream);
 
 /* ===========================================================================
  * WanVAE (videox_fun/models/wan_vae.py).  Activations are CHANNELS-LAST bf16 [T, H, W, C].

@@ -14,7 +14,7 @@ Host side mirrors the reference's interface for this path only:
     videocof_amd.dist                       <- videox_fun/dist/{fuser,wan_xfuser}.py (Ulysses on RCCL)
     videocof_amd.video_io                   <- fast_infer.py load_video_frames + videox_fun/utils/utils.py save_videos_grid's byte conversion
     videocof_amd.windows                    (no counterpart) temporal and spatial context windows: clips longer / frames larger than trained, opt-in
-    videocof_amd.edit_region                (no counterpart) edit region: the denoise loop only on the rectangle the edit mask touches, opt-in and lossy
+    videocof_amd.edit_region                (no counterpart) edit region: the denoise loop only on the rectangle (and, on request, the frame range) the edit mask touches, opt-in and lossy
     videocof_amd.local_attention            (no counterpart) local self-attention: key tiles listed per query block, opt-in and lossy
 
 Device arithmetic lives in ``libwan_hip.so`` (csrc/, C ABI in include/wan_hip.h).
@@ -41,6 +41,8 @@ from .windows import WindowPlan, window_plan, window_latent_frames, reference_wi
 from .windows import TilePlan, spatial_window_cells, reference_tile_gather, reference_tile_blend  # noqa: F401
 from .edit_region import (RegionPlan, region_plan, region_margin_cells, reference_mask_bounds, reference_region_crop,  # noqa: F401
                           reference_region_restore)
+from .edit_region import (TimeRegion, region_time_plan, region_time_margin_frames, reference_region_crop_frames,  # noqa: F401
+                          reference_region_restore_frames)
 from .local_attention import LocalAttentionPlan, local_attention_plan, reference_local_mask, reference_sparse_attention  # noqa: F401
 
 __version__ = "0.1.0"

@@ -2,6 +2,10 @@
 //   wan_mask_bounds      latent-cell weights uint8 [Bm, Fs, h, w] -> per latent frame the inclusive bounds of the non-zero weights
 //   wan_region_crop      the sub-box [y0, y0 + hr) x [x0, x0 + wr) of every frame of a contiguous [R, H, W] tensor -> [R, hr, wr]
 //   wan_region_restore   the full-frame source block and the region-sized final state -> the full-frame state, in one launch
+// and, where the call crops the time axis too (`edit_region_time_margin`: one contiguous range of latent frames, the approximation of
+// the temporal context windows, whose first latent frame is not the clip's first either), the same two kernels with a range of frames:
+//   wan_region_crop_frames      the sub-box of up to three runs of frames of a contiguous [R, F, H, W] tensor -> [R, Fo, hr, wr]
+//   wan_region_restore_frames   the region holds the source frames [t0, t0 + n) only: target frames outside the range are the source
 // All three are streams of rows at a pitch: the access unit is the widest of 16 / 8 / 4 bytes or one element that divides every length,
 // pitch, x origin and base address (region_unit_bytes below: the rule of tile_unit_bytes in window_kernels.hip), so all x arithmetic is
 // in whole units and no unit straddles the region's edge.  A workgroup is `rp` rows of `cw` lanes each (cw = min(units per row, 256),
@@ -80,12 +84,25 @@ __global__ __launch_bounds__(256) void mask_bounds_kernel(int* __restrict__ boun
 }
 
 // ------------------------------------------------------------------------------------------------------------- the crop
-// grid (frame, row chunk); `fu` = H * W, `pitch` = W, `ru` = wr, `org` = y0 * W + x0, all in units
+// up to three runs (start, count) of input frames, ascending; an unused run has count 0 and is never reached
+struct FrameRuns { int start[3]; int count[3]; };
+
+// grid (sample * Fo + output frame, row chunk); `F` input and `Fo` output frames per sample, `fu` = H * W, `pitch` = W, `ru` = wr,
+// `org` = y0 * W + x0, all in units.  Which input frame stands behind an output frame is read off the runs, per workgroup.
 template <typename U>
-__global__ __launch_bounds__(256) void region_crop_kernel(U* __restrict__ out, const U* __restrict__ in, int64_t fu, int pitch,
-                                                          int64_t org, int hr, int ru, int cw, int rp) {
-    const U* src = in + (int64_t)blockIdx.x * fu + org;                 // frame < R (the grid); the box lies inside it (checked by the host)
-    U* dst = out + (int64_t)blockIdx.x * hr * ru;
+__global__ __launch_bounds__(256) void region_crop_kernel(U* __restrict__ out, const U* __restrict__ in, FrameRuns runs, unsigned Fo,
+                                                          int F, int64_t fu, int pitch, int64_t org, int hr, int ru, int cw, int rp) {
+    const unsigned row = blockIdx.x;                  // < R * Fo (the grid)
+    int k = (int)(row % Fo);                          // < the sum of the counts
+    const int64_t sample = row / Fo;
+    int f = runs.start[0] + k;
+    if (k >= runs.count[0]) {
+        k -= runs.count[0];
+        f = runs.start[1] + k;
+        if (k >= runs.count[1]) f = runs.start[2] + k - runs.count[1];
+    }
+    const U* src = in + (sample * F + f) * fu + org;  // f < F, and the box lies inside the frame (checked by the host)
+    U* dst = out + (int64_t)row * hr * ru;
     const int lr = threadIdx.x / cw, lu = threadIdx.x % cw;
     if (lr >= rp) return;
     for (int r0 = blockIdx.y * UNROLL * rp; r0 < hr; r0 += gridDim.y * UNROLL * rp)
@@ -105,20 +122,23 @@ __global__ __launch_bounds__(256) void region_crop_kernel(U* __restrict__ out, c
 }
 
 // ------------------------------------------------------------------------------------------------------------- the restore
-// grid (output frame = (b * C + c) * (2 cc + G) + F, row chunk); `wu` = W, `x0u` = x0, `ru` = wr in units.  Which source frame stands
-// behind output frame F, and whether F takes the region at all, is per workgroup; a lane picks one of two addresses and loads once.
+// grid (output frame = (b * C + c) * (2 cc + G) + F, row chunk); `wu` = W, `x0u` = x0, `ru` = wr in units.  The region holds the frames
+// [source t0 .. t0 + n | grounding | target t0 .. t0 + n].  Which source frame stands behind output frame F, and whether F takes the
+// region at all (and from which of its frames), is per workgroup; a lane picks one of two addresses and loads once.
 template <typename U>
 __global__ __launch_bounds__(256) void region_restore_kernel(U* __restrict__ out, const U* __restrict__ source,
-                                                             const U* __restrict__ region, int cc, int G, int H, int wu, int y0,
-                                                             int x0u, int hr, int ru, int cw, int rp) {
+                                                             const U* __restrict__ region, int cc, int G, int t0, int n, int H, int wu,
+                                                             int y0, int x0u, int hr, int ru, int cw, int rp) {
     const unsigned Ftot = (unsigned)(2 * cc + G);
     const unsigned row = blockIdx.x;                  // < B * C * Ftot (the grid)
     const int F = (int)(row % Ftot);
     const int64_t bc = row / Ftot;
     const int sf = F < cc ? F : F < cc + G ? F - cc : F - cc - G;       // < cc: G <= cc (checked by the host)
-    const bool mixed = F >= cc;                       // grounding and target frames take the region inside its box
+    // grounding frames, and target frames of the range, take the region inside its box: rf is their frame there (< 2 n + G), -1: none
+    const int rf = F < cc ? -1 : F < cc + G ? n + (F - cc) : (sf >= t0 && sf < t0 + n) ? n + G + (sf - t0) : -1;
+    const bool mixed = rf >= 0;
     const U* s = source + (bc * cc + sf) * H * wu;
-    const U* r = region + (int64_t)row * hr * ru;
+    const U* r = region + (bc * (2 * n + G) + (mixed ? rf : 0)) * hr * ru;
     U* o = out + (int64_t)row * H * wu;
     const int lr = threadIdx.x / cw, lu = threadIdx.x % cw;
     if (lr >= rp) return;
@@ -191,56 +211,95 @@ extern "C" wan_status_t wan_mask_bounds(const void* weights_u8, void* bounds_i32
         else LAUNCH(unsigned char);                                      \
     } while (0)
 
-extern "C" wan_status_t wan_region_crop(void* out, const void* in, int elem_bytes, int64_t R, int H, int W, int y0, int x0, int hr,
-                                        int wr, void* stream) {
-    // (the box first: an empty region's output is an empty tensor, whose address is null)
-    WAN_REQUIRE(R >= 1 && box_ok(H, W, y0, x0, hr, wr), WAN_ERR_INVALID,
-                "wan_region_crop: the region [%d, %d + %d) x [%d, %d + %d) does not lie inside %lld frames of %d x %d", y0, y0, hr, x0, x0,
-                wr, (long long)R, H, W);
-    WAN_REQUIRE(out && in, WAN_ERR_INVALID, "wan_region_crop: null tensor");
-    WAN_REQUIRE(elem_bytes == 1 || elem_bytes == 2 || elem_bytes == 4, WAN_ERR_INVALID, "wan_region_crop: elements of %d bytes (1, 2 or 4)",
+// the crop behind both of its entry points (`who` names the one called in the messages)
+static wan_status_t crop_frames(const char* who, void* out, const void* in, int elem_bytes, int64_t R, int F, int H, int W,
+                                const int* runs, int n_runs, int y0, int x0, int hr, int wr, void* stream) {
+    // (the box and the runs first: an empty region's or an empty range's output is an empty tensor, whose address is null)
+    WAN_REQUIRE(R >= 1 && F >= 1 && box_ok(H, W, y0, x0, hr, wr), WAN_ERR_INVALID,
+                "%s: the region [%d, %d + %d) x [%d, %d + %d) does not lie inside %lld x %d frames of %d x %d", who, y0, y0, hr, x0, x0, wr,
+                (long long)R, F, H, W);
+    WAN_REQUIRE(runs && n_runs >= 1 && n_runs <= 3, WAN_ERR_INVALID, "%s: %d runs of frames at %p (1 to 3, not null)", who, n_runs,
+                (const void*)runs);
+    FrameRuns fr = {{0, 0, 0}, {0, 0, 0}};
+    int64_t Fo = 0;
+    for (int i = 0, end = 0; i < n_runs; ++i) {
+        const int start = runs[2 * i], count = runs[2 * i + 1];
+        WAN_REQUIRE(start >= end && count >= 1 && (int64_t)start + count <= F, WAN_ERR_INVALID,
+                    "%s: run %d = frames [%d, %d + %d) of %d (ascending, not overlapping, at least one frame each, inside the clip)", who, i,
+                    start, start, count, F);
+        fr.start[i] = start; fr.count[i] = count;
+        end = start + count;
+        Fo += count;
+    }
+    WAN_REQUIRE(out && in, WAN_ERR_INVALID, "%s: null tensor", who);
+    WAN_REQUIRE(elem_bytes == 1 || elem_bytes == 2 || elem_bytes == 4, WAN_ERR_INVALID, "%s: elements of %d bytes (1, 2 or 4)", who,
                 elem_bytes);
-    WAN_REQUIRE(R <= 0x7fffffff && (int64_t)H * W <= 0x7fffffff, WAN_ERR_INVALID,
-                "wan_region_crop: %lld frames of %lld elements (each at most 2^31 - 1)", (long long)R, (long long)((int64_t)H * W));
-    const int64_t es = elem_bytes;
+    WAN_REQUIRE(R <= 0x7fffffff && R * F <= 0x7fffffff && (int64_t)H * W <= 0x7fffffff, WAN_ERR_INVALID,
+                "%s: %lld clips of %d frames of %lld elements (frames in all and elements a frame: each at most 2^31 - 1)", who,
+                (long long)R, F, (long long)((int64_t)H * W));
+    const int64_t es = elem_bytes, frames = R * Fo;
     const int ub = region_unit_bytes(es, {W, wr, x0}, (uintptr_t)out | (uintptr_t)in);
     const int N = (int)(ub / es), ru = wr / N, cw = std::min(ru, 256), rp = 256 / cw;
-    const dim3 grid((unsigned)R, row_chunks(hr, UNROLL * rp, R));
+    const dim3 grid((unsigned)frames, row_chunks(hr, UNROLL * rp, frames));
     hipStream_t s = (hipStream_t)stream;
 #define WAN_CROP(U)                                                                                                            \
-    hipLaunchKernelGGL(region_crop_kernel<U>, grid, dim3(256), 0, s, (U*)out, (const U*)in, (int64_t)H * W / N, W / N,         \
-                       ((int64_t)y0 * W + x0) / N, hr, ru, cw, rp)
+    hipLaunchKernelGGL(region_crop_kernel<U>, grid, dim3(256), 0, s, (U*)out, (const U*)in, fr, (unsigned)Fo, F,               \
+                       (int64_t)H * W / N, W / N, ((int64_t)y0 * W + x0) / N, hr, ru, cw, rp)
     WAN_BY_UNIT(ub, WAN_CROP);
 #undef WAN_CROP
-    WAN_CHECK_LAUNCH("wan_region_crop");
+    WAN_CHECK_LAUNCH(who);
     return WAN_OK;
 }
 
-extern "C" wan_status_t wan_region_restore(void* out, const void* source, const void* region, int elem_bytes, int B, int C, int cc,
-                                           int G, int H, int W, int y0, int x0, int hr, int wr, void* stream) {
-    WAN_REQUIRE(out && source && region, WAN_ERR_INVALID, "wan_region_restore: null tensor");
-    WAN_REQUIRE(elem_bytes == 1 || elem_bytes == 2 || elem_bytes == 4, WAN_ERR_INVALID,
-                "wan_region_restore: elements of %d bytes (1, 2 or 4)", elem_bytes);
-    WAN_REQUIRE(B >= 1 && C >= 1 && cc >= 1, WAN_ERR_INVALID, "wan_region_restore: B=%d C=%d cc=%d", B, C, cc);
+extern "C" wan_status_t wan_region_crop(void* out, const void* in, int elem_bytes, int64_t R, int H, int W, int y0, int x0, int hr,
+                                        int wr, void* stream) {
+    const int every[2] = {0, 1};                      // R clips of one frame each, every one kept
+    return crop_frames("wan_region_crop", out, in, elem_bytes, R, 1, H, W, every, 1, y0, x0, hr, wr, stream);
+}
+
+extern "C" wan_status_t wan_region_crop_frames(void* out, const void* in, int elem_bytes, int64_t R, int F, int H, int W,
+                                               const int* runs, int n_runs, int y0, int x0, int hr, int wr, void* stream) {
+    return crop_frames("wan_region_crop_frames", out, in, elem_bytes, R, F, H, W, runs, n_runs, y0, x0, hr, wr, stream);
+}
+
+// the restore behind both of its entry points
+static wan_status_t restore_frames(const char* who, void* out, const void* source, const void* region, int elem_bytes, int B, int C,
+                                   int cc, int G, int H, int W, int t0, int n, int y0, int x0, int hr, int wr, void* stream) {
+    WAN_REQUIRE(out && source && region, WAN_ERR_INVALID, "%s: null tensor", who);
+    WAN_REQUIRE(elem_bytes == 1 || elem_bytes == 2 || elem_bytes == 4, WAN_ERR_INVALID, "%s: elements of %d bytes (1, 2 or 4)", who,
+                elem_bytes);
+    WAN_REQUIRE(B >= 1 && C >= 1 && cc >= 1, WAN_ERR_INVALID, "%s: B=%d C=%d cc=%d", who, B, C, cc);
     WAN_REQUIRE(0 <= G && G <= cc, WAN_ERR_INVALID,
-                "wan_region_restore: G=%d grounding frames for cc=%d source frames (grounding frame g takes source frame g outside the "
-                "region: 0 <= G <= cc)", G, cc);
+                "%s: G=%d grounding frames for cc=%d source frames (grounding frame g takes source frame g outside the region: "
+                "0 <= G <= cc)", who, G, cc);
+    WAN_REQUIRE(t0 >= 0 && n >= 1 && (int64_t)t0 + n <= cc, WAN_ERR_INVALID,
+                "%s: the frames [%d, %d + %d) do not lie inside the %d source frames", who, t0, t0, n, cc);
     WAN_REQUIRE(box_ok(H, W, y0, x0, hr, wr), WAN_ERR_INVALID,
-                "wan_region_restore: the region [%d, %d + %d) x [%d, %d + %d) does not lie inside a frame of %d x %d", y0, y0, hr, x0, x0, wr,
-                H, W);
+                "%s: the region [%d, %d + %d) x [%d, %d + %d) does not lie inside a frame of %d x %d", who, y0, y0, hr, x0, x0, wr, H, W);
     const int64_t frames = (int64_t)B * C * (2 * (int64_t)cc + G);
     WAN_REQUIRE(frames <= 0x7fffffff && (int64_t)H * W <= 0x7fffffff, WAN_ERR_INVALID,
-                "wan_region_restore: %lld frames of %lld elements (each at most 2^31 - 1)", (long long)frames, (long long)((int64_t)H * W));
+                "%s: %lld frames of %lld elements (each at most 2^31 - 1)", who, (long long)frames, (long long)((int64_t)H * W));
     const int64_t es = elem_bytes;
     const int ub = region_unit_bytes(es, {W, wr, x0}, (uintptr_t)out | (uintptr_t)source | (uintptr_t)region);
     const int N = (int)(ub / es), wu = W / N, cw = std::min(wu, 256), rp = 256 / cw;
     const dim3 grid((unsigned)frames, row_chunks(H, UNROLL * rp, frames));
     hipStream_t s = (hipStream_t)stream;
 #define WAN_RESTORE(U)                                                                                                         \
-    hipLaunchKernelGGL(region_restore_kernel<U>, grid, dim3(256), 0, s, (U*)out, (const U*)source, (const U*)region, cc, G, H, wu, y0, \
-                       x0 / N, hr, wr / N, cw, rp)
+    hipLaunchKernelGGL(region_restore_kernel<U>, grid, dim3(256), 0, s, (U*)out, (const U*)source, (const U*)region, cc, G, t0, n, H, \
+                       wu, y0, x0 / N, hr, wr / N, cw, rp)
     WAN_BY_UNIT(ub, WAN_RESTORE);
 #undef WAN_RESTORE
-    WAN_CHECK_LAUNCH("wan_region_restore");
+    WAN_CHECK_LAUNCH(who);
     return WAN_OK;
+}
+
+extern "C" wan_status_t wan_region_restore(void* out, const void* source, const void* region, int elem_bytes, int B, int C, int cc,
+                                           int G, int H, int W, int y0, int x0, int hr, int wr, void* stream) {
+    return restore_frames("wan_region_restore", out, source, region, elem_bytes, B, C, cc, G, H, W, 0, cc, y0, x0, hr, wr, stream);
+}
+
+extern "C" wan_status_t wan_region_restore_frames(void* out, const void* source, const void* region, int elem_bytes, int B, int C,
+                                                  int cc, int G, int H, int W, int t0, int n, int y0, int x0, int hr, int wr,
+                                                  void* stream) {
+    return restore_frames("wan_region_restore_frames", out, source, region, elem_bytes, B, C, cc, G, H, W, t0, n, y0, x0, hr, wr, stream);
 }

@@ -5,8 +5,13 @@ With ``edit_mask`` the loop already pins everything outside the mask to the sour
 state once to a rectangle around the mask's non-zero latent weights, runs the ordinary loop on that smaller clip and puts the result
 back into the source latents once.  ``region_plan`` fixes the rectangle; ``reference_mask_bounds`` / ``reference_region_crop`` /
 ``reference_region_restore`` state what ``wan_mask_bounds`` / ``wan_region_crop`` / ``wan_region_restore`` compute (ops.mask_bounds,
-ops.region_crop, ops.region_restore), bit for bit.  The time axis is never cropped: the first latent frame of the causal VAE is special,
-and a temporal crop would move it.
+ops.region_crop, ops.region_restore), bit for bit.
+
+The time axis is cropped only where the call gives ``edit_region_time_margin``: ``region_time_plan`` then fixes ONE contiguous range of
+latent frames around the frames the mask touches, and ``reference_region_crop_frames`` / ``reference_region_restore_frames`` state what
+``wan_region_crop_frames`` / ``wan_region_restore_frames`` compute.  The model then sees a clip whose first latent frame is not the
+clip's first (the causal VAE's special frame) -- as every temporal context window but the first does already: the same
+class of approximation, opt-in, lossy, no quality claim.
 """
 from __future__ import annotations
 
@@ -16,7 +21,8 @@ import numpy as np
 import torch
 
 __all__ = ["RegionPlan", "region_plan", "region_margin_cells", "reference_mask_bounds", "reference_region_crop",
-           "reference_region_restore"]
+           "reference_region_restore", "TimeRegion", "region_time_plan", "region_time_margin_frames", "reference_region_crop_frames",
+           "reference_region_restore_frames"]
 
 REGION_MARGIN_UNIT = 16         # pixels: the VAE's spatial ratio 8 times the patch 2 -- a margin keeps the region on the patch grid
 
@@ -102,6 +108,57 @@ def region_margin_cells(margin, ratio: int = 8) -> Tuple[int, int]:
     return int(margin[0]) // ratio, int(margin[1]) // ratio
 
 
+class TimeRegion(NamedTuple):
+    """The frames the loop runs on, in LATENT frames of the source segment: [t0, t0 + n)."""
+    t0: int
+    n: int
+
+    def pixels(self, ratio: int = 4) -> Tuple[int, int]:
+        """(first pixel frame, pixel frame count): the causal VAE's first latent frame is one pixel frame, every other ``ratio``."""
+        first = 0 if self.t0 == 0 else ratio * self.t0 - (ratio - 1)
+        return first, ratio * (self.t0 + self.n - 1) - first + 1
+
+
+def region_time_plan(bounds, frames: int, margin_frames: int, ground: int = 0) -> TimeRegion:
+    """The frame range of a mask whose non-zero latent weights have the per-frame ``bounds`` [Fs, 4] of ``mask_bounds``.  With lo, hi
+    the first and last non-empty row (y_hi >= y_lo and x_hi >= x_lo), Fs = ``frames`` the source segment's latent frames, m =
+    ``margin_frames`` latent frames of context on either side and G = ``ground`` grounding frames:
+
+        core = hi - lo + 1 + 2 m
+        n    = min(Fs, max(core, 2, G))
+        t0   = clamp(lo - m - max(n - core, 0) // 2, 0, Fs - n)
+
+    The floor max(2, G) keeps the cropped clip a layout the model, ``window_plan`` (windows of at least 2 frames) and the restore
+    (G <= n) accept.  The range lies inside the clip and contains [lo - m, hi + m] clipped to it.  It is NOT widened to the temporal
+    window's length (unlike the one-tile rule in space): every length up to the window is a trained one, and attention grows with
+    n squared.  An empty mask raises ``ValueError``."""
+    b = np.asarray(bounds.cpu() if torch.is_tensor(bounds) else bounds, dtype=np.int64).reshape(-1, 4)
+    for name, v, least in (("frames", frames, 1), ("margin_frames", margin_frames, 0), ("ground", ground, 0)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or v < least:
+            raise ValueError(f"region_time_plan: {name}={v!r}: an integer >= {least}")
+    Fs, m, G = int(frames), int(margin_frames), int(ground)
+    if b.shape[0] != Fs:
+        raise ValueError(f"region_time_plan: {b.shape[0]} rows of bounds for {Fs} latent frames")
+    on = np.flatnonzero((b[:, 1] >= b[:, 0]) & (b[:, 3] >= b[:, 2]))
+    if on.size == 0:
+        raise ValueError("edit_mask is empty (every latent weight is zero): there is no region to run the loop on")
+    lo, hi = int(on[0]), int(on[-1])
+    core = hi - lo + 1 + 2 * m
+    n = min(Fs, max(core, 2, G))
+    t0 = lo - m - max(n - core, 0) // 2
+    return TimeRegion(min(max(t0, 0), Fs - n), n)
+
+
+def region_time_margin_frames(margin, ratio: int = 4) -> int:
+    """The pipeline's ``edit_region_time_margin`` in PIXEL frames as latent frames: a non-negative multiple of the VAE's temporal
+    ratio."""
+    if isinstance(margin, bool) or not isinstance(margin, (int, np.integer)):
+        raise ValueError(f"edit_region_time_margin={margin!r} is not an integer count of pixel frames")
+    if margin < 0 or margin % ratio:
+        raise ValueError(f"edit_region_time_margin={margin} must be a non-negative multiple of {ratio} pixel frames (the VAE's temporal ratio)")
+    return int(margin) // ratio
+
+
 # ------------------------------------------------------------------------------------------------ the device passes, in torch
 def reference_mask_bounds(weights: torch.Tensor) -> torch.Tensor:
     """``wan_mask_bounds`` in torch: weights uint8 [Bm, Fs, h, w] -> int32 [Fs, 4] = (y_lo, y_hi, x_lo, x_hi) per latent frame, the
@@ -150,4 +207,51 @@ def reference_region_restore(source: torch.Tensor, state: torch.Tensor, origin) 
                           "reference_region_restore")
     out = torch.cat([source, source[:, :, :G], source], dim=2)
     out[:, :, cc:, y0:y0 + hr, x0:x0 + wr] = state[:, :, cc:]
+    return out
+
+
+def _runs(runs, F: int, who: str):
+    runs = [(int(a), int(c)) for a, c in runs]
+    end = 0
+    if not 1 <= len(runs) <= 3:
+        raise ValueError(f"{who}: {len(runs)} runs of frames (1 to 3 pairs (start, count))")
+    for a, c in runs:
+        if a < end or c < 1 or a + c > F:
+            raise ValueError(f"{who}: the run [{a}, {a} + {c}) of runs {runs} is empty, descends, overlaps or leaves the {F} frames")
+        end = a + c
+    return runs
+
+
+def reference_region_crop_frames(x: torch.Tensor, runs, region) -> torch.Tensor:
+    """``wan_region_crop_frames`` in torch: ``x`` [..., F, H, W]; ``runs`` = 1 to 3 pairs (start, count) of frames, ascending and not
+    overlapping; the sub-box ``region`` = (y0, x0, h, w) of the listed frames, one run after the other, contiguous."""
+    if x.dim() < 3:
+        raise ValueError(f"reference_region_crop_frames: expected [..., F, H, W], got {tuple(x.shape)}")
+    runs = _runs(runs, x.shape[-3], "reference_region_crop_frames")
+    y0, x0, hr, wr = _box(region, x.shape[-2], x.shape[-1], "reference_region_crop_frames")
+    return torch.cat([x[..., a:a + c, y0:y0 + hr, x0:x0 + wr] for a, c in runs], dim=-3).contiguous()
+
+
+def reference_region_restore_frames(source: torch.Tensor, state: torch.Tensor, origin, frames) -> torch.Tensor:
+    """``wan_region_restore_frames`` in torch: ``source`` [B, C, cc, H, W] and ``state`` [B, C, n + G + n, hr, wr], the loop's final state
+    on the source frames ``frames`` = (t0, n) and the box whose corner is ``origin`` = (y0, x0) -> the whole state [B, C, cc + G + cc,
+    H, W]: the source frames are the source; grounding frame g is the region's inside the box and source frame g outside; target frame f
+    is the region's where t0 <= f < t0 + n and inside the box, and source frame f everywhere else."""
+    if source.dim() != 5 or state.dim() != 5 or source.shape[:2] != state.shape[:2] or source.dtype != state.dtype:
+        raise ValueError(f"reference_region_restore_frames: source {source.dtype} {tuple(source.shape)} and state {state.dtype} "
+                         f"{tuple(state.shape)}: expected [B, C, cc, H, W] and [B, C, n + G + n, hr, wr] of one dtype")
+    if len(frames) != 2:
+        raise ValueError(f"reference_region_restore_frames: frames = (t0, n) in latent frames, got {frames!r}")
+    t0, n = int(frames[0]), int(frames[1])
+    cc, G = source.shape[2], state.shape[2] - 2 * n
+    if t0 < 0 or n < 1 or t0 + n > cc:
+        raise ValueError(f"reference_region_restore_frames: the frames [{t0}, {t0} + {n}) do not lie inside the {cc} source frames")
+    if not 0 <= G <= cc:
+        raise ValueError(f"reference_region_restore_frames: {state.shape[2]} state frames for a range of {n}: G={G} grounding frames "
+                         f"(0 <= G <= cc = {cc})")
+    y0, x0, hr, wr = _box((origin[0], origin[1], state.shape[3], state.shape[4]), source.shape[3], source.shape[4],
+                          "reference_region_restore_frames")
+    out = torch.cat([source, source[:, :, :G], source], dim=2)
+    out[:, :, cc:cc + G, y0:y0 + hr, x0:x0 + wr] = state[:, :, n:n + G]
+    out[:, :, cc + G + t0:cc + G + t0 + n, y0:y0 + hr, x0:x0 + wr] = state[:, :, n + G:]
     return out

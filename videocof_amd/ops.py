@@ -1715,6 +1715,62 @@ def region_restore(source: torch.Tensor, state: torch.Tensor, origin, out: Optio
     return out
 
 
+@_on_tensor_device
+def region_crop_frames(x: torch.Tensor, runs, region, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The sub-box ``region`` = (y0, x0, h, w) of the frames that ``runs`` lists of a contiguous ``x`` [..., F, H, W], as a contiguous
+    [..., Fo, h, w] tensor in ONE launch (``wan_region_crop_frames``).  ``runs``: 1 to 3 pairs (start, count) of frames, ascending and not
+    overlapping; Fo is the sum of the counts.  Elements of 1, 2 or 4 bytes, bits unchanged.  Serves the loop state (the runs of its
+    source, grounding and target segments) and the mask's weights (one run)."""
+    if not x.is_cuda:
+        raise RuntimeError(f"region_crop_frames.x: tensor is on {x.device}; the HIP path has no CPU fallback")
+    if x.element_size() not in (1, 2, 4):
+        raise ValueError(f"region_crop_frames: dtype {x.dtype} not supported (elements of 1, 2 or 4 bytes)")
+    if x.dim() < 3 or not x.is_contiguous():
+        raise ValueError(f"region_crop_frames.x: a contiguous [..., F, H, W] tensor, got {tuple(x.shape)}")
+    y0, x0, hr, wr = _region_box(region, "region_crop_frames")
+    runs = list(runs)
+    if any(not hasattr(pair, "__len__") or len(pair) != 2 for pair in runs):
+        raise ValueError(f"region_crop_frames: runs = pairs (start, count) of frames, got {runs!r}")
+    flat = [int(v) for pair in runs for v in pair]
+    F, H, W = (int(v) for v in x.shape[-3:])
+    R = int(math.prod(x.shape[:-3]))
+    Fo = sum(max(c, 0) for c in flat[1::2])
+    out = _region_out(out, tuple(x.shape[:-3]) + (Fo, max(hr, 0), max(wr, 0)), x, "region_crop_frames.out")
+    _lib.check(_lib.load().wan_region_crop_frames(_p(out), _p(x), x.element_size(), R, F, H, W, (ctypes.c_int * max(len(flat), 1))(*flat),
+                                                  len(flat) // 2, y0, x0, hr, wr, _stream()), "wan_region_crop_frames")
+    return out
+
+
+@_on_tensor_device
+def region_restore_frames(source: torch.Tensor, state: torch.Tensor, origin, frames, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The whole source block ``source`` [B, C, cc, H, W] and the loop's final state ``state`` [B, C, n + G + n, hr, wr] on the source
+    frames ``frames`` = (t0, n) and the box whose corner is ``origin`` = (y0, x0), as the whole state [B, C, cc + G + cc, H, W] in ONE
+    launch (``wan_region_restore_frames``): source frames are the source; grounding frame g is the region's inside the box and source
+    frame g outside it; target frame f is the region's where t0 <= f < t0 + n and inside the box, and source frame f everywhere else,
+    bit for bit.  Elements of 1, 2 or 4 bytes."""
+    if not source.is_cuda or not state.is_cuda:
+        raise RuntimeError(f"region_restore_frames: tensors are on {source.device} and {state.device}; the HIP path has no CPU fallback")
+    if source.element_size() not in (1, 2, 4):
+        raise ValueError(f"region_restore_frames: dtype {source.dtype} not supported (elements of 1, 2 or 4 bytes)")
+    if source.dim() != 5 or state.dim() != 5 or source.shape[:2] != state.shape[:2] or source.dtype != state.dtype \
+            or source.device != state.device:
+        raise ValueError(f"region_restore_frames: source {source.dtype} {tuple(source.shape)} on {source.device} and state {state.dtype} "
+                         f"{tuple(state.shape)} on {state.device}: expected [B, C, cc, H, W] and [B, C, n + G + n, hr, wr] of one dtype")
+    source, state = source.contiguous(), state.contiguous()
+    B, C, cc, H, W = (int(v) for v in source.shape)
+    Fr, hr, wr = (int(v) for v in state.shape[2:])
+    if len(origin) != 2:
+        raise ValueError(f"region_restore_frames: origin = (y0, x0) in cells, got {origin!r}")
+    if len(frames) != 2:
+        raise ValueError(f"region_restore_frames: frames = (t0, n) in latent frames, got {frames!r}")
+    t0, n = int(frames[0]), int(frames[1])
+    G = Fr - 2 * n
+    out = _region_out(out, (B, C, max(2 * cc + G, 0), H, W), source, "region_restore_frames.out")
+    _lib.check(_lib.load().wan_region_restore_frames(_p(out), _p(source), _p(state), source.element_size(), B, C, cc, G, H, W, t0, n,
+                                                     int(origin[0]), int(origin[1]), hr, wr, _stream()), "wan_region_restore_frames")
+    return out
+
+
 def _avail(t: torch.Tensor) -> int:
     """Elements from t's first element to the end of its storage."""
     return t.untyped_storage().nbytes() // t.element_size() - t.storage_offset()

@@ -45,6 +45,7 @@ class WanPipelineOutput:
     latents: Optional[torch.Tensor] = None          # extension: final latents (output_type="latent")
     compare_videos: Optional[Union[torch.Tensor, np.ndarray]] = None   # extension: source | edit side by side (compare=True)
     edit_region: Optional[tuple] = None             # extension: (y, x, h, w) in pixels, what the loop ran on (edit_region=True); None when off
+    edit_region_time: Optional[tuple] = None        # extension: (first pixel frame, pixel frame count) of it (edit_region_time_margin); None when off
 
 
 def _require_source(has_source: bool, why: str) -> None:
@@ -376,7 +377,15 @@ class WanPipeline:
             # model sees the region only and positions start at its corner; `callback_on_step_end` sees the region-sized state, and the SDE
             # sampler's per-step noise is drawn region-shaped.  The default margin is a guess.  Opt-in and lossy; no quality claim.
             edit_region=bool(switches.pop("edit_region", False)), edit_region_margin=switches.pop("edit_region_margin", (64, 64)),
-            region_margin=None)                          # set below: the margin in latent cells, checked
+            region_margin=None,                          # set below: the margin in latent cells, checked
+            # `edit_region_time_margin=None` (PIXEL frames, a multiple of 4): with `edit_region=True`, crop the time axis too -- the loop
+            # runs on ONE contiguous range of latent frames around the frames the mask touches, with this much context on either side
+            # (edit_region.region_time_plan), as the whole-clip form where the range fits one `temporal_window`, as windows inside the
+            # range where it does not.  Positions start at the range's first frame; the source is still encoded whole and the decode is
+            # whole-clip.  None: the time axis is not cropped.  There is no default margin: any value is a guess.  Opt-in and lossy, the
+            # class of approximation of temporal context windows; no quality claim.
+            edit_region_time_margin=switches.pop("edit_region_time_margin", None),
+            region_time_margin=None)                     # set below: the margin in latent frames, checked (None: no time crop)
         if switches:
             raise TypeError(f"__call__() got an unexpected keyword argument {next(iter(switches))!r}")
         if o.edit_mask is not None:
@@ -400,6 +409,12 @@ class WanPipeline:
             if o.edit_mask is None:
                 raise ValueError("edit_region=True: the region is where `edit_mask` is, and this call has no edit_mask")
             o.region_margin = region_margin_cells(o.edit_region_margin)
+        if o.edit_region_time_margin is not None:
+            from .edit_region import region_time_margin_frames
+            o.region_time_margin = region_time_margin_frames(o.edit_region_time_margin)
+            if not o.edit_region:
+                raise ValueError("edit_region_time_margin extends edit_region=True (the frame range is cropped with the rectangle), and "
+                                 "this call does not set it")
         if o.compare:
             if output_type != "uint8":
                 raise ValueError(f"compare=True composes the compare clip from uint8 frames on the device: it needs "
@@ -459,12 +474,15 @@ class WanPipeline:
         """Edit region, the first of its two stages: the bounds of the non-zero weights (wan_mask_bounds; their 16 bytes
         per latent frame come to the host -- the ONE synchronisation the option adds to a call), the region (edit_region.region_plan,
         with the tile of `spatial_window` if that is given), and the loop state and the weights cropped to it (wan_region_crop).
-        Returns (latents, weights, region): `region` is None with the option off -- nothing is launched then -- or (RegionPlan, the
-        full-frame source block to restore into; None where the region is the whole frame and nothing was cropped)."""
+        With `edit_region_time_margin` the frame range (edit_region.region_time_plan) comes from the same host copy of the bounds, and
+        state and weights are cropped in frames and cells at once (wan_region_crop_frames, still one launch each).
+        Returns (latents, weights, region, the source frames of the loop's clip): `region` is None with the option off -- nothing is
+        launched then -- or (RegionPlan, the whole source block to restore into; None where nothing was cropped, the TimeRegion; None
+        without a time crop)."""
         if not o.edit_region:
-            return latents, weights, None
+            return latents, weights, None, cc
         from . import ops
-        from .edit_region import region_plan
+        from .edit_region import region_plan, region_time_plan
         if G > cc:
             raise ValueError(f"edit_region: {G} grounding frames for {cc} source frames; outside the region grounding frame g is "
                              "source frame g, so at most as many")
@@ -472,18 +490,28 @@ class WanPipeline:
         bounds = ops.mask_bounds(weights).cpu()
         plan = region_plan(bounds, (hl, wl), o.region_margin, None if tile_cells is None else tile_cells[0],
                            int(self.transformer.config.patch_size[1]))
+        if o.region_time_margin is not None:
+            span = region_time_plan(bounds, cc, o.region_time_margin, G)
+            if (plan.h, plan.w, span.n) == (hl, wl, cc):
+                return latents, weights, (plan, None, span), cc
+            t0, n = span
+            runs = [(t0, n)] + ([(cc, G)] if G else []) + [(cc + G + t0, n)]
+            return (ops.region_crop_frames(latents.contiguous(), runs, plan), ops.region_crop_frames(weights, [(t0, n)], plan),
+                    (plan, latents[:, :, :cc], span), n)
         if (plan.h, plan.w) == (hl, wl):
-            return latents, weights, (plan, None)
-        return ops.region_crop(latents.contiguous(), plan), ops.region_crop(weights, plan), (plan, latents[:, :, :cc])
+            return latents, weights, (plan, None, None), cc
+        return ops.region_crop(latents.contiguous(), plan), ops.region_crop(weights, plan), (plan, latents[:, :, :cc], None), cc
 
     @staticmethod
     def _restore_region(latents, region):
-        """Edit region, the second stage: the loop's final state on the region put back into the source latents (wan_region_restore) --
-        outside the region the grounding and target frames are the source's bits."""
-        plan, source = region
+        """Edit region, the second stage: the loop's final state on the region put back into the source latents (wan_region_restore, or
+        wan_region_restore_frames after a time crop) -- outside the region the grounding and target frames are the source's bits."""
+        plan, source, span = region
         if source is None:
             return latents
         from . import ops
+        if span is not None:
+            return ops.region_restore_frames(source.to(latents.dtype), latents, (plan.y0, plan.x0), span)
         return ops.region_restore(source.to(latents.dtype), latents, (plan.y0, plan.x0))
 
     def _plan_windows(self, o, sizes, shape, cc, G, capture_graph):
@@ -806,10 +834,12 @@ class WanPipeline:
         self._stage("vae_encode", t_stage)
         # -- the mask and the windows; what one forward holds: the whole clip, or one window of `win_n` source frames and `win_hw` cells
         mask_weights = self._mask_weights(opt, latents, condition_count, ground_latent_count, source_frames, height, width)
-        latents, mask_weights, region = self._crop_to_region(opt, latents, mask_weights, window_sizes[1], condition_count, ground_latent_count)
-        plan, tiles = self._plan_windows(opt, window_sizes, latents.shape, condition_count, ground_latent_count, capture_graph)
+        # `loop_cc`: the source frames of the clip the loop runs on -- condition_count, or the frame range's after a time crop
+        latents, mask_weights, region, loop_cc = self._crop_to_region(opt, latents, mask_weights, window_sizes[1], condition_count,
+                                                                      ground_latent_count)
+        plan, tiles = self._plan_windows(opt, window_sizes, latents.shape, loop_cc, ground_latent_count, capture_graph)
         windowed = plan is not None or tiles is not None
-        win_n = condition_count if not windowed else tiles.t.window if tiles is not None else plan.window
+        win_n = loop_cc if not windowed else tiles.t.window if tiles is not None else plan.window
         win_hw = latents.shape[3] * latents.shape[4] if tiles is None else tiles.y.window * tiles.x.window
         win_frames = latents.shape[2] if not windowed else 2 * win_n + ground_latent_count
         seq_len = math.ceil(win_hw / math.prod(self.transformer.config.patch_size[1:]) * win_frames)     # :686-689
@@ -837,14 +867,14 @@ class WanPipeline:
                              (win_n, win_n + ground_latent_count) if use_rope_map and cot else None)
             if windowed:
                 latents, predict, target_frame0, cut = self._windowed_form(guided, latents, plan, tiles, opt.window_batch,
-                                                                           condition_count, ground_latent_count)
+                                                                           loop_cc, ground_latent_count)
             else:
-                predict, target_frame0, cut = self._whole_clip_form(guided, condition_count, ground_latent_count, zero_source)
+                predict, target_frame0, cut = self._whole_clip_form(guided, loop_cc, ground_latent_count, zero_source)
             callback = None if callback_on_step_end is None else (callback_on_step_end, callback_on_step_end_tensor_inputs, {
                 "prompt_embeds": prompt_embeds, "negative_prompt_embeds": negative_prompt_embeds})
             loop = lambda lat, embeds: cut(self._denoise(
                 lat, embeds, do_cfg, timesteps, predict, None if local_cfg is None else (local_cfg, opt.local_from),
-                None if mask_weights is None else (mask_weights, condition_count, target_frame0), extra_step_kwargs, callback))
+                None if mask_weights is None else (mask_weights, loop_cc, target_frame0), extra_step_kwargs, callback))
             if capture_graph == "loop":
                 key = (int(num_inference_steps), float(shift), bool(do_cfg), float(guidance_scale) if do_cfg else 0.0,
                        int(condition_count), int(ground_latent_count), bool(cot), bool(use_rope_map), int(seq_len))
@@ -861,4 +891,5 @@ class WanPipeline:
         self._stage("vae_decode", t_stage)
         return WanPipelineOutput(videos=videos, ground_videos=ground, edit_videos=edit, latents=latents, compare_videos=compared,
                                  edit_region=None if region is None else region[0].pixels(
-                                     getattr(getattr(self.vae, "config", None), "spatial_compression_ratio", 8)))
+                                     getattr(getattr(self.vae, "config", None), "spatial_compression_ratio", 8)),
+                                 edit_region_time=None if region is None or region[2] is None else region[2].pixels(ratio))
