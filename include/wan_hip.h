@@ -842,6 +842,40 @@ wan_status_t wan_frames_u8_to_video(const void* frames_u8, void* out, int out_dt
 wan_status_t wan_video_to_frames_u8(const void* video, int in_dtype, void* frames_u8, int B, int T, int H, int W,
                                     int t0, int nt, int T_out, int t_dst, void* stream);
 
+/* The same two conversions on a rectangle of the frame (`edit_region_vae_halo`): the VAE encodes and decodes the BOX
+ * only -- the edit region's rectangle widened by a halo -- and the frames that come back are the source's own bytes outside the
+ * region's rectangle.  videocof_amd/edit_region.py states each in plain torch / numpy (reference_frames_box_to_video,
+ * reference_video_box_stitch) and the kernels equal them bit for bit and byte for byte.
+ * replaces: nothing in the reference, which encodes and decodes whole frames.
+ * Common to both: the box is rows [by, by + bh), columns [bx, bx + bw) of the H x W frame, in pixels, any box inside the frame.  Streams
+ * of rows at a pitch as wan_region_crop's; the access unit is the largest of 16, 8, 4, 2 or 1 pixels that divides W, bx, bw and the byte
+ * tensors' base addresses and leaves the planes' words aligned, so no unit straddles the box's edge.  Everything is validated on the host
+ * before anything is enqueued; each enqueues ONE kernel on `stream` and never synchronises.
+ * wan_frames_u8_box_to_video (beside wan_frames_u8_to_video): frames uint8 [B, T, H, W, 3] -> out [B, 3, T, bh, bw] in out_dtype (0 fp32,
+ *     1 bf16), out[b, c, t, y, x] = cast(float32(frames[b, t, by + y, bx + x, c]) * float32(2.0 / 255.0) - 1.0f): that kernel's
+ *     arithmetic, and with the whole-frame box that kernel's bits.  A null tensor, a count below 1, another dtype, a box that does not
+ *     lie inside the frame, B * T or H * W * 3 of 2^31 or more -> WAN_ERR_INVALID.
+ * wan_video_box_stitch_u8 (beside wan_video_to_frames_u8 and wan_frames_u8_composite): video [B, 3, T, bh, bw] (the decoder's output on
+ *     the box; in_dtype 0 fp32, 1 bf16), frames [t0, t0 + nt), and source uint8 [Bs, Ts, H, W, 3] (Bs = 1 or B), frames [src_t0,
+ *     src_t0 + nt) -> frames uint8 [B, T_out, H, W, 3], frames [t_dst, t_dst + nt), every byte of them written exactly once.  With o the
+ *     source's byte, e the decoder's sample converted exactly as wan_video_to_frames_u8 converts it, (ry, rx, rh, rw) the region's
+ *     rectangle in frame pixels (inside the box) and f = feather:
+ *         outside the rectangle   out = o
+ *         inside it               d   = the least distance of the pixel to an edge of the rectangle that does NOT lie on the frame's
+ *                                       border (top: y - ry if ry > 0; bottom: ry + rh - 1 - y if ry + rh < H; left and right likewise;
+ *                                       no such edge: infinity)
+ *                                 a   = 255 if f == 0 or d >= f else (255 * (d + 1)) / (f + 1)                 (floor)
+ *                                 out = (a * e + (255 - a) * o + 127) / 255          (wan_frames_u8_composite's formula, floor, exact)
+ *     feather 0 is the literal stitch; a rectangle that is the whole frame gives wan_video_to_frames_u8's bytes.  The decoder's samples
+ *     outside the rectangle are never read.  `source_u8` and `frames_u8` must not overlap.  nt == 0 enqueues nothing.  A null tensor, a
+ *     count below 1, Bs not 1 or B, another dtype, a box not inside the frame, a rectangle not inside the box, a negative feather,
+ *     t0 + nt > T, src_t0 + nt > Ts, t_dst + nt > T_out, B * nt or H * W * 3 of 2^31 or more, a side above 2^24 -> WAN_ERR_INVALID. */
+wan_status_t wan_frames_u8_box_to_video(const void* frames_u8, void* out, int out_dtype, int B, int T, int H, int W, int by, int bx,
+                                        int bh, int bw, void* stream);
+wan_status_t wan_video_box_stitch_u8(const void* video, int in_dtype, const void* source_u8, void* frames_u8, int B, int Bs, int T,
+                                     int Ts, int T_out, int H, int W, int by, int bx, int bh, int bw, int ry, int rx, int rh, int rw,
+                                     int feather, int t0, int nt, int src_t0, int t_dst, void* stream);
+
 /* Fit a clip to another size: resample (antialiased triangle) and crop uint8 [B, T, H, W, 3] -> uint8 [B, T, Ho, Wo, 3] in one launch.
  * replaces: nothing in the reference's inference path, which hands the clip's own size to the pipeline (fast_infer.py:409-423), so its
  *           users resize per frame on the host; the geometry is the training loader's resize and centre crop

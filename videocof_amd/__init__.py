@@ -43,6 +43,7 @@ from .edit_region import (RegionPlan, region_plan, region_margin_cells, referenc
                           reference_region_restore)
 from .edit_region import (TimeRegion, region_time_plan, region_time_margin_frames, reference_region_crop_frames,  # noqa: F401
                           reference_region_restore_frames)
+from .edit_region import region_vae_box, reference_frames_box_to_video, reference_video_box_stitch  # noqa: F401
 from .local_attention import LocalAttentionPlan, local_attention_plan, reference_local_mask, reference_sparse_attention  # noqa: F401
 
 __version__ = "0.1.0"

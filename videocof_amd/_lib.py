@@ -260,6 +260,8 @@ SIGNATURES = {
     "wan_frames_u8_to_video": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "wan_video_to_frames_u8": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                        c_void_p]),
+    "wan_frames_u8_box_to_video": (c_int, [c_void_p, c_void_p] + [c_int] * 9 + [c_void_p]),
+    "wan_video_box_stitch_u8": (c_int, [c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 20 + [c_void_p]),
     "wan_frames_resample_table_bytes": (c_int64, [c_int, c_int]),
     "wan_frames_u8_resample": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int,
                                        c_void_p]),

@@ -7,6 +7,7 @@
 // registers with compile-time byte positions.  It needs H*W % 16 == 0 and 16-byte aligned bases; everything else (odd byte rows,
 // offset views) takes the element-wise kernels.
 #include <algorithm>
+#include <initializer_list>
 
 #include "common.hpp"
 
@@ -360,6 +361,172 @@ template <typename T> void launch_range_flag(const void* x, int64_t n, int* flag
     hipLaunchKernelGGL(range_flag_kernel<T>, dim3(blocks), dim3(256), 0, s, (const T*)x, n, nvec, flag);
 }
 
+// ---- the two conversions on a rectangle of the frame (`edit_region_vae_halo`): the VAE sees the box only
+//   in : the box [by, by + bh) x [bx, bx + bw) of uint8 [B, T, H, W, 3]  ->  [B, 3, T, bh, bw], byte_to_video's arithmetic
+//   out: [B, 3, T, bh, bw] and the uint8 source frames  ->  uint8 [B, T_out, H, W, 3]: the source's bytes, and inside the region's
+//        rectangle (which lies inside the box) the decoder's bytes (video_to_byte) blended over them
+// Streams of rows at a pitch, as the region kernels of edit_region.hip.  The access unit is N = 16, 8, 4, 2 or 1 PIXELS: the largest
+// that divides W, the box's x origin and width and the byte tensors' base addresses, and leaves the planes' words aligned
+// (box_unit_pixels below: the rule of tile_unit_bytes in window_kernels.hip, counted in pixels because an interleaved pixel is 3 bytes
+// and 3 is odd -- N pixels are three aligned N-byte words exactly where N divides the pixel index and the base).  So all x arithmetic
+// is in whole units and no unit straddles the box's edge.  A workgroup is `rp` rows of `cw` lanes each (cw = min(units per row, 256),
+// rp = 256 / cw; lanes beyond rp * cw idle): which frame and where the box lies are per workgroup (scalar); a lane adds its row and unit.
+template <int BYTES> struct RawOf;                        // BYTES of memory as one load / store
+template <> struct RawOf<16> { typedef u32x4 type; };
+template <> struct RawOf<8> { typedef u32x2 type; };
+template <> struct RawOf<4> { typedef unsigned int type; };
+template <> struct RawOf<2> { typedef unsigned short type; };
+template <> struct RawOf<1> { typedef unsigned char type; };
+
+template <int N> struct PixelUnit {                       // N interleaved pixels: three N-byte words
+    typedef typename RawOf<N>::type word_t;
+    struct Raw { word_t q[3]; };
+    struct Bytes { unsigned char v[3 * N]; };
+    __device__ static Bytes load(const uint8_t* p) {
+        const word_t* w = reinterpret_cast<const word_t*>(p);
+        const Raw r = {{w[0], w[1], w[2]}};
+        return __builtin_bit_cast(Bytes, r);
+    }
+    __device__ static void store(uint8_t* p, const Bytes& b) {
+        const Raw r = __builtin_bit_cast(Raw, b);
+        word_t* w = reinterpret_cast<word_t*>(p);
+        w[0] = r.q[0]; w[1] = r.q[1]; w[2] = r.q[2];
+    }
+};
+
+template <typename T, int N> struct PlaneUnit {           // N planar elements: the widest words their bytes allow, 16 at the most
+    static constexpr int BYTES = (int)sizeof(T) * N, WORD = BYTES < 16 ? BYTES : 16, WORDS = BYTES / WORD;
+    typedef typename RawOf<WORD>::type word_t;
+    struct Raw { word_t q[WORDS]; };
+    struct Vals { T v[N]; };
+    __device__ static Vals load(const T* p) {
+        const word_t* w = reinterpret_cast<const word_t*>(p);
+        Raw r;
+#pragma unroll
+        for (int i = 0; i < WORDS; ++i) r.q[i] = w[i];
+        return __builtin_bit_cast(Vals, r);
+    }
+    __device__ static void store(T* p, const Vals& v) {
+        const Raw r = __builtin_bit_cast(Raw, v);
+        word_t* w = reinterpret_cast<word_t*>(p);
+#pragma unroll
+        for (int i = 0; i < WORDS; ++i) w[i] = r.q[i];
+    }
+};
+
+// grid (b * T + t, row chunk); `bwu` = bw / N units per box row
+template <typename TOut, int N>
+__global__ __launch_bounds__(256) void frames_box_to_video_kernel(const uint8_t* __restrict__ frames, TOut* __restrict__ out, int T,
+                                                                  int H, int W, int by, int bx, int bh, int bwu, int cw, int rp) {
+    const unsigned bt = blockIdx.x;                       // < B * T (the grid)
+    const unsigned b = bt / (unsigned)T, t = bt - b * (unsigned)T;
+    const int lr = threadIdx.x / cw, lu = threadIdx.x % cw;
+    if (lr >= rp) return;
+    const uint8_t* src = frames + (((int64_t)bt * H + by) * W + bx) * 3;       // the box's first byte in this frame (inside it: the host)
+    const int64_t plane = (int64_t)bh * bwu * N;
+    TOut* dst = out + ((int64_t)b * 3 * T + t) * plane;   // channel c of this frame: + c * T * plane
+    for (int y = blockIdx.y * rp + lr; y < bh; y += gridDim.y * rp)
+        for (int u = lu; u < bwu; u += cw) {              // one pass unless a box row is longer than 256 units
+            const typename PixelUnit<N>::Bytes px = PixelUnit<N>::load(src + ((int64_t)y * W + u * N) * 3);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                typename PlaneUnit<TOut, N>::Vals o;
+#pragma unroll
+                for (int j = 0; j < N; ++j) o.v[j] = (TOut)byte_to_video(px.v[3 * j + c]);
+                PlaneUnit<TOut, N>::store(dst + c * T * plane + ((int64_t)y * bwu + u) * N, o);
+            }
+        }
+}
+
+struct stitch_args {
+    const void* video;                                    // [B, 3, T, bh, bw]
+    const uint8_t* source;                                // [Bs, Ts, H, W, 3]
+    uint8_t* frames;                                      // [B, T_out, H, W, 3]
+    int T, Ts, T_out, H, W, t0, nt, src_t0, t_dst;
+    int one_source;                                       // Bs == 1: every sample stitches against sample 0
+    int by, bx, bh, bw, ry, rx, rh, rw, feather;
+    int top, bottom, left, right;                         // 1: that edge of the rectangle does not lie on the frame's border, so it ramps
+    int wu, cw, rp;                                       // W / N units per frame row; the workgroup's shape
+};
+
+// grid (b * nt + t, row chunk).  Every byte of the frame is written once: the source's byte, or inside the rectangle
+// (a * e + (255 - a) * o + 127) / 255 with e the decoder's byte and a the ramp's weight (255 where no ramp reaches).
+template <typename TIn, int N>
+__global__ __launch_bounds__(256) void video_box_stitch_kernel(const stitch_args a) {
+    const unsigned row = blockIdx.x;                      // < B * nt (the grid)
+    const unsigned b = row / (unsigned)a.nt, t = row - b * (unsigned)a.nt;
+    const int lr = threadIdx.x / a.cw, lu = threadIdx.x % a.cw;
+    if (lr >= a.rp) return;
+    const int64_t frame_bytes = (int64_t)a.H * a.W * 3, plane = (int64_t)a.bh * a.bw;
+    const uint8_t* src = a.source + ((int64_t)(a.one_source ? 0u : b) * a.Ts + a.src_t0 + t) * frame_bytes;
+    uint8_t* dst = a.frames + ((int64_t)b * a.T_out + a.t_dst + t) * frame_bytes;
+    const TIn* vid = (const TIn*)a.video + ((int64_t)b * 3 * a.T + a.t0 + t) * plane;      // channel c of this frame: + c * T * plane
+    const int f = a.feather;
+    for (int y = blockIdx.y * a.rp + lr; y < a.H; y += gridDim.y * a.rp) {
+        const bool y_in = y >= a.ry && y < a.ry + a.rh;
+        int dy = 0x7fffffff;                              // the distance to the rectangle's ramping rows; none: "infinity"
+        if (a.top) dy = y - a.ry;
+        if (a.bottom) dy = min(dy, a.ry + a.rh - 1 - y);
+        for (int u = lu; u < a.wu; u += a.cw) {           // one pass unless a frame row is longer than 256 units
+            const int x0 = u * N;
+            const int64_t at = ((int64_t)y * a.W + x0) * 3;
+            typename PixelUnit<N>::Bytes px = PixelUnit<N>::load(src + at);
+            if (y_in && x0 + N > a.rx && x0 < a.rx + a.rw) {
+                // the unit meets the rectangle, so it lies inside the box: bx, bw and x0 are whole units
+                typename PlaneUnit<TIn, N>::Vals e[3];
+#pragma unroll
+                for (int c = 0; c < 3; ++c) e[c] = PlaneUnit<TIn, N>::load(vid + c * a.T * plane + (int64_t)(y - a.by) * a.bw + (x0 - a.bx));
+#pragma unroll
+                for (int j = 0; j < N; ++j) {
+                    const int x = x0 + j;
+                    unsigned int w = 0u;                  // outside the rectangle: weight 0 gives the source's byte
+                    if (x >= a.rx && x < a.rx + a.rw) {
+                        int d = dy;
+                        if (a.left) d = min(d, x - a.rx);
+                        if (a.right) d = min(d, a.rx + a.rw - 1 - x);
+                        w = (f == 0 || d >= f) ? 255u : 255u * (unsigned int)(d + 1) / (unsigned int)(f + 1);
+                    }
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) {
+                        const unsigned int ev = video_to_byte<TIn>((float)e[c].v[j]), ov = px.v[3 * j + c];
+                        px.v[3 * j + c] = (unsigned char)((w * ev + (255u - w) * ov + 127u) / 255u);
+                    }
+                }
+            }
+            PixelUnit<N>::store(dst + at, px);
+        }
+    }
+}
+
+// the largest of 16, 8, 4, 2 or 1 pixels that divides every length in `lens` (pixels) and the byte tensors' addresses, and whose
+// planar elements (of `es` bytes, at `plane_address`) are aligned words of min(16, N * es) bytes
+int box_unit_pixels(int64_t es, std::initializer_list<int64_t> lens, uintptr_t byte_addresses, uintptr_t plane_address) {
+    uint64_t m = (uint64_t)byte_addresses;
+    for (int64_t l : lens) m |= (uint64_t)l;
+    int N = 16;
+    while (N > 1 && ((m & (uint64_t)(N - 1)) != 0 || (plane_address & (uintptr_t)(std::min<int64_t>(16, N * es) - 1)) != 0)) N /= 2;
+    return N;
+}
+
+// workgroups along the rows: <= ~4096 in all, at most what the grid's second axis holds; the rest is a grid-stride loop
+unsigned box_row_chunks(int rows, int per_group, int64_t frames) {
+    const int64_t need = ((int64_t)rows + per_group - 1) / per_group;
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(need, 65535), 4096 / frames));
+}
+
+bool rect_inside(int H, int W, int y0, int x0, int h, int w) {
+    return y0 >= 0 && x0 >= 0 && h >= 1 && w >= 1 && (int64_t)y0 + h <= H && (int64_t)x0 + w <= W;
+}
+
+#define WAN_BY_PIXELS(N, LAUNCH)                                         \
+    do {                                                                 \
+        if ((N) == 16) LAUNCH(16);                                       \
+        else if ((N) == 8) LAUNCH(8);                                    \
+        else if ((N) == 4) LAUNCH(4);                                    \
+        else if ((N) == 2) LAUNCH(2);                                    \
+        else LAUNCH(1);                                                  \
+    } while (0)
+
 // grid: x over the items (16-pixel chunks or pixels) of one frame, y = frames
 dim3 grid_for(int64_t items_per_frame, int64_t frames) {
     return dim3((unsigned)std::min<int64_t>((items_per_frame + 255) / 256, 4096), (unsigned)frames);
@@ -482,5 +649,82 @@ extern "C" wan_status_t wan_frames_u8_compose(const wan_compose_src* srcs, int n
     const dim3 grid((unsigned)((items + 255) / 256), (unsigned)T_out);
     hipLaunchKernelGGL(frames_compose_kernel, grid, dim3(256), 0, (hipStream_t)stream, a);
     WAN_CHECK_LAUNCH("wan_frames_u8_compose");
+    return WAN_OK;
+}
+
+extern "C" wan_status_t wan_frames_u8_box_to_video(const void* frames_u8, void* out, int out_dtype, int B, int T, int H, int W, int by,
+                                                   int bx, int bh, int bw, void* stream) {
+    WAN_REQUIRE(B > 0 && T > 0 && H > 0 && W > 0, WAN_ERR_INVALID, "wan_frames_u8_box_to_video: bad shape B=%d T=%d H=%d W=%d", B, T, H, W);
+    WAN_REQUIRE(out_dtype == 0 || out_dtype == 1, WAN_ERR_INVALID, "wan_frames_u8_box_to_video: out_dtype=%d (0 fp32, 1 bf16)", out_dtype);
+    WAN_REQUIRE(rect_inside(H, W, by, bx, bh, bw), WAN_ERR_INVALID,
+                "wan_frames_u8_box_to_video: the box [%d, %d + %d) x [%d, %d + %d) does not lie inside a frame of %d x %d", by, by, bh, bx,
+                bx, bw, H, W);
+    // (the box first: an empty box's output is an empty tensor, whose address is null)
+    WAN_REQUIRE(frames_u8 && out, WAN_ERR_INVALID, "wan_frames_u8_box_to_video: null tensor");
+    const int64_t frames = (int64_t)B * T;
+    WAN_REQUIRE(frames <= 0x7fffffff && (int64_t)H * W * 3 <= 0x7fffffff, WAN_ERR_INVALID,
+                "wan_frames_u8_box_to_video: %lld frames of %lld bytes (each at most 2^31 - 1)", (long long)frames, (long long)H * W * 3);
+    const int64_t es = out_dtype == 0 ? 4 : 2;
+    const int N = box_unit_pixels(es, {W, bx, bw}, (uintptr_t)frames_u8, (uintptr_t)out);
+    const int bwu = bw / N, cw = std::min(bwu, 256), rp = 256 / cw;
+    const dim3 grid((unsigned)frames, box_row_chunks(bh, rp, frames));
+    hipStream_t s = (hipStream_t)stream;
+#define WAN_BOX_IN(N_)                                                                                                          \
+    do {                                                                                                                        \
+        if (out_dtype == 0)                                                                                                     \
+            hipLaunchKernelGGL((frames_box_to_video_kernel<float, N_>), grid, dim3(256), 0, s, (const uint8_t*)frames_u8,       \
+                               (float*)out, T, H, W, by, bx, bh, bwu, cw, rp);                                                  \
+        else                                                                                                                    \
+            hipLaunchKernelGGL((frames_box_to_video_kernel<bf16_t, N_>), grid, dim3(256), 0, s, (const uint8_t*)frames_u8,      \
+                               (bf16_t*)out, T, H, W, by, bx, bh, bwu, cw, rp);                                                 \
+    } while (0)
+    WAN_BY_PIXELS(N, WAN_BOX_IN);
+#undef WAN_BOX_IN
+    WAN_CHECK_LAUNCH("wan_frames_u8_box_to_video");
+    return WAN_OK;
+}
+
+extern "C" wan_status_t wan_video_box_stitch_u8(const void* video, int in_dtype, const void* source_u8, void* frames_u8, int B, int Bs,
+                                                int T, int Ts, int T_out, int H, int W, int by, int bx, int bh, int bw, int ry, int rx,
+                                                int rh, int rw, int feather, int t0, int nt, int src_t0, int t_dst, void* stream) {
+    const char* who = "wan_video_box_stitch_u8";
+    WAN_REQUIRE(B > 0 && T > 0 && Ts > 0 && T_out > 0 && H > 0 && W > 0, WAN_ERR_INVALID,
+                "%s: bad shape B=%d T=%d Ts=%d T_out=%d H=%d W=%d", who, B, T, Ts, T_out, H, W);
+    WAN_REQUIRE(Bs == 1 || Bs == B, WAN_ERR_INVALID, "%s: Bs=%d source clips for B=%d samples (1 or B)", who, Bs, B);
+    WAN_REQUIRE(in_dtype == 0 || in_dtype == 1, WAN_ERR_INVALID, "%s: in_dtype=%d (0 fp32, 1 bf16)", who, in_dtype);
+    WAN_REQUIRE(rect_inside(H, W, by, bx, bh, bw), WAN_ERR_INVALID,
+                "%s: the box [%d, %d + %d) x [%d, %d + %d) does not lie inside a frame of %d x %d", who, by, by, bh, bx, bx, bw, H, W);
+    WAN_REQUIRE(rect_inside(bh, bw, ry - by, rx - bx, rh, rw), WAN_ERR_INVALID,
+                "%s: the rectangle [%d, %d + %d) x [%d, %d + %d) does not lie inside the box [%d, %d + %d) x [%d, %d + %d)", who, ry, ry, rh,
+                rx, rx, rw, by, by, bh, bx, bx, bw);
+    WAN_REQUIRE(video && source_u8 && frames_u8, WAN_ERR_INVALID, "%s: null tensor", who);
+    WAN_REQUIRE(feather >= 0, WAN_ERR_INVALID, "%s: feather=%d pixels (not negative)", who, feather);
+    WAN_REQUIRE(t0 >= 0 && nt >= 0 && nt <= T - t0, WAN_ERR_INVALID, "%s: decoder frames [%d, %d + %d) of %d", who, t0, t0, nt, T);
+    WAN_REQUIRE(src_t0 >= 0 && nt <= Ts - src_t0, WAN_ERR_INVALID, "%s: source frames [%d, %d + %d) of %d", who, src_t0, src_t0, nt, Ts);
+    WAN_REQUIRE(t_dst >= 0 && nt <= T_out - t_dst, WAN_ERR_INVALID, "%s: %d frames at offset %d of a %d-frame clip", who, nt, t_dst, T_out);
+    // (the ramp's 255 * (d + 1) stays below 2^32 with d < 2^24)
+    WAN_REQUIRE((int64_t)B * nt <= 0x7fffffff && (int64_t)H * W * 3 <= 0x7fffffff && H <= (1 << 24) && W <= (1 << 24), WAN_ERR_INVALID,
+                "%s: %lld frames of %d x %d pixels (frames and bytes a frame at most 2^31 - 1, a side at most 2^24)", who,
+                (long long)B * nt, H, W);
+    if (nt == 0) return WAN_OK;
+    const int64_t es = in_dtype == 0 ? 4 : 2, frames = (int64_t)B * nt;
+    const int N = box_unit_pixels(es, {W, bx, bw}, (uintptr_t)source_u8 | (uintptr_t)frames_u8, (uintptr_t)video);
+    stitch_args a;
+    a.video = video; a.source = (const uint8_t*)source_u8; a.frames = (uint8_t*)frames_u8;
+    a.T = T; a.Ts = Ts; a.T_out = T_out; a.H = H; a.W = W; a.t0 = t0; a.nt = nt; a.src_t0 = src_t0; a.t_dst = t_dst;
+    a.one_source = Bs == 1;
+    a.by = by; a.bx = bx; a.bh = bh; a.bw = bw; a.ry = ry; a.rx = rx; a.rh = rh; a.rw = rw; a.feather = feather;
+    a.top = ry > 0; a.bottom = ry + rh < H; a.left = rx > 0; a.right = rx + rw < W;
+    a.wu = W / N; a.cw = std::min(a.wu, 256); a.rp = 256 / a.cw;
+    const dim3 grid((unsigned)frames, box_row_chunks(H, a.rp, frames));
+    hipStream_t s = (hipStream_t)stream;
+#define WAN_BOX_OUT(N_)                                                                                          \
+    do {                                                                                                         \
+        if (in_dtype == 0) hipLaunchKernelGGL((video_box_stitch_kernel<float, N_>), grid, dim3(256), 0, s, a);   \
+        else hipLaunchKernelGGL((video_box_stitch_kernel<bf16_t, N_>), grid, dim3(256), 0, s, a);                \
+    } while (0)
+    WAN_BY_PIXELS(N, WAN_BOX_OUT);
+#undef WAN_BOX_OUT
+    WAN_CHECK_LAUNCH(who);
     return WAN_OK;
 }

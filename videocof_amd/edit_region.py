@@ -12,6 +12,11 @@ latent frames around the frames the mask touches, and ``reference_region_crop_fr
 ``wan_region_crop_frames`` / ``wan_region_restore_frames`` compute.  The model then sees a clip whose first latent frame is not the
 clip's first (the causal VAE's special frame) -- as every temporal context window but the first does already: the same
 class of approximation, opt-in, lossy, no quality claim.
+
+With ``edit_region_vae_halo`` the VAE, too, sees only a part of the frame: ``region_vae_box`` fixes the BOX it encodes and decodes (the
+region's rectangle and a halo), ``reference_frames_box_to_video`` / ``reference_video_box_stitch`` state what
+``wan_frames_u8_box_to_video`` / ``wan_video_box_stitch_u8`` compute on either side of it (ops.frames_u8_box_to_video,
+ops.video_box_stitch_u8), bit for bit and byte for byte: the frames that come back are the source's own bytes outside the rectangle.
 """
 from __future__ import annotations
 
@@ -22,7 +27,8 @@ import torch
 
 __all__ = ["RegionPlan", "region_plan", "region_margin_cells", "reference_mask_bounds", "reference_region_crop",
            "reference_region_restore", "TimeRegion", "region_time_plan", "region_time_margin_frames", "reference_region_crop_frames",
-           "reference_region_restore_frames"]
+           "reference_region_restore_frames", "region_vae_box", "region_vae_halo_cells", "region_stitch_feather",
+           "reference_frames_box_to_video", "reference_video_box_stitch", "stitch_weights"]
 
 REGION_MARGIN_UNIT = 16         # pixels: the VAE's spatial ratio 8 times the patch 2 -- a margin keeps the region on the patch grid
 
@@ -159,6 +165,49 @@ def region_time_margin_frames(margin, ratio: int = 4) -> int:
     return int(margin) // ratio
 
 
+def region_vae_box(region, frame_cells, halo_cells) -> RegionPlan:
+    """The box the VAE encodes and decodes with ``edit_region_vae_halo``, in LATENT cells: the region's rectangle widened by
+    ``halo_cells`` = (rows, columns) on every side and clamped to the frame ``frame_cells`` = (H, W).  Per axis
+
+        b0 = max(0, start - hc),  b1 = min(F, start + size + hc)
+
+    The box lies inside the frame and contains the region.  The pipeline's halo is a multiple of 16 pixels, so hc is a multiple of the
+    patch 2 and the box lies on the frame's patch grid wherever the region does; planning the region inside the box
+    (``region_plan`` on the bounds less the box's origin, with ``frame_cells`` = the box) then gives the same region less the box's
+    origin.  (Not claimed where the frame is no multiple of the patch, 135 rows for 1080 pixels: the option works there too, the VAE
+    needs multiples of 8 pixels only.)  No finite halo is exact: the VAE's receptive field is many 3 x 3 convolutions deep and its
+    mid-block attention is global over the frame it sees, so every value is a guess."""
+    if len(region) != 4:
+        raise ValueError(f"region_vae_box: region = (y0, x0, h, w) in cells, got {region!r}")
+    for name, v in (("frame_cells", frame_cells), ("halo_cells", halo_cells)):
+        if isinstance(v, (str, bytes)) or not hasattr(v, "__len__") or len(v) != 2 or any(
+                isinstance(e, bool) or not isinstance(e, (int, np.integer)) or e < (1 if name == "frame_cells" else 0) for e in v):
+            raise ValueError(f"region_vae_box: {name}={v!r} is not a pair (rows, columns) of latent cell counts")
+    y0, x0, h, w = _box(region, int(frame_cells[0]), int(frame_cells[1]), "region_vae_box")
+    (H, W), (hy, hx) = (int(v) for v in frame_cells), (int(v) for v in halo_cells)
+    by0, by1 = max(0, y0 - hy), min(H, y0 + h + hy)
+    bx0, bx1 = max(0, x0 - hx), min(W, x0 + w + hx)
+    return RegionPlan(by0, bx0, by1 - by0, bx1 - bx0)
+
+
+def region_vae_halo_cells(halo, ratio: int = 8) -> int:
+    """The pipeline's ``edit_region_vae_halo`` in PIXELS as latent cells: a non-negative multiple of 16 pixels (the VAE's spatial ratio
+    8 times the patch 2), which keeps the box on the patch grid."""
+    if isinstance(halo, bool) or not isinstance(halo, (int, np.integer)):
+        raise ValueError(f"edit_region_vae_halo={halo!r} is not an integer pixel count")
+    if halo < 0 or halo % REGION_MARGIN_UNIT:
+        raise ValueError(f"edit_region_vae_halo={halo} must be a non-negative multiple of {REGION_MARGIN_UNIT} pixels (the VAE's spatial "
+                         "ratio 8 times the patch 2)")
+    return int(halo) // ratio
+
+
+def region_stitch_feather(feather) -> int:
+    """The pipeline's ``edit_region_stitch_feather``: a non-negative integer count of pixels."""
+    if isinstance(feather, bool) or not isinstance(feather, (int, np.integer)) or feather < 0:
+        raise ValueError(f"edit_region_stitch_feather={feather!r} is not a non-negative integer pixel count")
+    return int(feather)
+
+
 # ------------------------------------------------------------------------------------------------ the device passes, in torch
 def reference_mask_bounds(weights: torch.Tensor) -> torch.Tensor:
     """``wan_mask_bounds`` in torch: weights uint8 [Bm, Fs, h, w] -> int32 [Fs, 4] = (y_lo, y_hi, x_lo, x_hi) per latent frame, the
@@ -255,3 +304,80 @@ def reference_region_restore_frames(source: torch.Tensor, state: torch.Tensor, o
     out[:, :, cc:cc + G, y0:y0 + hr, x0:x0 + wr] = state[:, :, n:n + G]
     out[:, :, cc + G + t0:cc + G + t0 + n, y0:y0 + hr, x0:x0 + wr] = state[:, :, n + G:]
     return out
+
+
+def _pixel_rect(rect, H: int, W: int, who: str, what: str, of: str) -> Tuple[int, int, int, int]:
+    if len(rect) != 4:
+        raise ValueError(f"{who}: {what} = (y, x, h, w) in pixels, got {rect!r}")
+    y, x, h, w = (int(v) for v in rect)
+    if y < 0 or x < 0 or h < 1 or w < 1 or y + h > H or x + w > W:
+        raise ValueError(f"{who}: the {what} [{y}, {y} + {h}) x [{x}, {x} + {w}) does not lie inside {of} of {H} x {W}")
+    return y, x, h, w
+
+
+def reference_frames_box_to_video(frames_u8: torch.Tensor, box, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """``wan_frames_u8_box_to_video`` in torch: the box ``box`` = (y, x, h, w) in pixels of uint8 ``frames_u8`` [B, T, H, W, 3] ->
+    [B, 3, T, h, w] in ``dtype``: ``video_io.reference_frames_to_video``'s arithmetic (float32 ``x * (2.0 / 255.0) - 1.0``, two
+    operations rounded one after the other, then the cast) on the cropped frames."""
+    if frames_u8.dim() != 5 or frames_u8.shape[-1] != 3 or frames_u8.dtype != torch.uint8:
+        raise ValueError(f"reference_frames_box_to_video: expected uint8 [B, T, H, W, 3], got {frames_u8.dtype} {tuple(frames_u8.shape)}")
+    y, x, h, w = _pixel_rect(box, frames_u8.shape[2], frames_u8.shape[3], "reference_frames_box_to_video", "box", "a frame")
+    v = frames_u8[:, :, y:y + h, x:x + w].permute(0, 4, 1, 2, 3).float()
+    v = v * (2.0 / 255.0) - 1.0
+    return v.to(dtype).contiguous()
+
+
+def stitch_weights(frame, rect, feather: int) -> np.ndarray:
+    """The ramp of ``reference_video_box_stitch``: int64 [h, w] weights a over the rectangle ``rect`` = (y, x, h, w) of a frame
+    ``frame`` = (H, W).  d = the least distance of the pixel to an edge of the rectangle that does not lie on the frame's border (none:
+    infinity); a = 255 if feather == 0 or d >= feather else (255 * (d + 1)) // (feather + 1)."""
+    (H, W), f = (int(v) for v in frame), int(feather)
+    ry, rx, rh, rw = _pixel_rect(rect, H, W, "stitch_weights", "rectangle", "a frame")
+    if f < 0:
+        raise ValueError(f"stitch_weights: feather={feather} pixels (not negative)")
+    far = np.iinfo(np.int64).max
+    ys, xs = np.arange(rh, dtype=np.int64), np.arange(rw, dtype=np.int64)
+    dy, dx = np.full(rh, far), np.full(rw, far)
+    if ry > 0:
+        dy = np.minimum(dy, ys)
+    if ry + rh < H:
+        dy = np.minimum(dy, rh - 1 - ys)
+    if rx > 0:
+        dx = np.minimum(dx, xs)
+    if rx + rw < W:
+        dx = np.minimum(dx, rw - 1 - xs)
+    d = np.minimum(dy[:, None], dx[None, :])
+    if f == 0:
+        return np.full((rh, rw), 255, np.int64)
+    return np.where(d >= f, 255, (255 * (np.minimum(d, f) + 1)) // (f + 1))
+
+
+def reference_video_box_stitch(source_u8: torch.Tensor, edit_u8: torch.Tensor, box, rect, feather: int = 0) -> torch.Tensor:
+    """``wan_video_box_stitch_u8`` in numpy int64 on the host: ``source_u8`` uint8 [Bs, T, H, W, 3] (Bs = 1 or B), ``edit_u8`` uint8
+    [B, T, bh, bw, 3] = the decoder's frames on the box ``box`` = (y, x, bh, bw) as bytes (``video_io.reference_video_to_frames`` of
+    the decoder's output; frame t stitches against source frame t) -> uint8 [B, T, H, W, 3].  With ``rect`` = (y, x, h, w) the region's
+    rectangle in frame pixels, inside the box, o the source's byte, e the edit's and a = ``stitch_weights``:
+
+        outside the rectangle   out = o
+        inside it               out = (a * e + (255 - a) * o + 127) // 255
+
+    ``feather`` 0 is the literal stitch; edges of the rectangle on the frame's border do not ramp."""
+    if source_u8.dim() != 5 or edit_u8.dim() != 5 or source_u8.dtype != torch.uint8 or edit_u8.dtype != torch.uint8 \
+            or source_u8.shape[-1] != 3 or edit_u8.shape[-1] != 3 or source_u8.shape[0] not in (1, edit_u8.shape[0]) \
+            or source_u8.shape[1] != edit_u8.shape[1]:
+        raise ValueError(f"reference_video_box_stitch: source {source_u8.dtype} {tuple(source_u8.shape)} and edit {edit_u8.dtype} "
+                         f"{tuple(edit_u8.shape)}: expected uint8 [1 or B, T, H, W, 3] and [B, T, bh, bw, 3]")
+    H, W = int(source_u8.shape[2]), int(source_u8.shape[3])
+    by, bx, bh, bw = _pixel_rect(box, H, W, "reference_video_box_stitch", "box", "a frame")
+    if tuple(edit_u8.shape[2:4]) != (bh, bw):
+        raise ValueError(f"reference_video_box_stitch: a box of {bh} x {bw} pixels for edit frames of {tuple(edit_u8.shape[2:4])}")
+    ry, rx, rh, rw = _pixel_rect(rect, H, W, "reference_video_box_stitch", "rectangle", "a frame")
+    if ry < by or rx < bx or ry + rh > by + bh or rx + rw > bx + bw:
+        raise ValueError(f"reference_video_box_stitch: the rectangle {tuple(rect)} does not lie inside the box {tuple(box)}")
+    a = stitch_weights((H, W), (ry, rx, rh, rw), feather)[None, None, :, :, None]
+    out = source_u8.cpu().numpy().astype(np.int64)
+    out = np.broadcast_to(out, (edit_u8.shape[0],) + out.shape[1:]).copy()
+    e = edit_u8.cpu().numpy().astype(np.int64)[:, :, ry - by:ry - by + rh, rx - bx:rx - bx + rw]
+    o = out[:, :, ry:ry + rh, rx:rx + rw]
+    out[:, :, ry:ry + rh, rx:rx + rw] = (a * e + (255 - a) * o + 127) // 255
+    return torch.from_numpy(out.astype(np.uint8))

@@ -1093,6 +1093,84 @@ def video_to_frames_u8(video: torch.Tensor, out: Optional[torch.Tensor] = None, 
     return out
 
 
+def _pixel_box(box, name: str, what: str = "box"):
+    if not hasattr(box, "__len__") or len(box) != 4:
+        raise ValueError(f"{name}: {what} = (y, x, h, w) in pixels, got {box!r}")
+    return tuple(int(v) for v in box)
+
+
+@_on_tensor_device
+def frames_u8_box_to_video(frames: torch.Tensor, box, out_dtype: torch.dtype = torch.bfloat16, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The box ``box`` = (y, x, h, w) in pixels of uint8 [B,T,H,W,3] frames -> [B,3,T,h,w] in out_dtype (fp32|bf16) in ONE launch
+    (``wan_frames_u8_box_to_video``): ``frames_u8_to_video``'s arithmetic on the box only, and with the whole-frame box its bits.
+    Any box inside the frame; ``out``: a contiguous tensor of that shape and dtype to write into."""
+    _need(frames, torch.uint8, "frames_u8_box_to_video.frames")
+    if frames.dim() != 5 or frames.shape[-1] != 3:
+        raise ValueError(f"frames_u8_box_to_video.frames: expected [B, T, H, W, 3], got {tuple(frames.shape)}")
+    if out_dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"frames_u8_box_to_video: dtype {out_dtype} not supported (float32 or bfloat16)")
+    by, bx, bh, bw = _pixel_box(box, "frames_u8_box_to_video")
+    frames = frames.contiguous()
+    B, T, H, W, _ = (int(v) for v in frames.shape)
+    shape = (B, 3, T, max(bh, 0), max(bw, 0))
+    if out is None:
+        out = torch.empty(shape, device=frames.device, dtype=out_dtype)
+    elif tuple(out.shape) != shape or out.dtype != out_dtype or not out.is_contiguous() or out.device != frames.device:
+        raise ValueError(f"frames_u8_box_to_video.out: {out.dtype} {tuple(out.shape)} on {out.device} for contiguous {out_dtype} "
+                         f"{shape} on {frames.device}")
+    _lib.check(_lib.load().wan_frames_u8_box_to_video(_p(frames), _p(out), 0 if out_dtype == torch.float32 else 1, B, T, H, W, by, bx,
+                                                      bh, bw, _stream()), "wan_frames_u8_box_to_video")
+    return out
+
+
+@_on_tensor_device
+def video_box_stitch_u8(video: torch.Tensor, source: torch.Tensor, box, rect, feather: int = 0, out: Optional[torch.Tensor] = None,
+                        frame_range: Optional[Tuple[int, int]] = None, dst_frame: int = 0, src_frame: int = 0) -> torch.Tensor:
+    """The decoder's output on the box, ``video`` [B,3,T,bh,bw] (fp32|bf16), stitched into the uint8 ``source`` frames [Bs,Ts,H,W,3]
+    (Bs = 1 or B) in ONE launch (``wan_video_box_stitch_u8``): uint8 [B,T_out,H,W,3] frames that are the source's bytes outside the
+    rectangle ``rect`` = (y, x, h, w) (frame pixels, inside ``box`` = (y, x, bh, bw)) and inside it the decoder's bytes
+    (``video_to_frames_u8``'s conversion), blended over the source along a linear ramp of ``feather`` pixels on the inside of every
+    edge of the rectangle that is not the frame's border (edit_region.reference_video_box_stitch is the definition; 0 = the literal
+    stitch).  ``frame_range`` = (first, end) picks frames of ``video``; they stitch against the source frames from ``src_frame`` on and
+    land in ``out`` (a contiguous uint8 [B,T_out,H,W,3] device clip, not overlapping ``source``; returned as given) from frame
+    ``dst_frame`` on; without ``out`` a clip of exactly the chosen frames is allocated."""
+    if video.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"video_box_stitch_u8.video: expected float32 or bfloat16, got {video.dtype}")
+    _need(video, video.dtype, "video_box_stitch_u8.video")
+    _need(source, torch.uint8, "video_box_stitch_u8.source")
+    if video.dim() != 5 or video.shape[1] != 3:
+        raise ValueError(f"video_box_stitch_u8.video: expected [B, 3, T, bh, bw], got {tuple(video.shape)}")
+    if source.dim() != 5 or source.shape[-1] != 3 or source.device != video.device:
+        raise ValueError(f"video_box_stitch_u8.source: expected uint8 [Bs, Ts, H, W, 3] on {video.device}, got {tuple(source.shape)} "
+                         f"on {source.device}")
+    video, source = video.contiguous(), source.contiguous()
+    B, _, T, vh, vw = (int(v) for v in video.shape)
+    Bs, Ts, H, W, _ = (int(v) for v in source.shape)
+    by, bx, bh, bw = _pixel_box(box, "video_box_stitch_u8")
+    ry, rx, rh, rw = _pixel_box(rect, "video_box_stitch_u8", "rect")
+    if (bh, bw) != (vh, vw):
+        raise ValueError(f"video_box_stitch_u8: a box of {bh} x {bw} pixels for decoder frames of {vh} x {vw}")
+    if isinstance(feather, bool) or not isinstance(feather, (int, np.integer)):
+        raise ValueError(f"video_box_stitch_u8: feather={feather!r} is not an integer pixel count")
+    t0, t1 = (0, T) if frame_range is None else (int(frame_range[0]), int(frame_range[1]))
+    if not 0 <= t0 <= t1 <= T:
+        raise ValueError(f"video_box_stitch_u8: frame_range {(t0, t1)} of {T} frames")
+    if out is None:
+        if dst_frame != 0:
+            raise ValueError("video_box_stitch_u8: dst_frame needs `out`")
+        out = torch.empty(B, t1 - t0, H, W, 3, device=video.device, dtype=torch.uint8)
+    else:
+        _need(out, torch.uint8, "video_box_stitch_u8.out")
+        if out.dim() != 5 or not out.is_contiguous() or out.device != video.device or \
+                (out.shape[0], out.shape[2], out.shape[3], out.shape[4]) != (B, H, W, 3):
+            raise ValueError(f"video_box_stitch_u8.out: expected a contiguous [{B}, T_out, {H}, {W}, 3] on {video.device}, got "
+                             f"{tuple(out.shape)} on {out.device}")
+    _lib.check(_lib.load().wan_video_box_stitch_u8(_p(video), 0 if video.dtype == torch.float32 else 1, _p(source), _p(out), B, Bs, T, Ts,
+                                                   int(out.shape[1]), H, W, by, bx, bh, bw, ry, rx, rh, rw, int(feather), t0, t1 - t0,
+                                                   int(src_frame), int(dst_frame), _stream()), "wan_video_box_stitch_u8")
+    return out
+
+
 @_on_tensor_device
 def frames_u8_resample(frames: torch.Tensor, out_height: int, out_width: int, xtab: torch.Tensor, kx: int, ytab: torch.Tensor,
                        ky: int) -> torch.Tensor:

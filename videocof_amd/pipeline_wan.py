@@ -46,6 +46,7 @@ class WanPipelineOutput:
     compare_videos: Optional[Union[torch.Tensor, np.ndarray]] = None   # extension: source | edit side by side (compare=True)
     edit_region: Optional[tuple] = None             # extension: (y, x, h, w) in pixels, what the loop ran on (edit_region=True); None when off
     edit_region_time: Optional[tuple] = None        # extension: (first pixel frame, pixel frame count) of it (edit_region_time_margin); None when off
+    edit_region_vae: Optional[tuple] = None         # extension: (y, x, h, w) in pixels, the box the VAE ran on (edit_region_vae_halo); None when off
 
 
 def _require_source(has_source: bool, why: str) -> None:
@@ -293,14 +294,20 @@ class WanPipeline:
     def attention_kwargs(self):
         return getattr(self, "_attention_kwargs", None)
 
-    def _decode_frames_u8(self, latents, out, clip=None, dst_frame=0, keep=None) -> np.ndarray:
+    def _decode_frames_u8(self, latents, out, clip=None, dst_frame=0, keep=None, stitch=None) -> np.ndarray:
         """decode, then wan_video_to_frames_u8 into frames [dst_frame, dst_frame + T) of the device clip `clip` (uint8
         [B, T_clip, H, W, 3]; None = one of exactly T frames), then ONE asynchronous copy per sample of that frame range -- one
         contiguous run of bytes -- into `out`, a page-locked uint8 [B, T, H, W, 3] host tensor (or a frame slice of one).
-        `keep`: a list that receives the device frames of the segment (the compare clip is composed from them)."""
+        `keep`: a list that receives the device frames of the segment (the compare clip is composed from them).
+        `stitch` (`edit_region_vae_halo`): (the device source frames, the box, the region's rectangle, the feather) -- the latents are
+        the box's, and wan_video_box_stitch_u8 writes the whole frames instead: the source's bytes from frame 0 on, the decoder's inside
+        the rectangle."""
         from . import ops
         frames = self.vae.decode(latents.to(self.vae.dtype)).sample
-        clip = ops.video_to_frames_u8(frames, out=clip, dst_frame=dst_frame)
+        if stitch is None:
+            clip = ops.video_to_frames_u8(frames, out=clip, dst_frame=dst_frame)
+        else:
+            clip = ops.video_box_stitch_u8(frames, stitch[0], stitch[1], stitch[2], stitch[3], out=clip, dst_frame=dst_frame)
         seg = clip[:, dst_frame:dst_frame + frames.shape[2]]
         if keep is not None:
             keep.append(seg)
@@ -343,7 +350,7 @@ class WanPipeline:
         return out.numpy()
 
     # -------------------------------------------------------------- __call__ (:516-799): its stages, in the order it runs them
-    def _parse_switches(self, switches, video, has_source, source_frames, height, width, output_type, capture_graph):
+    def _parse_switches(self, switches, video, has_source, source_frames, height, width, output_type, capture_graph, has_latents=False):
         """The keywords of ``__call__`` that travel in `switches` (as `as_uint8` is decode_latents': the named parameters stay the
         reference's plus the extensions tests/test_oracle_vs_reference.py lists), and every check of them that needs no device."""
         o = SimpleNamespace(
@@ -385,7 +392,18 @@ class WanPipeline:
             # whole-clip.  None: the time axis is not cropped.  There is no default margin: any value is a guess.  Opt-in and lossy, the
             # class of approximation of temporal context windows; no quality claim.
             edit_region_time_margin=switches.pop("edit_region_time_margin", None),
-            region_time_margin=None)                     # set below: the margin in latent frames, checked (None: no time crop)
+            region_time_margin=None,                     # set below: the margin in latent frames, checked (None: no time crop)
+            # `edit_region_vae_halo=None, edit_region_stitch_feather=0` (PIXELS; the halo a multiple of 16): with `edit_region=True`, the
+            # VAE encodes and decodes only the BOX -- the region's rectangle widened by the halo on every side, clamped to the frame
+            # (edit_region.region_vae_box) -- and the returned frames are the source's own bytes outside the region's rectangle
+            # (wan_frames_u8_box_to_video before the encoder, wan_video_box_stitch_u8 after the decoder).  Needs uint8 frames as `video`
+            # and output_type="uint8"; `latents` in the output are then the box's.  The time axis is never cropped in the VAE.  The
+            # feather is the width of a linear ramp on the inside of the rectangle's edges that are not the frame's border; 0 is the
+            # literal stitch.  None: the VAE runs on whole frames.  The halo has no default: the VAE's receptive field is many 3 x 3
+            # convolutions deep and its mid-block attention is global over the frame it sees, so no finite halo is exact and every
+            # value is a guess.  Opt-in and lossy (a VAE that sees a crop is as lossy as a DiT that sees one); no quality claim.
+            edit_region_vae_halo=switches.pop("edit_region_vae_halo", None), edit_region_stitch_feather=switches.pop("edit_region_stitch_feather", 0),
+            vae_halo=None, stitch_feather=0)             # set below: the halo in latent cells (None: the VAE sees whole frames) and the feather, checked
         if switches:
             raise TypeError(f"__call__() got an unexpected keyword argument {next(iter(switches))!r}")
         if o.edit_mask is not None:
@@ -415,6 +433,31 @@ class WanPipeline:
             if not o.edit_region:
                 raise ValueError("edit_region_time_margin extends edit_region=True (the frame range is cropped with the rectangle), and "
                                  "this call does not set it")
+        from .edit_region import region_stitch_feather
+        o.stitch_feather = region_stitch_feather(o.edit_region_stitch_feather)
+        if o.edit_region_vae_halo is not None:
+            from .edit_region import region_vae_halo_cells
+            o.vae_halo = region_vae_halo_cells(o.edit_region_vae_halo)
+            if not o.edit_region:
+                raise ValueError("edit_region_vae_halo extends edit_region=True (the box is the region's rectangle and a halo), and this "
+                                 "call does not set it")
+            if output_type != "uint8":
+                raise ValueError(f"edit_region_vae_halo returns the source's own bytes outside the region: it needs output_type='uint8', "
+                                 f"not {output_type!r}")
+            src = torch.from_numpy(video) if isinstance(video, np.ndarray) else video
+            if has_latents or not torch.is_tensor(src) or src.dtype != torch.uint8 or src.dim() not in (4, 5) or src.shape[-1] != 3:
+                raise ValueError("edit_region_vae_halo crops the source's pixels and stitches the result into them: it needs the uint8 "
+                                 "source frames as `video` ([T, H, W, 3] or [B, T, H, W, 3]) and neither `latents` nor `source_latents`"
+                                 + (", and this call gives latents" if has_latents else
+                                    f", got {getattr(src, 'dtype', type(src))} {tuple(getattr(src, 'shape', ()))}"))
+            if tuple(src.shape[-4:-1]) != (source_frames, height, width):
+                raise ValueError(f"edit_region_vae_halo: `video` {tuple(src.shape)} is not [{source_frames}, {height}, {width}, 3] or [B, "
+                                 f"{source_frames}, {height}, {width}, 3] (source_frames, height, width of this call)")
+            if self.vae is None:
+                raise ValueError("edit_region_vae_halo: the box is encoded and decoded by the VAE, and this pipeline has none")
+        elif o.stitch_feather:
+            raise ValueError(f"edit_region_stitch_feather={o.stitch_feather} softens the stitch of edit_region_vae_halo, and this call "
+                             "does not set it")
         if o.compare:
             if output_type != "uint8":
                 raise ValueError(f"compare=True composes the compare clip from uint8 frames on the device: it needs "
@@ -453,22 +496,36 @@ class WanPipeline:
             _require_source(has_source, f"{name}={option}: the windows are cut from a source clip")
         return window_latents, tile_cells
 
-    def _mask_weights(self, o, latents, cc, G, source_frames, height, width):
-        """Edit inside a mask: the latent-cell weights uint8 [1 or B, Fs, hl, wl], made once (None without a mask)."""
+    def _mask_weights(self, o, shape, device, cc, G, source_frames, height, width):
+        """Edit inside a mask: the latent-cell weights uint8 [1 or B, Fs, hl, wl], made once (None without a mask).  `shape`: the
+        latents' [B, C, F, hl, wl] -- or, before the encode (`edit_region_vae_halo`), what the call's sizes say it will be."""
         if o.mask_args is None:
             return None
         from . import video_io
-        B, _, Ftot, hl, wl = latents.shape
+        B, _, Ftot, hl, wl = shape
         lead = 1 if o.edit_mask.dim() == 3 else int(o.edit_mask.shape[0])
         cells = (height // video_io.LATENT_CELL, width // video_io.LATENT_CELL)
         if not _has_layout(Ftot, cc, G) or (hl, wl) != cells or lead not in (1, B):
             raise ValueError(f"edit_mask: a mask {tuple(o.edit_mask.shape)} for latents of {B} samples, {Ftot} frames of {hl} x {wl} "
                              f"cells; expected {_LAYOUT.format(cc, G)} frames of {cells[0]} x {cells[1]} cells and a mask for 1 or {B} samples")
-        weights = video_io.latent_edit_mask((o.edit_mask if o.edit_mask.dim() == 4 else o.edit_mask.unsqueeze(0)).to(latents.device),
+        weights = video_io.latent_edit_mask((o.edit_mask if o.edit_mask.dim() == 4 else o.edit_mask.unsqueeze(0)).to(device),
                                             grow=o.mask_args[0], grow_t=o.mask_args[1], feather=o.mask_args[2])
         if weights.shape[1] != cc:
             raise ValueError(f"edit_mask: {source_frames} mask frames are {weights.shape[1]} latent frames; the source segment has {cc}")
         return weights
+
+    def _plan_region(self, o, weights, hl, wl, tile_cells, cc, G):
+        """The bounds of the non-zero weights (wan_mask_bounds), their copy to the host -- the ONE synchronisation of edit_region -- and
+        the rules on it: (RegionPlan, TimeRegion or None without `edit_region_time_margin`)."""
+        from . import ops
+        from .edit_region import region_plan, region_time_plan
+        if G > cc:
+            raise ValueError(f"edit_region: {G} grounding frames for {cc} source frames; outside the region grounding frame g is "
+                             "source frame g, so at most as many")
+        bounds = ops.mask_bounds(weights).cpu()
+        plan = region_plan(bounds, (hl, wl), o.region_margin, None if tile_cells is None else tile_cells[0],
+                           int(self.transformer.config.patch_size[1]))
+        return plan, None if o.region_time_margin is None else region_time_plan(bounds, cc, o.region_time_margin, G)
 
     def _crop_to_region(self, o, latents, weights, tile_cells, cc, G):
         """Edit region, the first of its two stages: the bounds of the non-zero weights (wan_mask_bounds; their 16 bytes
@@ -482,16 +539,9 @@ class WanPipeline:
         if not o.edit_region:
             return latents, weights, None, cc
         from . import ops
-        from .edit_region import region_plan, region_time_plan
-        if G > cc:
-            raise ValueError(f"edit_region: {G} grounding frames for {cc} source frames; outside the region grounding frame g is "
-                             "source frame g, so at most as many")
         hl, wl = int(latents.shape[3]), int(latents.shape[4])
-        bounds = ops.mask_bounds(weights).cpu()
-        plan = region_plan(bounds, (hl, wl), o.region_margin, None if tile_cells is None else tile_cells[0],
-                           int(self.transformer.config.patch_size[1]))
-        if o.region_time_margin is not None:
-            span = region_time_plan(bounds, cc, o.region_time_margin, G)
+        plan, span = self._plan_region(o, weights, hl, wl, tile_cells, cc, G)
+        if span is not None:
             if (plan.h, plan.w, span.n) == (hl, wl, cc):
                 return latents, weights, (plan, None, span), cc
             t0, n = span
@@ -503,16 +553,57 @@ class WanPipeline:
         return ops.region_crop(latents.contiguous(), plan), ops.region_crop(weights, plan), (plan, latents[:, :, :cc], None), cc
 
     @staticmethod
-    def _restore_region(latents, region):
+    def _restore_region(latents, region, box=None):
         """Edit region, the second stage: the loop's final state on the region put back into the source latents (wan_region_restore, or
-        wan_region_restore_frames after a time crop) -- outside the region the grounding and target frames are the source's bits."""
+        wan_region_restore_frames after a time crop) -- outside the region the grounding and target frames are the source's bits.
+        `box` (`edit_region_vae_halo`): the source latents are the VAE box's, and the region's corner counts from the box's."""
         plan, source, span = region
         if source is None:
             return latents
         from . import ops
+        origin = (plan.y0, plan.x0) if box is None else (plan.y0 - box.y0, plan.x0 - box.x0)
         if span is not None:
-            return ops.region_restore_frames(source.to(latents.dtype), latents, (plan.y0, plan.x0), span)
-        return ops.region_restore(source.to(latents.dtype), latents, (plan.y0, plan.x0))
+            return ops.region_restore_frames(source.to(latents.dtype), latents, origin, span)
+        return ops.region_restore(source.to(latents.dtype), latents, origin)
+
+    def _encode_box_to_region(self, o, video, generator, dtype, device, tile_cells, cc, G, source_frames, height, width):
+        """Edit region with `edit_region_vae_halo`: what prepare_*_latents, _mask_weights and _crop_to_region do, with
+        the VAE on the box only.  The weights, the bounds and the region come first -- they need the mask and the call's sizes only --
+        then the box (edit_region.region_vae_box).  The uint8 frames go to the device once and stay there (the stitch reads them);
+        wan_frames_u8_box_to_video and the encoder give source latents of the box's size.  The noise is drawn with the ONE call
+        prepare_cot_video_latents makes, for the whole frame, and cropped to the region: the call's random stream and the noise inside
+        the region are those of the call without the option.  The loop state is [the box's source latents cropped to the region |
+        the cropped noise]; the frame range of `edit_region_time_margin` is cropped at the latent level as ever (the VAE box is
+        spatial only).  Returns (latents, weights, region, the source frames of the loop's clip, the box in cells, (the device
+        frames, the box, the region's rectangle, the feather) for the stitch); `region` as _crop_to_region returns it, its source
+        block the box's."""
+        from . import ops
+        from .edit_region import RegionPlan, region_vae_box
+        frames = torch.from_numpy(video) if isinstance(video, np.ndarray) else video
+        frames = (frames if frames.dim() == 5 else frames.unsqueeze(0)).to(device).contiguous()
+        B, scr = int(frames.shape[0]), getattr(getattr(self.vae, "config", None), "spatial_compression_ratio", 8)
+        hl, wl = height // scr, width // scr
+        weights = self._mask_weights(o, (B, None, 2 * cc + G, hl, wl), device, cc, G, source_frames, height, width)
+        plan, span = self._plan_region(o, weights, hl, wl, tile_cells, cc, G)
+        box = region_vae_box(plan, (hl, wl), (o.vae_halo, o.vae_halo))
+        inner = RegionPlan(plan.y0 - box.y0, plan.x0 - box.x0, plan.h, plan.w)           # the region inside the box
+        t_stage = self._stage("vae_encode")
+        planes = ops.frames_u8_box_to_video(frames, box.pixels(scr), dtype)
+        source = torch.cat([self.vae.encode(planes[i:i + 1])[0].mode() for i in range(B)])       # as _encode_modes
+        if source.shape[2] != cc:
+            raise ValueError(f"edit_region_vae_halo: {source_frames} source frames are {source.shape[2]} latent frames; the source segment has {cc}")
+        noise = self._randn((B, source.shape[1], cc + G, hl, wl), generator, device, dtype)
+        self._stage("vae_encode", t_stage)
+        stitch = (frames, box.pixels(scr), plan.pixels(scr), o.stitch_feather)
+        t0, n = (0, cc) if span is None else span
+        if (plan.h, plan.w, n) == (hl, wl, cc):                                              # nothing to crop: the box is the frame too
+            return torch.cat([source, noise], dim=2), weights, (plan, None, span), cc, box, stitch
+        if span is None:
+            state = torch.cat([ops.region_crop(source, inner), ops.region_crop(noise, plan)], dim=2)
+            return state, ops.region_crop(weights, plan), (plan, source, None), cc, box, stitch
+        state = torch.cat([ops.region_crop_frames(source, [(t0, n)], inner),
+                           ops.region_crop_frames(noise, ([(0, G)] if G else []) + [(G + t0, n)], plan)], dim=2)
+        return state, ops.region_crop_frames(weights, [(t0, n)], plan), (plan, source, span), n, box, stitch
 
     def _plan_windows(self, o, sizes, shape, cc, G, capture_graph):
         """(plan, tiles) of a clip of latent `shape`: the temporal WindowPlan, or None where the clip fits one window (or the option
@@ -727,8 +818,9 @@ class WanPipeline:
             return loop(lat, emb)
         return self._graphed_loop(key, latents, embeds, loop_fn, keep=(timesteps, self.scheduler.sigmas))
 
-    def _decode_outputs(self, latents, output_type, cot, cc, G, compare_source, return_dict):
-        """:757-790 -- decode only the grounding and edit segments: (videos, ground_videos, edit_videos, compare_videos)."""
+    def _decode_outputs(self, latents, output_type, cot, cc, G, compare_source, return_dict, stitch=None):
+        """:757-790 -- decode only the grounding and edit segments: (videos, ground_videos, edit_videos, compare_videos).  `stitch`: see
+        _decode_frames_u8 -- the frames have the source's size then, not the latents'."""
         ground_video = edit_video = video_out = compare_out = None
         if output_type == "latent":
             return video_out, ground_video, edit_video, compare_out
@@ -748,6 +840,8 @@ class WanPipeline:
             ng = nfr(g1 - g0) if (g1 > g0 and g0 < Ftot) else 0
             ne = nfr(Ftot - g1) if g1 < Ftot else 0
             B, H, W = latents.shape[0], latents.shape[3] * scr, latents.shape[4] * scr
+            if stitch is not None:
+                H, W = int(stitch[0].shape[2]), int(stitch[0].shape[3])
             clip = dev_clip = None
             if ng + ne > 0 and (u8 or latents.is_cuda):
                 shape, dtype = ((B, ng + ne, H, W, 3), torch.uint8) if u8 else ((B, 3, ng + ne, H, W), torch.float32)
@@ -756,7 +850,7 @@ class WanPipeline:
 
             def segment(lat, a, b, keep=None):      # latent frames `lat` decoded into frames [a, b) of the clip
                 if u8:
-                    return self._decode_frames_u8(lat, clip[:, a:b], dev_clip, a, keep)
+                    return self._decode_frames_u8(lat, clip[:, a:b], dev_clip, a, keep, stitch)
                 return self.decode_latents(lat, None if clip is None else clip[:, :, a:b])
             if ng:
                 ground_video = segment(latents[:, :, g0:g1], 0, ng)
@@ -767,8 +861,8 @@ class WanPipeline:
             elif not u8:
                 video_out = np.concatenate([v for v in (ground_video, edit_video) if v is not None], axis=2)
         elif cc < Ftot:
-            video_out = edit_video = (self._decode_frames_u8(latents[:, :, cc:], None, keep=edit_dev) if edit_dev is not None
-                                      else self.decode_latents(latents[:, :, cc:], as_uint8=u8))
+            video_out = edit_video = (self._decode_frames_u8(latents[:, :, cc:], None, keep=edit_dev, stitch=stitch)
+                                      if edit_dev is not None or stitch is not None else self.decode_latents(latents[:, :, cc:], as_uint8=u8))
         if edit_dev:
             from . import video_io
             src = (compare_source if compare_source.dim() == 5 else compare_source.unsqueeze(0)).to(edit_dev[0].device)
@@ -797,7 +891,8 @@ class WanPipeline:
                  skip_source_prediction: bool = True, capture_graph=False, **switches):
         # -- the switches (see _parse_switches for what they are), checked before anything runs
         has_source = video is not None or source_latents is not None or latents is not None
-        opt = self._parse_switches(switches, video, has_source, source_frames, height, width, output_type, capture_graph)
+        opt = self._parse_switches(switches, video, has_source, source_frames, height, width, output_type, capture_graph,
+                                   has_latents=latents is not None or source_latents is not None)
         # `timesteps`: with either scheduler built here the reference never looks at it (pipeline_wan.py:613-621: UniPC takes
         # set_timesteps(num_inference_steps, device=, shift=), DPM++ the sigmas of get_sampling_sigmas); accepted and ignored here too.
         del timesteps
@@ -822,21 +917,32 @@ class WanPipeline:
         condition_count = 1 if source_frames == 1 else (source_frames - 1) // ratio + 1         # :630-631
         window_sizes = self._window_sizes(opt, ratio, has_source)
         ground_latent_count = 0
-        t_stage = self._stage("vae_encode")
         if cot:
             ground_latent_count = 1 if reasoning_frames <= 1 else (reasoning_frames - 1) // ratio + 1   # :637
-            latents = self.prepare_cot_video_latents(video, ground_latent_count, dtype=weight_dtype, device=device, generator=generator,
-                                                     condition_count=condition_count, latents=latents, source_latents=source_latents)
+        vae_box = stitch = None
+        if opt.vae_halo is not None:
+            # `edit_region_vae_halo`: the mask, the region and the box first, then the encode of the box only
+            latents, mask_weights, region, loop_cc, vae_box, stitch = self._encode_box_to_region(
+                opt, video, generator, weight_dtype, device, window_sizes[1], condition_count, ground_latent_count, source_frames,
+                height, width)
+            if opt.compare:
+                opt.compare_source = stitch[0]           # the source frames are on the device already
         else:
-            # repeat / org layouts: noise block has the source's frame count (:653-677 -> :343-378)
-            latents = self.prepare_video_latents_new(video, dtype=weight_dtype, device=device, generator=generator,
-                                                     condition_count=condition_count, latents=latents, source_latents=source_latents)
-        self._stage("vae_encode", t_stage)
-        # -- the mask and the windows; what one forward holds: the whole clip, or one window of `win_n` source frames and `win_hw` cells
-        mask_weights = self._mask_weights(opt, latents, condition_count, ground_latent_count, source_frames, height, width)
-        # `loop_cc`: the source frames of the clip the loop runs on -- condition_count, or the frame range's after a time crop
-        latents, mask_weights, region, loop_cc = self._crop_to_region(opt, latents, mask_weights, window_sizes[1], condition_count,
-                                                                      ground_latent_count)
+            t_stage = self._stage("vae_encode")
+            if cot:
+                latents = self.prepare_cot_video_latents(video, ground_latent_count, dtype=weight_dtype, device=device, generator=generator,
+                                                         condition_count=condition_count, latents=latents, source_latents=source_latents)
+            else:
+                # repeat / org layouts: noise block has the source's frame count (:653-677 -> :343-378)
+                latents = self.prepare_video_latents_new(video, dtype=weight_dtype, device=device, generator=generator,
+                                                         condition_count=condition_count, latents=latents, source_latents=source_latents)
+            self._stage("vae_encode", t_stage)
+            # -- the mask and the windows; what one forward holds: the whole clip, or one window of `win_n` source frames and `win_hw` cells
+            mask_weights = self._mask_weights(opt, latents.shape, latents.device, condition_count, ground_latent_count, source_frames,
+                                              height, width)
+            # `loop_cc`: the source frames of the clip the loop runs on -- condition_count, or the frame range's after a time crop
+            latents, mask_weights, region, loop_cc = self._crop_to_region(opt, latents, mask_weights, window_sizes[1], condition_count,
+                                                                          ground_latent_count)
         plan, tiles = self._plan_windows(opt, window_sizes, latents.shape, loop_cc, ground_latent_count, capture_graph)
         windowed = plan is not None or tiles is not None
         win_n = loop_cc if not windowed else tiles.t.window if tiles is not None else plan.window
@@ -882,14 +988,16 @@ class WanPipeline:
             else:
                 latents = loop(latents, in_prompt_embeds)
         if region is not None:
-            latents = self._restore_region(latents, region)
+            latents = self._restore_region(latents, region, vae_box)
         self._stage("denoise_loop", t_stage)
         # -- decode (:757-790)
         t_stage = self._stage("vae_decode")
         videos, ground, edit, compared = self._decode_outputs(latents, output_type, cot, condition_count, ground_latent_count,
-                                                              opt.compare_source, return_dict)
+                                                              opt.compare_source, return_dict, stitch)
         self._stage("vae_decode", t_stage)
         return WanPipelineOutput(videos=videos, ground_videos=ground, edit_videos=edit, latents=latents, compare_videos=compared,
                                  edit_region=None if region is None else region[0].pixels(
                                      getattr(getattr(self.vae, "config", None), "spatial_compression_ratio", 8)),
-                                 edit_region_time=None if region is None or region[2] is None else region[2].pixels(ratio))
+                                 edit_region_time=None if region is None or region[2] is None else region[2].pixels(ratio),
+                                 edit_region_vae=None if vae_box is None else vae_box.pixels(
+                                     getattr(getattr(self.vae, "config", None), "spatial_compression_ratio", 8)))
