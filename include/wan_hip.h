@@ -763,6 +763,34 @@ wan_status_t wan_region_crop_frames(void* out, const void* in, int elem_bytes, i
 wan_status_t wan_region_restore_frames(void* out, const void* source, const void* region, int elem_bytes, int B, int C, int cc, int G,
                                        int H, int W, int t0, int n, int y0, int x0, int hr, int wr, void* stream);
 
+/* a17g  Edit region, a box that follows the mask from frame to frame (`edit_region_follow`): one size hr x wr for the
+ *      clip and a corner per latent frame.  The frames forms of a17f with a table of corners; videocof_amd/edit_region.py states both
+ *      in plain torch (reference_region_crop_track, reference_region_restore_track) and the kernels equal them bit for bit.
+ *      replaces: nothing in the reference, whose loop runs on whole frames.
+ *      `origins` is read on the HOST, like `runs`: int32 pairs (y0_f, x0_f), one per frame.  Every entry is validated before anything
+ *      is enqueued, then the table travels BY VALUE in the kernel's arguments, two 16-bit values per frame, at most
+ *      WAN_REGION_TRACK_MAX_FRAMES frames; a workgroup indexes it with its own frame, which is a scalar load of the argument segment.
+ *      So: no device allocation, no host-to-device copy, no synchronisation, ONE kernel per call.  The access unit is a17f's over W, wr,
+ *      the bitwise OR of every x0_f and the base addresses: a single odd x0_f lowers it for the whole launch.
+ *      wan_region_crop_track: wan_region_crop_frames with the box of INPUT frame f at origins[f] (`origins`: [F, 2]): in [R, F, H, W]
+ *          -> out [R, Fo, hr, wr], output frame k = the box of the k-th frame the runs list, at that frame's corner.  The kernel
+ *          knows no layout: for the loop state [source | grounding | target] the caller passes a table over all F = 2 cc + G frames
+ *          in which grounding g has source frame g's corner and target f source frame f's; the weights take the table of the cc
+ *          source frames.
+ *      wan_region_restore_track: wan_region_restore_frames with the box of source frame f at origins[f] (`origins`: [cc, 2]):
+ *              source frame f            source[f]
+ *              grounding frame g         region[n + g] inside box g, source[g] outside it                    (hence 0 <= G <= cc)
+ *              target frame f            region[n + G + f - t0] where t0 <= f < t0 + n and inside box f, source[f] everywhere else
+ *          so outside its frame's box, and outside the range, the target IS the source, bit for bit.
+ *      WAN_ERR_INVALID: whatever the frames forms reject, a null `origins`, any box that does not lie inside the frame (of ALL F, or
+ *      cc, entries, listed by a run or not), more than WAN_REGION_TRACK_MAX_FRAMES frames (F, or cc).  A corner must be below 65536.
+ *      Constant origins give the bytes of the frames forms. */
+#define WAN_REGION_TRACK_MAX_FRAMES 512
+wan_status_t wan_region_crop_track(void* out, const void* in, int elem_bytes, int64_t R, int F, int H, int W, const int* runs,
+                                   int n_runs, const int* origins, int hr, int wr, void* stream);
+wan_status_t wan_region_restore_track(void* out, const void* source, const void* region, int elem_bytes, int B, int C, int cc, int G,
+                                      int H, int W, int t0, int n, const int* origins, int hr, int wr, void* stream);
+
 /* ===========================================================================
  * WanVAE (videox_fun/models/wan_vae.py).  Activations are CHANNELS-LAST bf16 [T, H, W, C].
  * ------------------------------------------------------------------------- */

@@ -244,6 +244,9 @@ SIGNATURES = {
     "wan_region_restore": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 11 + [c_void_p]),
     "wan_region_crop_frames": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, POINTER(c_int)] + [c_int] * 5 + [c_void_p]),
     "wan_region_restore_frames": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 13 + [c_void_p]),
+    "wan_region_crop_track": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, POINTER(c_int), c_int, POINTER(c_int),
+                                      c_int, c_int, c_void_p]),
+    "wan_region_restore_track": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 9 + [POINTER(c_int), c_int, c_int, c_void_p]),
     "wan_gemm_bf16_batched": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64,
                                       c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "wan_embedding_rows": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p]),

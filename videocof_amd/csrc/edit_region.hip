@@ -6,6 +6,10 @@
 // the temporal context windows, whose first latent frame is not the clip's first either), the same two kernels with a range of frames:
 //   wan_region_crop_frames      the sub-box of up to three runs of frames of a contiguous [R, F, H, W] tensor -> [R, Fo, hr, wr]
 //   wan_region_restore_frames   the region holds the source frames [t0, t0 + n) only: target frames outside the range are the source
+// and, where the box follows the mask from frame to frame (`edit_region_follow`: one size, a corner per latent frame), the frames forms
+// with a table of corners in the kernel's arguments, which a workgroup indexes with its frame (a scalar load, like every other argument):
+//   wan_region_crop_track       the box of input frame f lies at origins[f]
+//   wan_region_restore_track    the box of source frame f (and of grounding and target frame f) lies at origins[f]
 // All three are streams of rows at a pitch: the access unit is the widest of 16 / 8 / 4 bytes or one element that divides every length,
 // pitch, x origin and base address (region_unit_bytes below: the rule of tile_unit_bytes in window_kernels.hip), so all x arithmetic is
 // in whole units and no unit straddles the region's edge.  A workgroup is `rp` rows of `cw` lanes each (cw = min(units per row, 256),
@@ -137,6 +141,86 @@ __global__ __launch_bounds__(256) void region_restore_kernel(U* __restrict__ out
     // grounding frames, and target frames of the range, take the region inside its box: rf is their frame there (< 2 n + G), -1: none
     const int rf = F < cc ? -1 : F < cc + G ? n + (F - cc) : (sf >= t0 && sf < t0 + n) ? n + G + (sf - t0) : -1;
     const bool mixed = rf >= 0;
+    const U* s = source + (bc * cc + sf) * H * wu;
+    const U* r = region + (bc * (2 * n + G) + (mixed ? rf : 0)) * hr * ru;
+    U* o = out + (int64_t)row * H * wu;
+    const int lr = threadIdx.x / cw, lu = threadIdx.x % cw;
+    if (lr >= rp) return;
+    for (int r0 = blockIdx.y * UNROLL * rp; r0 < H; r0 += gridDim.y * UNROLL * rp)
+        for (int u = lu; u < wu; u += cw) {           // one pass unless a row is longer than 256 units
+            U v[UNROLL];
+#pragma unroll
+            for (int j = 0; j < UNROLL; ++j) {
+                const int y = r0 + j * rp + lr;
+                if (y >= H) continue;
+                const bool inside = mixed && y >= y0 && y < y0 + hr && u >= x0u && u < x0u + ru;
+                const U* p = inside ? r + (int64_t)(y - y0) * ru + (u - x0u) : s + (int64_t)y * wu + u;
+                v[j] = *p;
+            }
+#pragma unroll
+            for (int j = 0; j < UNROLL; ++j) {
+                const int y = r0 + j * rp + lr;
+                if (y < H) o[(int64_t)y * wu + u] = v[j];
+            }
+        }
+}
+
+// ------------------------------------------------------------------------------------------------------------- the box that follows
+// the corners of up to WAN_REGION_TRACK_MAX_FRAMES frames, by value in the kernel's arguments: y0 in the high half, x0 in the low half
+// (both < 2^16, checked by the host).  Indexed with the workgroup's frame only, so the read is one scalar load of the argument segment.
+struct TrackTable { unsigned at[WAN_REGION_TRACK_MAX_FRAMES]; };
+
+// region_crop_kernel with the box of input frame f at origins.at[f]; `xs` = log2 of the elements per unit (every x0 is whole units)
+template <typename U>
+__global__ __launch_bounds__(256) void region_crop_track_kernel(U* __restrict__ out, const U* __restrict__ in, FrameRuns runs,
+                                                                TrackTable origins, unsigned Fo, int F, int64_t fu, int pitch, int xs,
+                                                                int hr, int ru, int cw, int rp) {
+    const unsigned row = blockIdx.x;                  // < R * Fo (the grid)
+    int k = (int)(row % Fo);                          // < the sum of the counts
+    const int64_t sample = row / Fo;
+    int f = runs.start[0] + k;
+    if (k >= runs.count[0]) {
+        k -= runs.count[0];
+        f = runs.start[1] + k;
+        if (k >= runs.count[1]) f = runs.start[2] + k - runs.count[1];
+    }
+    const unsigned at = origins.at[f];                // f < F <= WAN_REGION_TRACK_MAX_FRAMES, and every box lies inside the frame (host)
+    const int64_t org = (int64_t)(at >> 16) * pitch + ((at & 0xffffu) >> xs);
+    const U* src = in + (sample * F + f) * fu + org;
+    U* dst = out + (int64_t)row * hr * ru;
+    const int lr = threadIdx.x / cw, lu = threadIdx.x % cw;
+    if (lr >= rp) return;
+    for (int r0 = blockIdx.y * UNROLL * rp; r0 < hr; r0 += gridDim.y * UNROLL * rp)
+        for (int u = lu; u < ru; u += cw) {           // one pass unless a region row is longer than 256 units
+            U v[UNROLL];                              // UNROLL independent loads in flight per lane, then the stores
+#pragma unroll
+            for (int j = 0; j < UNROLL; ++j) {
+                const int r = r0 + j * rp + lr;
+                if (r < hr) v[j] = src[(int64_t)r * pitch + u];
+            }
+#pragma unroll
+            for (int j = 0; j < UNROLL; ++j) {
+                const int r = r0 + j * rp + lr;
+                if (r < hr) dst[(int64_t)r * ru + u] = v[j];
+            }
+        }
+}
+
+// region_restore_kernel with the box of source frame sf at origins.at[sf]
+template <typename U>
+__global__ __launch_bounds__(256) void region_restore_track_kernel(U* __restrict__ out, const U* __restrict__ source,
+                                                                   const U* __restrict__ region, TrackTable origins, int cc, int G,
+                                                                   int t0, int n, int H, int wu, int xs, int hr, int ru, int cw,
+                                                                   int rp) {
+    const unsigned Ftot = (unsigned)(2 * cc + G);
+    const unsigned row = blockIdx.x;                  // < B * C * Ftot (the grid)
+    const int F = (int)(row % Ftot);
+    const int64_t bc = row / Ftot;
+    const int sf = F < cc ? F : F < cc + G ? F - cc : F - cc - G;       // < cc <= WAN_REGION_TRACK_MAX_FRAMES: G <= cc (checked by the host)
+    const int rf = F < cc ? -1 : F < cc + G ? n + (F - cc) : (sf >= t0 && sf < t0 + n) ? n + G + (sf - t0) : -1;
+    const bool mixed = rf >= 0;
+    const unsigned at = origins.at[sf];
+    const int y0 = (int)(at >> 16), x0u = (int)((at & 0xffffu) >> xs);
     const U* s = source + (bc * cc + sf) * H * wu;
     const U* r = region + (bc * (2 * n + G) + (mixed ? rf : 0)) * hr * ru;
     U* o = out + (int64_t)row * H * wu;
@@ -302,4 +386,108 @@ extern "C" wan_status_t wan_region_restore_frames(void* out, const void* source,
                                                   int cc, int G, int H, int W, int t0, int n, int y0, int x0, int hr, int wr,
                                                   void* stream) {
     return restore_frames("wan_region_restore_frames", out, source, region, elem_bytes, B, C, cc, G, H, W, t0, n, y0, x0, hr, wr, stream);
+}
+
+// the table of corners, checked and packed: every one of the `frames` boxes of hr x wr lies inside the H x W frame.  `x_or` takes the
+// bitwise OR of the x0 (the access unit must divide every one of them).
+static wan_status_t pack_origins(const char* who, TrackTable* table, int64_t* x_or, const int* origins, int frames, int H, int W, int hr,
+                                 int wr) {
+    WAN_REQUIRE(origins, WAN_ERR_INVALID, "%s: null origins", who);
+    WAN_REQUIRE(frames >= 1 && frames <= WAN_REGION_TRACK_MAX_FRAMES, WAN_ERR_INVALID,
+                "%s: a table of %d frames (1 to %d: it travels in the kernel's arguments)", who, frames, WAN_REGION_TRACK_MAX_FRAMES);
+    *x_or = 0;
+    for (int f = 0; f < frames; ++f) {
+        const int y0 = origins[2 * f], x0 = origins[2 * f + 1];
+        WAN_REQUIRE(box_ok(H, W, y0, x0, hr, wr) && y0 <= 0xffff && x0 <= 0xffff, WAN_ERR_INVALID,
+                    "%s: frame %d: the region [%d, %d + %d) x [%d, %d + %d) does not lie inside a frame of %d x %d (corners below 65536)",
+                    who, f, y0, y0, hr, x0, x0, wr, H, W);
+        table->at[f] = ((unsigned)y0 << 16) | (unsigned)x0;
+        *x_or |= x0;
+    }
+    for (int f = frames; f < WAN_REGION_TRACK_MAX_FRAMES; ++f) table->at[f] = 0;
+    return WAN_OK;
+}
+
+static int log2_of(int n) {                           // n = 1, 2, 4, 8 or 16
+    int s = 0;
+    while ((1 << s) < n) ++s;
+    return s;
+}
+
+extern "C" wan_status_t wan_region_crop_track(void* out, const void* in, int elem_bytes, int64_t R, int F, int H, int W, const int* runs,
+                                              int n_runs, const int* origins, int hr, int wr, void* stream) {
+    const char* who = "wan_region_crop_track";
+    // (the boxes and the runs first, as in crop_frames: an empty region's output is an empty tensor, whose address is null)
+    WAN_REQUIRE(R >= 1 && F >= 1 && H >= 1 && W >= 1 && hr >= 1 && wr >= 1 && hr <= H && wr <= W, WAN_ERR_INVALID,
+                "%s: a region of %d x %d in %lld x %d frames of %d x %d", who, hr, wr, (long long)R, F, H, W);
+    TrackTable table;
+    int64_t x_or = 0;
+    const wan_status_t st = pack_origins(who, &table, &x_or, origins, F, H, W, hr, wr);
+    if (st != WAN_OK) return st;
+    WAN_REQUIRE(runs && n_runs >= 1 && n_runs <= 3, WAN_ERR_INVALID, "%s: %d runs of frames at %p (1 to 3, not null)", who, n_runs,
+                (const void*)runs);
+    FrameRuns fr = {{0, 0, 0}, {0, 0, 0}};
+    int64_t Fo = 0;
+    for (int i = 0, end = 0; i < n_runs; ++i) {
+        const int start = runs[2 * i], count = runs[2 * i + 1];
+        WAN_REQUIRE(start >= end && count >= 1 && (int64_t)start + count <= F, WAN_ERR_INVALID,
+                    "%s: run %d = frames [%d, %d + %d) of %d (ascending, not overlapping, at least one frame each, inside the clip)", who, i,
+                    start, start, count, F);
+        fr.start[i] = start; fr.count[i] = count;
+        end = start + count;
+        Fo += count;
+    }
+    WAN_REQUIRE(out && in, WAN_ERR_INVALID, "%s: null tensor", who);
+    WAN_REQUIRE(elem_bytes == 1 || elem_bytes == 2 || elem_bytes == 4, WAN_ERR_INVALID, "%s: elements of %d bytes (1, 2 or 4)", who,
+                elem_bytes);
+    WAN_REQUIRE(R <= 0x7fffffff && R * F <= 0x7fffffff && (int64_t)H * W <= 0x7fffffff, WAN_ERR_INVALID,
+                "%s: %lld clips of %d frames of %lld elements (frames in all and elements a frame: each at most 2^31 - 1)", who,
+                (long long)R, F, (long long)((int64_t)H * W));
+    const int64_t es = elem_bytes, frames = R * Fo;
+    const int ub = region_unit_bytes(es, {W, wr, x_or}, (uintptr_t)out | (uintptr_t)in);
+    const int N = (int)(ub / es), ru = wr / N, cw = std::min(ru, 256), rp = 256 / cw;
+    const dim3 grid((unsigned)frames, row_chunks(hr, UNROLL * rp, frames));
+    hipStream_t s = (hipStream_t)stream;
+#define WAN_CROP_TRACK(U)                                                                                                      \
+    hipLaunchKernelGGL(region_crop_track_kernel<U>, grid, dim3(256), 0, s, (U*)out, (const U*)in, fr, table, (unsigned)Fo, F,  \
+                       (int64_t)H * W / N, W / N, log2_of(N), hr, ru, cw, rp)
+    WAN_BY_UNIT(ub, WAN_CROP_TRACK);
+#undef WAN_CROP_TRACK
+    WAN_CHECK_LAUNCH(who);
+    return WAN_OK;
+}
+
+extern "C" wan_status_t wan_region_restore_track(void* out, const void* source, const void* region, int elem_bytes, int B, int C, int cc,
+                                                 int G, int H, int W, int t0, int n, const int* origins, int hr, int wr, void* stream) {
+    const char* who = "wan_region_restore_track";
+    WAN_REQUIRE(out && source && region, WAN_ERR_INVALID, "%s: null tensor", who);
+    WAN_REQUIRE(elem_bytes == 1 || elem_bytes == 2 || elem_bytes == 4, WAN_ERR_INVALID, "%s: elements of %d bytes (1, 2 or 4)", who,
+                elem_bytes);
+    WAN_REQUIRE(B >= 1 && C >= 1 && cc >= 1, WAN_ERR_INVALID, "%s: B=%d C=%d cc=%d", who, B, C, cc);
+    WAN_REQUIRE(0 <= G && G <= cc, WAN_ERR_INVALID,
+                "%s: G=%d grounding frames for cc=%d source frames (grounding frame g takes source frame g outside the region: "
+                "0 <= G <= cc)", who, G, cc);
+    WAN_REQUIRE(t0 >= 0 && n >= 1 && (int64_t)t0 + n <= cc, WAN_ERR_INVALID,
+                "%s: the frames [%d, %d + %d) do not lie inside the %d source frames", who, t0, t0, n, cc);
+    WAN_REQUIRE(H >= 1 && W >= 1 && hr >= 1 && wr >= 1 && hr <= H && wr <= W, WAN_ERR_INVALID,
+                "%s: a region of %d x %d in a frame of %d x %d", who, hr, wr, H, W);
+    TrackTable table;
+    int64_t x_or = 0;
+    const wan_status_t st = pack_origins(who, &table, &x_or, origins, cc, H, W, hr, wr);
+    if (st != WAN_OK) return st;
+    const int64_t frames = (int64_t)B * C * (2 * (int64_t)cc + G);
+    WAN_REQUIRE(frames <= 0x7fffffff && (int64_t)H * W <= 0x7fffffff, WAN_ERR_INVALID,
+                "%s: %lld frames of %lld elements (each at most 2^31 - 1)", who, (long long)frames, (long long)((int64_t)H * W));
+    const int64_t es = elem_bytes;
+    const int ub = region_unit_bytes(es, {W, wr, x_or}, (uintptr_t)out | (uintptr_t)source | (uintptr_t)region);
+    const int N = (int)(ub / es), wu = W / N, cw = std::min(wu, 256), rp = 256 / cw;
+    const dim3 grid((unsigned)frames, row_chunks(H, UNROLL * rp, frames));
+    hipStream_t s = (hipStream_t)stream;
+#define WAN_RESTORE_TRACK(U)                                                                                                   \
+    hipLaunchKernelGGL(region_restore_track_kernel<U>, grid, dim3(256), 0, s, (U*)out, (const U*)source, (const U*)region, table, cc, \
+                       G, t0, n, H, wu, log2_of(N), hr, wr / N, cw, rp)
+    WAN_BY_UNIT(ub, WAN_RESTORE_TRACK);
+#undef WAN_RESTORE_TRACK
+    WAN_CHECK_LAUNCH(who);
+    return WAN_OK;
 }

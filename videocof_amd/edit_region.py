@@ -17,6 +17,12 @@ With ``edit_region_vae_halo`` the VAE, too, sees only a part of the frame: ``reg
 region's rectangle and a halo), ``reference_frames_box_to_video`` / ``reference_video_box_stitch`` state what
 ``wan_frames_u8_box_to_video`` / ``wan_video_box_stitch_u8`` compute on either side of it (ops.frames_u8_box_to_video,
 ops.video_box_stitch_u8), bit for bit and byte for byte: the frames that come back are the source's own bytes outside the rectangle.
+
+With ``edit_region_follow`` the rectangle keeps ONE size and takes a corner per latent frame: ``region_track_plan`` fixes the corners
+from the same per-frame bounds (a sliding union over ``span`` latent frames is the only smoothing), and ``reference_region_crop_track``
+/ ``reference_region_restore_track`` state what ``wan_region_crop_track`` / ``wan_region_restore_track`` compute.  Source frame f,
+target frame f and the weights of frame f are cropped at the same corner, so the loop's pin to the source stays exact; the model sees
+a stabilised crop whose background slides: opt-in, lossy, no quality claim.
 """
 from __future__ import annotations
 
@@ -28,9 +34,11 @@ import torch
 __all__ = ["RegionPlan", "region_plan", "region_margin_cells", "reference_mask_bounds", "reference_region_crop",
            "reference_region_restore", "TimeRegion", "region_time_plan", "region_time_margin_frames", "reference_region_crop_frames",
            "reference_region_restore_frames", "region_vae_box", "region_vae_halo_cells", "region_stitch_feather",
-           "reference_frames_box_to_video", "reference_video_box_stitch", "stitch_weights"]
+           "reference_frames_box_to_video", "reference_video_box_stitch", "stitch_weights", "TrackPlan", "region_track_plan",
+           "region_follow_frames", "reference_region_crop_track", "reference_region_restore_track", "REGION_TRACK_MAX_FRAMES"]
 
 REGION_MARGIN_UNIT = 16         # pixels: the VAE's spatial ratio 8 times the patch 2 -- a margin keeps the region on the patch grid
+REGION_TRACK_MAX_FRAMES = 512   # WAN_REGION_TRACK_MAX_FRAMES: the frames a table of corners may have (it travels in the kernel's arguments)
 
 
 class RegionPlan(NamedTuple):
@@ -54,6 +62,30 @@ def _axis(lo: int, hi: int, F: int, m: int, T: Optional[int], p: int) -> Tuple[i
     return min(max(start, 0), F - size), size, want
 
 
+def _plan_args(who: str, bounds, frame_cells, margin_cells, tile_cells, patch):
+    """The argument checks of ``region_plan`` and ``region_track_plan``: (bounds int64 [rows, 4], p, [(H, W), (my, mx), (Ty, Tx)])."""
+    b = np.asarray(bounds.cpu() if torch.is_tensor(bounds) else bounds, dtype=np.int64).reshape(-1, 4)
+    p = int(patch)
+    if p < 1:
+        raise ValueError(f"{who}: patch={patch!r} (>= 1)")
+    pairs = []
+    for name, v in (("frame_cells", frame_cells), ("margin_cells", margin_cells), ("tile_cells", tile_cells)):
+        if v is None and name == "tile_cells":
+            pairs.append((None, None))
+            continue
+        if isinstance(v, (str, bytes)) or not hasattr(v, "__len__") or len(v) != 2 or any(
+                isinstance(e, bool) or not isinstance(e, (int, np.integer)) for e in v):
+            raise ValueError(f"{who}: {name}={v!r} is not a pair (rows, columns) of latent cell counts")
+        if name == "frame_cells":
+            if any(int(e) < 1 for e in v):
+                raise ValueError(f"{who}: frame_cells={tuple(v)!r}: each at least 1")
+        elif any(int(e) < (0 if name == "margin_cells" else p) or int(e) % p for e in v):
+            raise ValueError(f"{who}: {name}={tuple(v)!r}: each a {'non-negative' if name == 'margin_cells' else 'positive'} "
+                             f"multiple of the patch {p}")
+        pairs.append((int(v[0]), int(v[1])))
+    return b, p, pairs
+
+
 def region_plan(bounds, frame_cells, margin_cells, tile_cells=None, patch: int = 2) -> RegionPlan:
     """The region of a mask whose non-zero latent weights have the inclusive ``bounds`` = (y_lo, y_hi, x_lo, x_hi) -- one such row, or one
     per latent frame as ``mask_bounds`` returns them ([Fs, 4]; the union is taken, rows of an empty frame, (h, -1, w, -1), drop out).
@@ -69,26 +101,7 @@ def region_plan(bounds, frame_cells, margin_cells, tile_cells=None, patch: int =
     F is one too (every frame the model takes whole) the region's sides are multiples of p and it lies on the frame's own patch grid.
     (A frame of 135 rows, 1080 pixels, is none: it only runs as ``spatial_window`` tiles, which start anywhere, and so does a region
     of it.)  An empty mask raises ``ValueError``."""
-    b = np.asarray(bounds.cpu() if torch.is_tensor(bounds) else bounds, dtype=np.int64).reshape(-1, 4)
-    p = int(patch)
-    if p < 1:
-        raise ValueError(f"region_plan: patch={patch!r} (>= 1)")
-    pairs = []
-    for name, v in (("frame_cells", frame_cells), ("margin_cells", margin_cells), ("tile_cells", tile_cells)):
-        if v is None and name == "tile_cells":
-            pairs.append((None, None))
-            continue
-        if isinstance(v, (str, bytes)) or not hasattr(v, "__len__") or len(v) != 2 or any(
-                isinstance(e, bool) or not isinstance(e, (int, np.integer)) for e in v):
-            raise ValueError(f"region_plan: {name}={v!r} is not a pair (rows, columns) of latent cell counts")
-        if name == "frame_cells":
-            if any(int(e) < 1 for e in v):
-                raise ValueError(f"region_plan: frame_cells={tuple(v)!r}: each at least 1")
-        elif any(int(e) < (0 if name == "margin_cells" else p) or int(e) % p for e in v):
-            raise ValueError(f"region_plan: {name}={tuple(v)!r}: each a {'non-negative' if name == 'margin_cells' else 'positive'} "
-                             f"multiple of the patch {p}")
-        pairs.append((int(v[0]), int(v[1])))
-    (H, W), (my, mx), (Ty, Tx) = pairs
+    b, p, ((H, W), (my, mx), (Ty, Tx)) = _plan_args("region_plan", bounds, frame_cells, margin_cells, tile_cells, patch)
     b = b[(b[:, 1] >= b[:, 0]) & (b[:, 3] >= b[:, 2])]
     if b.shape[0] == 0:
         raise ValueError("edit_mask is empty (every latent weight is zero): there is no region to run the loop on")
@@ -112,6 +125,86 @@ def region_margin_cells(margin, ratio: int = 8) -> Tuple[int, int]:
             raise ValueError(f"edit_region_margin={tuple(margin)!r}: {e} must be a non-negative multiple of {REGION_MARGIN_UNIT} pixels "
                              "(the VAE's spatial ratio 8 times the patch 2)")
     return int(margin[0]) // ratio, int(margin[1]) // ratio
+
+
+class TrackPlan(NamedTuple):
+    """The box that follows the mask, in LATENT cells: one size (h, w) for the clip and ``origins`` int32 [Fs, 2] = (y0_f, x0_f), the
+    corner of source frame f's box."""
+    h: int
+    w: int
+    origins: np.ndarray
+
+    def pixels(self, ratio: int = 8):
+        """((h, w), ((y_f, x_f), ...)) in pixels."""
+        return (self.h * ratio, self.w * ratio), tuple((int(y) * ratio, int(x) * ratio) for y, x in self.origins)
+
+    def enclosing(self) -> RegionPlan:
+        """The rectangle that encloses every frame's box."""
+        y0, x0 = (int(v) for v in self.origins.min(axis=0))
+        y1, x1 = (int(v) for v in self.origins.max(axis=0))
+        return RegionPlan(y0, x0, y1 - y0 + self.h, x1 - x0 + self.w)
+
+
+def _track_axis(lo, hi, F: int, m: int, T: Optional[int], p: int) -> Tuple[np.ndarray, int]:
+    """One axis of the rule for every frame at once: (starts int64 [Fs], size).  ``lo``, ``hi``: int64 [Fs], never empty."""
+    lo_a, hi_a = lo // p * p, (hi // p + 1) * p
+    want_f = np.minimum(F, hi_a - lo_a + 2 * m)
+    want = int(want_f.max())
+    size = min(T, F) if T is not None and want <= T else want
+    start = lo_a - m - ((size - want_f) // (2 * p)) * p
+    return np.clip(start, 0, F - size), size
+
+
+def region_track_plan(bounds, frame_cells, margin_cells, tile_cells=None, patch: int = 2, span: int = 0) -> TrackPlan:
+    """The box that FOLLOWS a mask whose non-zero latent weights have the per-frame ``bounds`` [Fs, 4] of ``mask_bounds``: one size for
+    the whole clip, one corner per latent frame.  The arguments are ``region_plan``'s, and ``span`` >= 0, in latent frames:
+
+        U_f = the union of the non-empty rows bounds[g] with |g - f| <= span                                   (the sliding union)
+        a frame whose U_f is empty takes the U of the nearest frame whose U is not (the earlier one on a tie)
+
+    and per axis and frame, with lo_f, hi_f taken from U_f and F, p, m, T as in ``region_plan``:
+
+        lo'_f = lo_f // p * p,  hi'_f = (hi_f // p + 1) * p,  want_f = min(F, hi'_f - lo'_f + 2 m),  want = max over f of want_f
+        size    = min(T, F)  if T is given and want <= T  else  want
+        start_f = clamp(lo'_f - m - ((size - want_f) // (2 p)) * p, 0, F - size)
+
+    Every box lies inside the frame; box f contains [lo'_f - m, hi'_f + m) clipped to the frame; corners are on the patch grid except
+    where the clamp to F - size moves them off it on a frame that is no multiple of p, as in ``region_plan``.  The span is the only
+    smoothing: a larger one gives a larger, calmer box, and span >= Fs - 1 is ``region_plan`` exactly, on every frame.  An empty mask
+    raises ``ValueError``."""
+    who = "region_track_plan"
+    b, p, ((H, W), (my, mx), (Ty, Tx)) = _plan_args(who, bounds, frame_cells, margin_cells, tile_cells, patch)
+    if isinstance(span, bool) or not isinstance(span, (int, np.integer)) or span < 0:
+        raise ValueError(f"{who}: span={span!r}: an integer >= 0, in latent frames")
+    Fs, s = b.shape[0], int(span)
+    on = (b[:, 1] >= b[:, 0]) & (b[:, 3] >= b[:, 2])
+    if not on.any():
+        raise ValueError("edit_mask is empty (every latent weight is zero): there is no region to run the loop on")
+    y_lo, y_hi, x_lo, x_hi = int(b[on, 0].min()), int(b[on, 1].max()), int(b[on, 2].min()), int(b[on, 3].max())
+    if y_lo < 0 or y_hi >= H or x_lo < 0 or x_hi >= W:
+        raise ValueError(f"{who}: bounds rows [{y_lo}, {y_hi}] x columns [{x_lo}, {x_hi}] leave a frame of {H} x {W} cells")
+    u = np.zeros((Fs, 4), np.int64)
+    full = np.zeros(Fs, bool)
+    for f in range(Fs):
+        near = b[max(0, f - s):f + s + 1][on[max(0, f - s):f + s + 1]]
+        if near.shape[0]:
+            u[f], full[f] = (near[:, 0].min(), near[:, 1].max(), near[:, 2].min(), near[:, 3].max()), True
+    have = np.flatnonzero(full)
+    for f in np.flatnonzero(~full):
+        u[f] = u[have[np.argmin(np.abs(have - f))]]          # argmin takes the first of equals: the earlier frame on a tie
+    ys, h = _track_axis(u[:, 0], u[:, 1], H, my, Ty, p)
+    xs, w = _track_axis(u[:, 2], u[:, 3], W, mx, Tx, p)
+    return TrackPlan(h, w, np.stack([ys, xs], axis=1).astype(np.int32))
+
+
+def region_follow_frames(follow, ratio: int = 4) -> int:
+    """The pipeline's ``edit_region_follow`` in PIXEL frames as the ``span`` of ``region_track_plan`` in latent frames: a non-negative
+    multiple of the VAE's temporal ratio."""
+    if isinstance(follow, bool) or not isinstance(follow, (int, np.integer)):
+        raise ValueError(f"edit_region_follow={follow!r} is not an integer count of pixel frames")
+    if follow < 0 or follow % ratio:
+        raise ValueError(f"edit_region_follow={follow} must be a non-negative multiple of {ratio} pixel frames (the VAE's temporal ratio)")
+    return int(follow) // ratio
 
 
 class TimeRegion(NamedTuple):
@@ -303,6 +396,62 @@ def reference_region_restore_frames(source: torch.Tensor, state: torch.Tensor, o
     out = torch.cat([source, source[:, :, :G], source], dim=2)
     out[:, :, cc:cc + G, y0:y0 + hr, x0:x0 + wr] = state[:, :, n:n + G]
     out[:, :, cc + G + t0:cc + G + t0 + n, y0:y0 + hr, x0:x0 + wr] = state[:, :, n + G:]
+    return out
+
+
+def _origins(origins, frames: int, size, H: int, W: int, who: str) -> np.ndarray:
+    """A table of corners, checked: int64 [frames, 2], every box of ``size`` = (h, w) inside a frame of H x W."""
+    o = np.asarray(origins.cpu() if torch.is_tensor(origins) else origins)
+    if o.ndim != 2 or o.shape[1] != 2 or o.dtype.kind not in "iu":
+        raise ValueError(f"{who}: origins = integer [frames, 2] pairs (y0, x0) in cells, got {o.dtype} {o.shape}")
+    if not 1 <= o.shape[0] <= REGION_TRACK_MAX_FRAMES or o.shape[0] != frames:
+        raise ValueError(f"{who}: {o.shape[0]} rows of origins for {frames} frames (one each, at most {REGION_TRACK_MAX_FRAMES})")
+    if len(size) != 2:
+        raise ValueError(f"{who}: size = (h, w) in cells, got {size!r}")
+    o = o.astype(np.int64)
+    for f, (y0, x0) in enumerate(o):
+        _box((y0, x0, size[0], size[1]), H, W, f"{who}: frame {f}")
+    return o
+
+
+def reference_region_crop_track(x: torch.Tensor, runs, origins, size) -> torch.Tensor:
+    """``wan_region_crop_track`` in torch: ``x`` [..., F, H, W]; ``runs`` as in ``reference_region_crop_frames``; ``origins`` integer
+    [F, 2] = the corner (y0, x0) of every INPUT frame's box; ``size`` = (h, w), one for all.  The box of the listed frames, each at its
+    own corner, one run after the other, contiguous.  (The loop state [source | grounding | target] takes a table over its 2 cc + G
+    frames: grounding g has source frame g's corner, target f source frame f's.)"""
+    if x.dim() < 3:
+        raise ValueError(f"reference_region_crop_track: expected [..., F, H, W], got {tuple(x.shape)}")
+    runs = _runs(runs, x.shape[-3], "reference_region_crop_track")
+    o = _origins(origins, x.shape[-3], size, x.shape[-2], x.shape[-1], "reference_region_crop_track")
+    hr, wr = int(size[0]), int(size[1])
+    return torch.stack([x[..., f, o[f, 0]:o[f, 0] + hr, o[f, 1]:o[f, 1] + wr] for a, c in runs for f in range(a, a + c)],
+                       dim=-3).contiguous()
+
+
+def reference_region_restore_track(source: torch.Tensor, state: torch.Tensor, origins, frames) -> torch.Tensor:
+    """``wan_region_restore_track`` in torch: ``reference_region_restore_frames`` with the box of source frame f at ``origins[f]``
+    (integer [cc, 2]): grounding frame g is the region's inside box g and source frame g outside it; target frame f is the region's
+    where t0 <= f < t0 + n and inside box f, and source frame f everywhere else."""
+    who = "reference_region_restore_track"
+    if source.dim() != 5 or state.dim() != 5 or source.shape[:2] != state.shape[:2] or source.dtype != state.dtype:
+        raise ValueError(f"{who}: source {source.dtype} {tuple(source.shape)} and state {state.dtype} "
+                         f"{tuple(state.shape)}: expected [B, C, cc, H, W] and [B, C, n + G + n, hr, wr] of one dtype")
+    if len(frames) != 2:
+        raise ValueError(f"{who}: frames = (t0, n) in latent frames, got {frames!r}")
+    t0, n = int(frames[0]), int(frames[1])
+    cc, G = source.shape[2], state.shape[2] - 2 * n
+    if t0 < 0 or n < 1 or t0 + n > cc:
+        raise ValueError(f"{who}: the frames [{t0}, {t0} + {n}) do not lie inside the {cc} source frames")
+    if not 0 <= G <= cc:
+        raise ValueError(f"{who}: {state.shape[2]} state frames for a range of {n}: G={G} grounding frames (0 <= G <= cc = {cc})")
+    hr, wr = int(state.shape[3]), int(state.shape[4])
+    o = _origins(origins, cc, (hr, wr), source.shape[3], source.shape[4], who)
+    out = torch.cat([source, source[:, :, :G], source], dim=2)
+    for g in range(G):
+        out[:, :, cc + g, o[g, 0]:o[g, 0] + hr, o[g, 1]:o[g, 1] + wr] = state[:, :, n + g]
+    for k in range(n):
+        y0, x0 = o[t0 + k]
+        out[:, :, cc + G + t0 + k, y0:y0 + hr, x0:x0 + wr] = state[:, :, n + G + k]
     return out
 
 

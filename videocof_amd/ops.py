@@ -1849,6 +1849,80 @@ def region_restore_frames(source: torch.Tensor, state: torch.Tensor, origin, fra
     return out
 
 
+def _track_origins(origins, name: str):
+    """A table of corners as the C side takes it: (ctypes int array or None for an empty table, rows)."""
+    import numpy as np
+    o = np.asarray(origins.cpu() if torch.is_tensor(origins) else origins)
+    if o.ndim != 2 or o.shape[1] != 2 or o.dtype.kind not in "iu":
+        raise ValueError(f"{name}: origins = integer [frames, 2] pairs (y0, x0) in cells, got {o.dtype} {o.shape}")
+    if o.shape[0] == 0:
+        return None, 0
+    if int(o.min()) < -2 ** 31 or int(o.max()) >= 2 ** 31:
+        raise ValueError(f"{name}: origins leave the int32 range")
+    return (ctypes.c_int * o.size).from_buffer_copy(np.ascontiguousarray(o, dtype=np.int32)), int(o.shape[0])
+
+
+@_on_tensor_device
+def region_crop_track(x: torch.Tensor, runs, origins, size, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``region_crop_frames`` with a box that moves: ``origins`` integer [F, 2] on the HOST = the corner (y0, x0) of every input frame's
+    box, ``size`` = (h, w), one for all -> contiguous [..., Fo, h, w] in ONE launch (``wan_region_crop_track``: the table travels in
+    the kernel's arguments, at most 512 frames; nothing is allocated, copied to the device or synchronised).  The loop state takes a
+    table over its 2 cc + G frames (grounding g at source frame g's corner, target f at source frame f's), the weights the source
+    frames' table."""
+    if not x.is_cuda:
+        raise RuntimeError(f"region_crop_track.x: tensor is on {x.device}; the HIP path has no CPU fallback")
+    if x.element_size() not in (1, 2, 4):
+        raise ValueError(f"region_crop_track: dtype {x.dtype} not supported (elements of 1, 2 or 4 bytes)")
+    if x.dim() < 3 or not x.is_contiguous():
+        raise ValueError(f"region_crop_track.x: a contiguous [..., F, H, W] tensor, got {tuple(x.shape)}")
+    if len(size) != 2:
+        raise ValueError(f"region_crop_track: size = (h, w) in cells, got {size!r}")
+    hr, wr = int(size[0]), int(size[1])
+    runs = list(runs)
+    if any(not hasattr(pair, "__len__") or len(pair) != 2 for pair in runs):
+        raise ValueError(f"region_crop_track: runs = pairs (start, count) of frames, got {runs!r}")
+    flat = [int(v) for pair in runs for v in pair]
+    F, H, W = (int(v) for v in x.shape[-3:])
+    table, rows = _track_origins(origins, "region_crop_track")
+    if rows != F:
+        raise ValueError(f"region_crop_track: {rows} rows of origins for {F} input frames (one each)")
+    R = int(math.prod(x.shape[:-3]))
+    Fo = sum(max(c, 0) for c in flat[1::2])
+    out = _region_out(out, tuple(x.shape[:-3]) + (Fo, max(hr, 0), max(wr, 0)), x, "region_crop_track.out")
+    _lib.check(_lib.load().wan_region_crop_track(_p(out), _p(x), x.element_size(), R, F, H, W, (ctypes.c_int * max(len(flat), 1))(*flat),
+                                                 len(flat) // 2, table, hr, wr, _stream()), "wan_region_crop_track")
+    return out
+
+
+@_on_tensor_device
+def region_restore_track(source: torch.Tensor, state: torch.Tensor, origins, frames, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``region_restore_frames`` with a box that moves: ``origins`` integer [cc, 2] on the HOST = the corner of source frame f's box
+    (grounding g uses origins[g]).  Outside its frame's box, and outside the range ``frames`` = (t0, n), the target is the source bit
+    for bit.  ONE launch (``wan_region_restore_track``); at most 512 source frames."""
+    if not source.is_cuda or not state.is_cuda:
+        raise RuntimeError(f"region_restore_track: tensors are on {source.device} and {state.device}; the HIP path has no CPU fallback")
+    if source.element_size() not in (1, 2, 4):
+        raise ValueError(f"region_restore_track: dtype {source.dtype} not supported (elements of 1, 2 or 4 bytes)")
+    if source.dim() != 5 or state.dim() != 5 or source.shape[:2] != state.shape[:2] or source.dtype != state.dtype \
+            or source.device != state.device:
+        raise ValueError(f"region_restore_track: source {source.dtype} {tuple(source.shape)} on {source.device} and state {state.dtype} "
+                         f"{tuple(state.shape)} on {state.device}: expected [B, C, cc, H, W] and [B, C, n + G + n, hr, wr] of one dtype")
+    source, state = source.contiguous(), state.contiguous()
+    B, C, cc, H, W = (int(v) for v in source.shape)
+    Fr, hr, wr = (int(v) for v in state.shape[2:])
+    if len(frames) != 2:
+        raise ValueError(f"region_restore_track: frames = (t0, n) in latent frames, got {frames!r}")
+    t0, n = int(frames[0]), int(frames[1])
+    G = Fr - 2 * n
+    table, rows = _track_origins(origins, "region_restore_track")
+    if rows != cc:
+        raise ValueError(f"region_restore_track: {rows} rows of origins for {cc} source frames (one each)")
+    out = _region_out(out, (B, C, max(2 * cc + G, 0), H, W), source, "region_restore_track.out")
+    _lib.check(_lib.load().wan_region_restore_track(_p(out), _p(source), _p(state), source.element_size(), B, C, cc, G, H, W, t0, n,
+                                                    table, hr, wr, _stream()), "wan_region_restore_track")
+    return out
+
+
 def _avail(t: torch.Tensor) -> int:
     """Elements from t's first element to the end of its storage."""
     return t.untyped_storage().nbytes() // t.element_size() - t.storage_offset()

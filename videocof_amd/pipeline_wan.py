@@ -47,6 +47,7 @@ class WanPipelineOutput:
     edit_region: Optional[tuple] = None             # extension: (y, x, h, w) in pixels, what the loop ran on (edit_region=True); None when off
     edit_region_time: Optional[tuple] = None        # extension: (first pixel frame, pixel frame count) of it (edit_region_time_margin); None when off
     edit_region_vae: Optional[tuple] = None         # extension: (y, x, h, w) in pixels, the box the VAE ran on (edit_region_vae_halo); None when off
+    edit_region_track: Optional[tuple] = None       # extension: ((h, w), ((y_f, x_f), ...)) in pixels, the box of every latent frame of the source segment (edit_region_follow; edit_region then encloses them all); None when off
 
 
 def _require_source(has_source: bool, why: str) -> None:
@@ -403,7 +404,16 @@ class WanPipeline:
             # convolutions deep and its mid-block attention is global over the frame it sees, so no finite halo is exact and every
             # value is a guess.  Opt-in and lossy (a VAE that sees a crop is as lossy as a DiT that sees one); no quality claim.
             edit_region_vae_halo=switches.pop("edit_region_vae_halo", None), edit_region_stitch_feather=switches.pop("edit_region_stitch_feather", 0),
-            vae_halo=None, stitch_feather=0)             # set below: the halo in latent cells (None: the VAE sees whole frames) and the feather, checked
+            vae_halo=None, stitch_feather=0,             # set below: the halo in latent cells (None: the VAE sees whole frames) and the feather, checked
+            # `edit_region_follow=None` (PIXEL frames, a multiple of 4): with `edit_region=True`, the rectangle keeps ONE size and takes a
+            # corner per latent frame, so a moving object's box stays the object's size, not its path's (edit_region.region_track_plan).
+            # The value is the only smoothing: frame f's box covers the mask of the frames within this many pixel frames of it; 0 follows
+            # every frame on its own, a value of the clip's length or more is `edit_region=True` alone.  Source frame f, target frame f
+            # and the weights of frame f are cropped at the same corner (wan_region_crop_track / wan_region_restore_track), so the pin
+            # to the source stays exact; the model sees a stabilised crop whose background slides.  Not with `edit_region_vae_halo`.
+            # None: one rectangle for the clip.  There is no default: any value is a guess.  Opt-in and lossy; no quality claim.
+            edit_region_follow=switches.pop("edit_region_follow", None),
+            region_follow=None)                          # set below: the span in latent frames, checked (None: the box does not move)
         if switches:
             raise TypeError(f"__call__() got an unexpected keyword argument {next(iter(switches))!r}")
         if o.edit_mask is not None:
@@ -433,6 +443,16 @@ class WanPipeline:
             if not o.edit_region:
                 raise ValueError("edit_region_time_margin extends edit_region=True (the frame range is cropped with the rectangle), and "
                                  "this call does not set it")
+        if o.edit_region_follow is not None:
+            from .edit_region import region_follow_frames
+            o.region_follow = region_follow_frames(o.edit_region_follow)
+            if not o.edit_region:
+                raise ValueError("edit_region_follow extends edit_region=True (the rectangle takes a corner per latent frame), and this "
+                                 "call does not set it")
+            if o.edit_region_vae_halo is not None:
+                raise ValueError("edit_region_follow with edit_region_vae_halo: a pixel box that moves from frame to frame inside a "
+                                 "causal VAE (whose every frame leans on the features of the frames before it, at the same pixels) is "
+                                 "a different problem; the VAE box is one rectangle for the clip")
         from .edit_region import region_stitch_feather
         o.stitch_feather = region_stitch_feather(o.edit_region_stitch_feather)
         if o.edit_region_vae_halo is not None:
@@ -516,15 +536,16 @@ class WanPipeline:
 
     def _plan_region(self, o, weights, hl, wl, tile_cells, cc, G):
         """The bounds of the non-zero weights (wan_mask_bounds), their copy to the host -- the ONE synchronisation of edit_region -- and
-        the rules on it: (RegionPlan, TimeRegion or None without `edit_region_time_margin`)."""
+        the rules on it: (RegionPlan -- or, with `edit_region_follow`, the TrackPlan from the same host copy --, TimeRegion or None
+        without `edit_region_time_margin`)."""
         from . import ops
-        from .edit_region import region_plan, region_time_plan
+        from .edit_region import region_plan, region_time_plan, region_track_plan
         if G > cc:
             raise ValueError(f"edit_region: {G} grounding frames for {cc} source frames; outside the region grounding frame g is "
                              "source frame g, so at most as many")
         bounds = ops.mask_bounds(weights).cpu()
-        plan = region_plan(bounds, (hl, wl), o.region_margin, None if tile_cells is None else tile_cells[0],
-                           int(self.transformer.config.patch_size[1]))
+        rule = (hl, wl), o.region_margin, None if tile_cells is None else tile_cells[0], int(self.transformer.config.patch_size[1])
+        plan = region_plan(bounds, *rule) if o.region_follow is None else region_track_plan(bounds, *rule, span=o.region_follow)
         return plan, None if o.region_time_margin is None else region_time_plan(bounds, cc, o.region_time_margin, G)
 
     def _crop_to_region(self, o, latents, weights, tile_cells, cc, G):
@@ -533,6 +554,8 @@ class WanPipeline:
         with the tile of `spatial_window` if that is given), and the loop state and the weights cropped to it (wan_region_crop).
         With `edit_region_time_margin` the frame range (edit_region.region_time_plan) comes from the same host copy of the bounds, and
         state and weights are cropped in frames and cells at once (wan_region_crop_frames, still one launch each).
+        With `edit_region_follow` the plan is a TrackPlan and both are cropped by ONE table of corners (wan_region_crop_track): the
+        weights by the source frames' table, the state by the same table laid out as [source | grounding | target].
         Returns (latents, weights, region, the source frames of the loop's clip): `region` is None with the option off -- nothing is
         launched then -- or (RegionPlan, the whole source block to restore into; None where nothing was cropped, the TimeRegion; None
         without a time crop)."""
@@ -541,6 +564,14 @@ class WanPipeline:
         from . import ops
         hl, wl = int(latents.shape[3]), int(latents.shape[4])
         plan, span = self._plan_region(o, weights, hl, wl, tile_cells, cc, G)
+        if o.region_follow is not None:
+            t0, n = (0, cc) if span is None else span
+            if (plan.h, plan.w, n) == (hl, wl, cc):
+                return latents, weights, (plan, None, span), cc
+            table = np.concatenate([plan.origins, plan.origins[:G], plan.origins])
+            runs = [(0, 2 * cc + G)] if span is None else [(t0, n)] + ([(cc, G)] if G else []) + [(cc + G + t0, n)]
+            return (ops.region_crop_track(latents.contiguous(), runs, table, (plan.h, plan.w)),
+                    ops.region_crop_track(weights, [(t0, n)], plan.origins, (plan.h, plan.w)), (plan, latents[:, :, :cc], span), n)
         if span is not None:
             if (plan.h, plan.w, span.n) == (hl, wl, cc):
                 return latents, weights, (plan, None, span), cc
@@ -555,12 +586,15 @@ class WanPipeline:
     @staticmethod
     def _restore_region(latents, region, box=None):
         """Edit region, the second stage: the loop's final state on the region put back into the source latents (wan_region_restore, or
-        wan_region_restore_frames after a time crop) -- outside the region the grounding and target frames are the source's bits.
+        wan_region_restore_frames after a time crop, wan_region_restore_track where the box follows the mask) -- outside the region the grounding and target frames are the source's bits.
         `box` (`edit_region_vae_halo`): the source latents are the VAE box's, and the region's corner counts from the box's."""
         plan, source, span = region
         if source is None:
             return latents
         from . import ops
+        if hasattr(plan, "origins"):                     # `edit_region_follow`: a TrackPlan (never with a VAE box)
+            return ops.region_restore_track(source.to(latents.dtype), latents, plan.origins,
+                                            (0, source.shape[2]) if span is None else span)
         origin = (plan.y0, plan.x0) if box is None else (plan.y0 - box.y0, plan.x0 - box.x0)
         if span is not None:
             return ops.region_restore_frames(source.to(latents.dtype), latents, origin, span)
@@ -995,8 +1029,11 @@ class WanPipeline:
         videos, ground, edit, compared = self._decode_outputs(latents, output_type, cot, condition_count, ground_latent_count,
                                                               opt.compare_source, return_dict, stitch)
         self._stage("vae_decode", t_stage)
+        tracked = region is not None and opt.region_follow is not None
         return WanPipelineOutput(videos=videos, ground_videos=ground, edit_videos=edit, latents=latents, compare_videos=compared,
-                                 edit_region=None if region is None else region[0].pixels(
+                                 edit_region=None if region is None else (region[0].enclosing() if tracked else region[0]).pixels(
+                                     getattr(getattr(self.vae, "config", None), "spatial_compression_ratio", 8)),
+                                 edit_region_track=None if not tracked else region[0].pixels(
                                      getattr(getattr(self.vae, "config", None), "spatial_compression_ratio", 8)),
                                  edit_region_time=None if region is None or region[2] is None else region[2].pixels(ratio),
                                  edit_region_vae=None if vae_box is None else vae_box.pixels(
