@@ -791,6 +791,44 @@ wan_status_t wan_region_crop_track(void* out, const void* in, int elem_bytes, in
 wan_status_t wan_region_restore_track(void* out, const void* source, const void* region, int elem_bytes, int B, int C, int cc, int G,
                                       int H, int W, int t0, int n, const int* origins, int hr, int wr, void* stream);
 
+/* a17h  Edit region, a mask of separate objects split into boxes (`edit_region_split`): at most WAN_REGION_SPLIT_MAX
+ *      bands along ONE axis, a box of ONE size hr x wr per band, the boxes run as samples of one forward.
+ *      videocof_amd/edit_region.py states all three in plain torch (reference_mask_spans, reference_region_crop_split,
+ *      reference_region_restore_split) and the kernels equal them bit for bit.
+ *      replaces: nothing in the reference, whose loop runs on whole frames.
+ *      wan_mask_spans: weights uint8 [Bm, Fs, h, w] -> spans int16 [Fs, h + w, 2].  Per latent frame the first h pairs are, per row,
+ *          the inclusive (x_lo, x_hi) of the non-zero weights over all Bm samples, (w, -1) for a row without one; the next w pairs
+ *          are, per column, (y_lo, y_hi), (h, -1) for a column without one.  A frame's bounds (wan_mask_bounds) are the min and max of
+ *          its spans, so a call that splits copies these 4 (h + w) Fs bytes to the host INSTEAD of the bounds.  One workgroup per
+ *          latent frame; a pair is one 32-bit word, every word written exactly once: no atomics, no init pass.  The reads follow
+ *          wan_mask_bounds' access unit.  WAN_ERR_INVALID: what wan_mask_bounds rejects (the spans' address a multiple of 4), h or w
+ *          of 32768 or more.
+ *      The boxes: `origins` int32 [K, 2] = (y0_k, x0_k) and `cuts` int32 [K + 1], read on the HOST like `runs`; `axis` 1: the cuts are
+ *          columns, 0: rows.  Band k OWNS [cuts[k], cuts[k + 1]) on the cut axis and everything on the other one; boxes may overlap and
+ *          may reach past what their band owns.  Everything is validated before anything is enqueued, then the table (a corner and an
+ *          owned interval per box) travels BY VALUE in the kernel's arguments: no device allocation, no copy, no synchronisation, ONE
+ *          kernel per call.  The access unit is a17f's over W, wr, every x0_k, the base addresses and, for a column cut, every cut
+ *          column: no unit straddles a box's edge or a cut.
+ *      wan_region_crop_split: wan_region_crop_frames for every box at once: in [R, F, H, W] -> out [K, R, Fo, hr, wr], box-major, bits
+ *          unchanged.  With clip != 0 every element outside what band k owns is written as ZERO in box k: the form for the mask's
+ *          weights, which pins the cells of another band's object to the source inside this box.
+ *      wan_region_restore_split: source [B, C, cc, H, W], region [K B, C, n + G + n, hr, wr] (box-major) -> out [B, C, cc + G + cc, H, W]:
+ *              source frame f            source[f]
+ *              grounding frame g         box k's region[n + g] where the cell lies inside box k AND inside what band k owns, else source[g]
+ *              target frame f            box k's region[n + G + f - t0] where t0 <= f < t0 + n and the same holds, else source[f]
+ *          Every output unit is written once, from one of K + 1 places.
+ *      WAN_ERR_INVALID: whatever the frames forms reject, null `origins` or `cuts`, K outside 1..WAN_REGION_SPLIT_MAX, another axis, a
+ *      box that does not lie inside the frame, cuts that do not ascend strictly from 0 to the axis' extent.
+ *      K = 1 gives the bytes of the frames forms. */
+#define WAN_REGION_SPLIT_MAX 8
+wan_status_t wan_mask_spans(const void* weights_u8, void* spans_i16, int Bm, int Fs, int h, int w, void* stream);
+wan_status_t wan_region_crop_split(void* out, const void* in, int elem_bytes, int64_t R, int F, int H, int W, const int* runs,
+                                   int n_runs, const int* origins, const int* cuts, int K, int axis, int clip, int hr, int wr,
+                                   void* stream);
+wan_status_t wan_region_restore_split(void* out, const void* source, const void* region, int elem_bytes, int B, int C, int cc, int G,
+                                      int H, int W, int t0, int n, const int* origins, const int* cuts, int K, int axis, int hr,
+                                      int wr, void* stream);
+
 /* ===========================================================================
  * WanVAE (videox_fun/models/wan_vae.py).  Activations are CHANNELS-LAST bf16 [T, H, W, C].
  * ------------------------------------------------------------------------- */

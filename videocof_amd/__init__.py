@@ -14,7 +14,7 @@ Host side mirrors the reference's interface for this path only:
     videocof_amd.dist                       <- videox_fun/dist/{fuser,wan_xfuser}.py (Ulysses on RCCL)
     videocof_amd.video_io                   <- fast_infer.py load_video_frames + videox_fun/utils/utils.py save_videos_grid's byte conversion
     videocof_amd.windows                    (no counterpart) temporal and spatial context windows: clips longer / frames larger than trained, opt-in
-    videocof_amd.edit_region                (no counterpart) edit region: the denoise loop only on the rectangle (and, on request, the frame range; on request a rectangle that follows the mask from frame to frame) the edit mask touches, opt-in and lossy
+    videocof_amd.edit_region                (no counterpart) edit region: the denoise loop only on the rectangle (and, on request, the frame range; on request a rectangle that follows the mask from frame to frame, or one box per separate object) the edit mask touches, opt-in and lossy
     videocof_amd.local_attention            (no counterpart) local self-attention: key tiles listed per query block, opt-in and lossy
 
 Device arithmetic lives in ``libwan_hip.so`` (csrc/, C ABI in include/wan_hip.h).
@@ -46,6 +46,8 @@ from .edit_region import (TimeRegion, region_time_plan, region_time_margin_frame
 from .edit_region import region_vae_box, reference_frames_box_to_video, reference_video_box_stitch  # noqa: F401
 from .edit_region import (TrackPlan, region_track_plan, region_follow_frames, reference_region_crop_track,  # noqa: F401
                           reference_region_restore_track)
+from .edit_region import (SplitPlan, region_split_plan, reference_mask_spans, reference_region_crop_split,  # noqa: F401
+                          reference_region_restore_split)
 from .local_attention import LocalAttentionPlan, local_attention_plan, reference_local_mask, reference_sparse_attention  # noqa: F401
 
 __version__ = "0.1.0"

@@ -247,6 +247,11 @@ SIGNATURES = {
     "wan_region_crop_track": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, POINTER(c_int), c_int, POINTER(c_int),
                                       c_int, c_int, c_void_p]),
     "wan_region_restore_track": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 9 + [POINTER(c_int), c_int, c_int, c_void_p]),
+    "wan_mask_spans": (c_int, [c_void_p, c_void_p] + [c_int] * 4 + [c_void_p]),
+    "wan_region_crop_split": (c_int, [c_void_p, c_void_p, c_int, c_int64, c_int, c_int, c_int, POINTER(c_int), c_int, POINTER(c_int),
+                                      POINTER(c_int)] + [c_int] * 5 + [c_void_p]),
+    "wan_region_restore_split": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int] * 9 + [POINTER(c_int), POINTER(c_int)] + [c_int] * 4
+                                 + [c_void_p]),
     "wan_gemm_bf16_batched": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int64, c_int64,
                                       c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "wan_embedding_rows": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p]),

@@ -23,6 +23,12 @@ from the same per-frame bounds (a sliding union over ``span`` latent frames is t
 / ``reference_region_restore_track`` state what ``wan_region_crop_track`` / ``wan_region_restore_track`` compute.  Source frame f,
 target frame f and the weights of frame f are cropped at the same corner, so the loop's pin to the source stays exact; the model sees
 a stabilised crop whose background slides: opt-in, lossy, no quality claim.
+
+With ``edit_region_split`` a mask of separate objects is split into at most K bands along ONE axis, every band gets a box of ONE common
+size, and the boxes run as samples of the ordinary loop: ``reference_mask_spans`` states what ``wan_mask_spans`` brings to the host (per
+row and per column the extent of the non-zero weights), ``region_split_plan`` fixes the boxes and the part of the frame each band owns,
+and ``reference_region_crop_split`` / ``reference_region_restore_split`` state what ``wan_region_crop_split`` /
+``wan_region_restore_split`` compute.  A box sees only itself; opt-in, lossy, no quality claim.
 """
 from __future__ import annotations
 
@@ -35,10 +41,13 @@ __all__ = ["RegionPlan", "region_plan", "region_margin_cells", "reference_mask_b
            "reference_region_restore", "TimeRegion", "region_time_plan", "region_time_margin_frames", "reference_region_crop_frames",
            "reference_region_restore_frames", "region_vae_box", "region_vae_halo_cells", "region_stitch_feather",
            "reference_frames_box_to_video", "reference_video_box_stitch", "stitch_weights", "TrackPlan", "region_track_plan",
-           "region_follow_frames", "reference_region_crop_track", "reference_region_restore_track", "REGION_TRACK_MAX_FRAMES"]
+           "region_follow_frames", "reference_region_crop_track", "reference_region_restore_track", "REGION_TRACK_MAX_FRAMES",
+           "SplitPlan", "region_split_plan", "region_split_count", "spans_bounds", "reference_mask_spans",
+           "reference_region_crop_split", "reference_region_restore_split", "REGION_SPLIT_MAX"]
 
 REGION_MARGIN_UNIT = 16         # pixels: the VAE's spatial ratio 8 times the patch 2 -- a margin keeps the region on the patch grid
 REGION_TRACK_MAX_FRAMES = 512   # WAN_REGION_TRACK_MAX_FRAMES: the frames a table of corners may have (it travels in the kernel's arguments)
+REGION_SPLIT_MAX = 8            # WAN_REGION_SPLIT_MAX: the boxes a split may have (their table travels in the kernel's arguments)
 
 
 class RegionPlan(NamedTuple):
@@ -205,6 +214,140 @@ def region_follow_frames(follow, ratio: int = 4) -> int:
     if follow < 0 or follow % ratio:
         raise ValueError(f"edit_region_follow={follow} must be a non-negative multiple of {ratio} pixel frames (the VAE's temporal ratio)")
     return int(follow) // ratio
+
+
+class SplitPlan(NamedTuple):
+    """The boxes of a mask of separate objects, in LATENT cells: ``axis`` = the axis the frame is cut along (1: columns, the cuts are
+    column indices; 0: rows), one size (h, w) for all boxes, ``origins`` int32 [K', 2] = (y0_k, x0_k), and ``cuts`` int32 [K' + 1]:
+    band k OWNS [cuts[k], cuts[k + 1]) on the cut axis and everything on the other one."""
+    axis: int
+    h: int
+    w: int
+    origins: np.ndarray
+    cuts: np.ndarray
+
+    def pixels(self, ratio: int = 8):
+        """((y, x, h, w), ...) in pixels, one per box."""
+        return tuple((int(y) * ratio, int(x) * ratio, self.h * ratio, self.w * ratio) for y, x in self.origins)
+
+    def enclosing(self) -> RegionPlan:
+        """The rectangle that encloses every box."""
+        y0, x0 = (int(v) for v in self.origins.min(axis=0))
+        y1, x1 = (int(v) for v in self.origins.max(axis=0))
+        return RegionPlan(y0, x0, y1 - y0 + self.h, x1 - x0 + self.w)
+
+
+def _spans_array(spans, H: int, W: int, who: str) -> np.ndarray:
+    s = np.asarray(spans.cpu() if torch.is_tensor(spans) else spans)
+    if s.ndim != 3 or s.shape[1:] != (H + W, 2) or s.dtype.kind not in "iu" or s.shape[0] < 1:
+        raise ValueError(f"{who}: spans = integer [Fs, {H} + {W}, 2] for a frame of {H} x {W} cells (mask_spans), got {s.dtype} {s.shape}")
+    return s.astype(np.int64)
+
+
+def spans_bounds(spans, frame_cells) -> np.ndarray:
+    """The per-frame bounds int32 [Fs, 4] = (y_lo, y_hi, x_lo, x_hi) of ``mask_bounds`` out of the spans of ``mask_spans``: a frame's
+    bounds are the min and max of its spans; (h, -1, w, -1) for a frame without a non-zero weight."""
+    H, W = int(frame_cells[0]), int(frame_cells[1])
+    s = _spans_array(spans, H, W, "spans_bounds")
+    rows, cols = s[:, :H], s[:, H:]
+    return np.stack([cols[:, :, 0].min(axis=1), cols[:, :, 1].max(axis=1), rows[:, :, 0].min(axis=1), rows[:, :, 1].max(axis=1)],
+                    axis=1).astype(np.int32)
+
+
+def _split_axis(lo, hi, F: int, m: int, T: Optional[int], p: int) -> Tuple[np.ndarray, int]:
+    """One axis of the rule for every band at once: (starts int64 [bands], size).  ``_axis`` with want = the largest band's."""
+    lo_a, hi_a = lo // p * p, (hi // p + 1) * p
+    want_b = np.minimum(F, hi_a - lo_a + 2 * m)
+    want = int(want_b.max())
+    size = min(T, F) if T is not None and want <= T else want
+    start = lo_a - m - ((size - want_b) // (2 * p)) * p
+    return np.clip(start, 0, F - size), size
+
+
+def _split_candidate(lo, hi, F: int, keep, p: int):
+    """The bands of one axis with the gaps ``keep`` kept and every other one merged across.  ``lo``, ``hi``: int64 [F], per cell of the
+    cut axis the union span on the OTHER axis (hi < lo: the cell is empty).  Returns (cut-axis bounds int64 [k, 2], other-axis bounds
+    int64 [k, 2], cuts int64 [k + 1]) -- or the runs of occupied patches and the gaps between them where ``keep`` is None."""
+    on = hi >= lo
+    patches = -(-F // p)
+    occupied = np.array([on[i * p:(i + 1) * p].any() for i in range(patches)])
+    edges = np.flatnonzero(np.diff(np.concatenate([[False], occupied, [False]]).astype(np.int8)))
+    first, last = edges[0::2], edges[1::2] - 1               # the bands: runs [first_i, last_i] of occupied patches
+    if keep is None:
+        return first, last
+    keep = sorted(keep)                                      # gap g lies between band g and band g + 1
+    a = np.array([0] + [g + 1 for g in keep])                # the first band of every merged band
+    b = np.array(keep + [len(first) - 1])                    # and its last
+    cut_b, other_b = [], []
+    for i, j in zip(a, b):
+        cells = np.arange(first[i] * p, min((last[j] + 1) * p, F))
+        cells = cells[on[cells]]
+        cut_b.append((cells[0], cells[-1]))
+        other_b.append((lo[cells].min(), hi[cells].max()))
+    cuts = [0] + [p * ((last[j] + 1 + first[j + 1]) // 2) for j in b[:-1]] + [F]
+    return np.array(cut_b, np.int64), np.array(other_b, np.int64), np.array(cuts, np.int64)
+
+
+def region_split_plan(spans, frame_cells, margin_cells, tile_cells=None, patch: int = 2, max_regions: int = 2):
+    """The boxes of a mask of SEPARATE objects, from the ``spans`` int16 [Fs, h + w, 2] of ``mask_spans``: at most ``max_regions`` (2 to 8)
+    bands along ONE axis, columns or rows, and a box of ONE common size for every band.  The other arguments are ``region_plan``'s.
+
+        1. The union over frames is taken: per row the span of its non-zero columns, per column the span of its non-zero rows.
+        2. Per axis, patch i is occupied if any cell i p .. i p + p - 1 is; runs of occupied patches are the bands, runs of empty ones
+           between them the gaps.
+        3. For k = 1 .. min(max_regions, bands) the k - 1 widest gaps are kept (of equal gaps the earlier one) and the others merged
+           across.
+        4. A band's bounds on the cut axis are its first and last occupied cell; on the other axis the min and max of the spans of its
+           rows or columns -- exact for a cut along one axis.
+        5. Per axis, with lo_b, hi_b a band's bounds and F, p, m, T as in ``region_plan``:
+               lo'_b = lo_b // p * p,  hi'_b = (hi_b // p + 1) * p,  want_b = min(F, hi'_b - lo'_b + 2 m),  want = max over b of want_b
+               size    = min(T, F)  if T is given and want <= T  else  want
+               start_b = clamp(lo'_b - m - ((size - want_b) // (2 p)) * p, 0, F - size)
+        6. A candidate costs k * h * w cells; the cheapest over (axis, k) is taken, ties go to the smaller k, then to columns.
+        7. Between band i - 1 and band i the cut is p * ((last patch of i - 1 + 1 + first patch of i) // 2): a patch boundary inside
+           the gap.  cuts[0] = 0, cuts[K'] = F.  Band i owns [cuts[i], cuts[i + 1]) on the cut axis, everything on the other.
+
+    k = 1 is the same for both axes and IS ``region_plan`` of the bounds: a mask of one object, or one whose split does not pay, returns
+    that ``RegionPlan``; otherwise a ``SplitPlan``.  Boxes may overlap and may reach past what their band owns (context); all of a
+    band's mask lies inside both its box and what it owns.  Keeping the widest gaps is a rule, not a search: another choice of gaps
+    can be cheaper.  An empty mask raises ``ValueError``."""
+    who = "region_split_plan"
+    _, p, ((H, W), (my, mx), (Ty, Tx)) = _plan_args(who, np.zeros((0, 4)), frame_cells, margin_cells, tile_cells, patch)
+    K = region_split_count(max_regions, who + ": max_regions")
+    s = _spans_array(spans, H, W, who)
+    lo, hi = s[:, :, 0].min(axis=0), s[:, :, 1].max(axis=0)                    # the union over frames
+    if not (hi >= lo).any():
+        raise ValueError("edit_mask is empty (every latent weight is zero): there is no region to run the loop on")
+    if lo[:H][hi[:H] >= lo[:H]].min() < 0 or hi[:H].max() >= W or lo[H:][hi[H:] >= lo[H:]].min() < 0 or hi[H:].max() >= H:
+        raise ValueError(f"{who}: the spans leave a frame of {H} x {W} cells")
+    single = region_plan(spans_bounds(s, (H, W)), (H, W), (my, mx), tile_cells, p)
+    best, best_cost = single, single.h * single.w
+    # (axis 1: the cut runs along the columns, whose spans are rows; axis 0: along the rows, whose spans are columns)
+    axes = {1: (lo[H:], hi[H:], W, mx, Tx, H, my, Ty), 0: (lo[:H], hi[:H], H, my, Ty, W, mx, Tx)}
+    gaps = {}
+    for axis, (alo, ahi, F, _, _, _, _, _) in axes.items():
+        first, last = _split_candidate(alo, ahi, F, None, p)
+        width = first[1:] - last[:-1] - 1
+        gaps[axis] = sorted(range(len(width)), key=lambda g: (-width[g], g))       # widest first, of equal gaps the earlier one
+    for k in range(2, K + 1):
+        for axis in (1, 0):
+            alo, ahi, F, m, T, Fo, mo, To = axes[axis]
+            if k - 1 > len(gaps[axis]):
+                continue
+            cut_b, other_b, cuts = _split_candidate(alo, ahi, F, gaps[axis][:k - 1], p)
+            starts, size = _split_axis(cut_b[:, 0], cut_b[:, 1], F, m, T, p)
+            ostarts, osize = _split_axis(other_b[:, 0], other_b[:, 1], Fo, mo, To, p)
+            if k * size * osize < best_cost:
+                (ys, h), (xs, w) = ((ostarts, osize), (starts, size)) if axis == 1 else ((starts, size), (ostarts, osize))
+                best, best_cost = SplitPlan(axis, h, w, np.stack([ys, xs], axis=1).astype(np.int32), cuts.astype(np.int32)), k * size * osize
+    return best
+
+
+def region_split_count(split, name: str = "edit_region_split") -> int:
+    """The pipeline's ``edit_region_split``: an integer count of boxes from 2 to 8."""
+    if isinstance(split, bool) or not isinstance(split, (int, np.integer)) or not 2 <= split <= REGION_SPLIT_MAX:
+        raise ValueError(f"{name}={split!r}: an integer from 2 to {REGION_SPLIT_MAX}, the most boxes the mask is split into")
+    return int(split)
 
 
 class TimeRegion(NamedTuple):
@@ -452,6 +595,105 @@ def reference_region_restore_track(source: torch.Tensor, state: torch.Tensor, or
     for k in range(n):
         y0, x0 = o[t0 + k]
         out[:, :, cc + G + t0 + k, y0:y0 + hr, x0:x0 + wr] = state[:, :, n + G + k]
+    return out
+
+
+def reference_mask_spans(weights: torch.Tensor) -> torch.Tensor:
+    """``wan_mask_spans`` in torch: weights uint8 [Bm, Fs, h, w] -> int16 [Fs, h + w, 2].  Per latent frame the first h pairs are, per
+    row, the inclusive (x_lo, x_hi) of the non-zero weights over all samples, (w, -1) for a row without one; the next w pairs are, per
+    column, (y_lo, y_hi), (h, -1) for a column without one."""
+    if weights.dim() != 4 or weights.dtype != torch.uint8:
+        raise ValueError(f"reference_mask_spans: expected uint8 [Bm, Fs, h, w], got {weights.dtype} {tuple(weights.shape)}")
+    _, Fs, h, w = weights.shape
+    if h >= 32768 or w >= 32768:
+        raise ValueError(f"reference_mask_spans: a frame of {h} x {w} cells (each below 32768: the spans are int16)")
+    on = (weights != 0).any(dim=0).cpu()
+    out = torch.empty((Fs, h + w, 2), dtype=torch.int16)
+    for f in range(Fs):
+        for lines, start, empty in ((on[f], 0, w), (on[f].t(), h, h)):
+            for i, line in enumerate(lines):
+                at = line.nonzero().flatten()
+                out[f, start + i] = torch.tensor([int(at[0]), int(at[-1])] if at.numel() else [empty, -1], dtype=torch.int16)
+    return out
+
+
+def _split_table(origins, cuts, axis, size, H: int, W: int, who: str):
+    """The boxes of a split, checked: (origins int64 [K, 2], cuts int64 [K + 1], axis)."""
+    o = np.asarray(origins.cpu() if torch.is_tensor(origins) else origins)
+    c = np.asarray(cuts.cpu() if torch.is_tensor(cuts) else cuts)
+    if o.ndim != 2 or o.shape[1] != 2 or o.dtype.kind not in "iu" or not 1 <= o.shape[0] <= REGION_SPLIT_MAX:
+        raise ValueError(f"{who}: origins = integer [K, 2] pairs (y0, x0) in cells, 1 to {REGION_SPLIT_MAX} boxes, got {o.dtype} {o.shape}")
+    if isinstance(axis, bool) or axis not in (0, 1):
+        raise ValueError(f"{who}: axis={axis!r} (1: the cuts are columns, 0: rows)")
+    F = (H, W)[axis]
+    if c.ndim != 1 or c.dtype.kind not in "iu" or c.shape[0] != o.shape[0] + 1 or c[0] != 0 or c[-1] != F or (np.diff(c) < 1).any():
+        raise ValueError(f"{who}: cuts = {o.shape[0] + 1} ascending integers from 0 to {F}, got {c.tolist() if c.ndim == 1 else c.shape}")
+    if len(size) != 2:
+        raise ValueError(f"{who}: size = (h, w) in cells, got {size!r}")
+    o = o.astype(np.int64)
+    for k, (y0, x0) in enumerate(o):
+        _box((y0, x0, size[0], size[1]), H, W, f"{who}: box {k}")
+    return o, c.astype(np.int64), int(axis)
+
+
+def _owned(k: int, cuts, axis: int, H: int, W: int) -> torch.Tensor:
+    """bool [H, W]: the cells band k owns."""
+    own = torch.zeros(H, W, dtype=torch.bool)
+    if axis == 1:
+        own[:, int(cuts[k]):int(cuts[k + 1])] = True
+    else:
+        own[int(cuts[k]):int(cuts[k + 1])] = True
+    return own
+
+
+def reference_region_crop_split(x: torch.Tensor, runs, origins, cuts, axis: int, size, clip: bool = False) -> torch.Tensor:
+    """``wan_region_crop_split`` in torch: ``x`` [R..., F, H, W]; ``runs`` as in ``reference_region_crop_frames``; ``origins`` integer
+    [K, 2], ``cuts`` integer [K + 1] and ``axis`` as in ``SplitPlan``; ``size`` = (h, w), one for all -> [K, R..., Fo, h, w], box-major:
+    box k of the listed frames.  With ``clip`` everything outside what band k owns is ZERO in box k (the weights: there the loop pins
+    the cells of another band's object to the source)."""
+    who = "reference_region_crop_split"
+    if x.dim() < 3:
+        raise ValueError(f"{who}: expected [..., F, H, W], got {tuple(x.shape)}")
+    runs = _runs(runs, x.shape[-3], who)
+    H, W = int(x.shape[-2]), int(x.shape[-1])
+    o, c, axis = _split_table(origins, cuts, axis, size, H, W, who)
+    hr, wr = int(size[0]), int(size[1])
+    out = []
+    for k, (y0, x0) in enumerate(o):
+        src = torch.where(_owned(k, c, axis, H, W), x, torch.zeros((), dtype=x.dtype)) if clip else x
+        out.append(torch.cat([src[..., a:a + n, y0:y0 + hr, x0:x0 + wr] for a, n in runs], dim=-3))
+    return torch.stack(out).contiguous()
+
+
+def reference_region_restore_split(source: torch.Tensor, state: torch.Tensor, origins, cuts, axis: int, frames) -> torch.Tensor:
+    """``wan_region_restore_split`` in torch: ``source`` [B, C, cc, H, W] and ``state`` [K B, C, n + G + n, hr, wr], box-major, the loop's
+    final state on the source frames ``frames`` = (t0, n) and the K boxes of ``origins`` / ``cuts`` / ``axis`` -> [B, C, cc + G + cc, H,
+    W]: source frames are the source; a grounding or target cell takes box k's value where it lies inside box k AND inside what band k
+    owns (the target only in frames t0 <= f < t0 + n); everywhere else it is the source, bit for bit."""
+    who = "reference_region_restore_split"
+    if source.dim() != 5 or state.dim() != 5 or source.shape[1] != state.shape[1] or source.dtype != state.dtype:
+        raise ValueError(f"{who}: source {source.dtype} {tuple(source.shape)} and state {state.dtype} "
+                         f"{tuple(state.shape)}: expected [B, C, cc, H, W] and [K B, C, n + G + n, hr, wr] of one dtype")
+    if len(frames) != 2:
+        raise ValueError(f"{who}: frames = (t0, n) in latent frames, got {frames!r}")
+    t0, n = int(frames[0]), int(frames[1])
+    B, _, cc, H, W = (int(v) for v in source.shape)
+    G = state.shape[2] - 2 * n
+    if t0 < 0 or n < 1 or t0 + n > cc:
+        raise ValueError(f"{who}: the frames [{t0}, {t0} + {n}) do not lie inside the {cc} source frames")
+    if not 0 <= G <= cc:
+        raise ValueError(f"{who}: {state.shape[2]} state frames for a range of {n}: G={G} grounding frames (0 <= G <= cc = {cc})")
+    hr, wr = int(state.shape[3]), int(state.shape[4])
+    o, c, axis = _split_table(origins, cuts, axis, (hr, wr), H, W, who)
+    if state.shape[0] != len(o) * B:
+        raise ValueError(f"{who}: {state.shape[0]} state samples for {len(o)} boxes of {B} samples")
+    out = torch.cat([source, source[:, :, :G], source], dim=2)
+    for k, (y0, x0) in enumerate(o):
+        take = _owned(k, c, axis, H, W)[y0:y0 + hr, x0:x0 + wr]
+        box = state[k * B:(k + 1) * B]
+        for dst, src in ((slice(cc, cc + G), slice(n, n + G)), (slice(cc + G + t0, cc + G + t0 + n), slice(n + G, 2 * n + G))):
+            view = out[:, :, dst, y0:y0 + hr, x0:x0 + wr]
+            view[..., take] = box[:, :, src][..., take]
     return out
 
 

@@ -1923,6 +1923,104 @@ def region_restore_track(source: torch.Tensor, state: torch.Tensor, origins, fra
     return out
 
 
+@_on_tensor_device
+def mask_spans(weights: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Latent-cell weights uint8 [Bm, Fs, h, w] -> device int16 [Fs, h + w, 2]: per latent frame and row the inclusive (x_lo, x_hi) of
+    the non-zero weights over all samples, (w, -1) for a row without one, then per column (y_lo, y_hi), (h, -1) for a column without
+    one (``wan_mask_spans``: one workgroup per frame, no atomics, every word written once).  A frame's bounds (``mask_bounds``) are the
+    min and max of its spans.  Never synchronises: the caller copies the 4 * (h + w) * Fs bytes to the host."""
+    _need(weights, torch.uint8, "mask_spans.weights")
+    if weights.dim() != 4 or not weights.is_contiguous():
+        raise ValueError(f"mask_spans.weights: a contiguous uint8 [Bm, Fs, h, w] tensor, got {tuple(weights.shape)}")
+    Bm, Fs, h, w = (int(v) for v in weights.shape)
+    if out is None:
+        out = torch.empty((Fs, h + w, 2), device=weights.device, dtype=torch.int16)
+    elif tuple(out.shape) != (Fs, h + w, 2) or out.dtype != torch.int16 or not out.is_contiguous() or out.device != weights.device:
+        raise ValueError(f"mask_spans.out: {out.dtype} {tuple(out.shape)} on {out.device} for contiguous int16 {(Fs, h + w, 2)} on "
+                         f"{weights.device}")
+    _lib.check(_lib.load().wan_mask_spans(_p(weights), _p(out), Bm, Fs, h, w, _stream()), "wan_mask_spans")
+    return out
+
+
+def _split_boxes(origins, cuts, name: str):
+    """The boxes of a split as the C side takes them: (origins, cuts as ctypes int arrays or None, K)."""
+    import numpy as np
+    o = np.asarray(origins.cpu() if torch.is_tensor(origins) else origins)
+    c = np.asarray(cuts.cpu() if torch.is_tensor(cuts) else cuts)
+    if o.ndim != 2 or o.shape[1] != 2 or o.dtype.kind not in "iu":
+        raise ValueError(f"{name}: origins = integer [K, 2] pairs (y0, x0) in cells, got {o.dtype} {o.shape}")
+    if c.ndim != 1 or c.dtype.kind not in "iu" or c.shape[0] != o.shape[0] + 1:
+        raise ValueError(f"{name}: cuts = {o.shape[0] + 1} integers for {o.shape[0]} boxes, got {c.dtype} {c.shape}")
+    if o.shape[0] == 0:
+        return None, None, 0
+    if min(int(o.min()), int(c.min())) < -2 ** 31 or max(int(o.max()), int(c.max())) >= 2 ** 31:
+        raise ValueError(f"{name}: origins or cuts leave the int32 range")
+    as_c = lambda a: (ctypes.c_int * a.size).from_buffer_copy(np.ascontiguousarray(a, dtype=np.int32))
+    return as_c(o), as_c(c), int(o.shape[0])
+
+
+@_on_tensor_device
+def region_crop_split(x: torch.Tensor, runs, origins, cuts, axis: int, size, clip: bool = False,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``region_crop_frames`` for the K boxes of a split at once: ``origins`` integer [K, 2] and ``cuts`` integer [K + 1] on the HOST,
+    ``axis`` 1 (the cuts are columns) or 0 (rows) as in ``edit_region.SplitPlan``, ``size`` = (h, w), one for all -> contiguous
+    [K, ..., Fo, h, w], box-major, in ONE launch (``wan_region_crop_split``: the table travels in the kernel's arguments, at most 8
+    boxes).  ``clip``: everything outside what band k owns is zero in box k -- the form for the mask's weights."""
+    if not x.is_cuda:
+        raise RuntimeError(f"region_crop_split.x: tensor is on {x.device}; the HIP path has no CPU fallback")
+    if x.element_size() not in (1, 2, 4):
+        raise ValueError(f"region_crop_split: dtype {x.dtype} not supported (elements of 1, 2 or 4 bytes)")
+    if x.dim() < 3 or not x.is_contiguous():
+        raise ValueError(f"region_crop_split.x: a contiguous [..., F, H, W] tensor, got {tuple(x.shape)}")
+    if len(size) != 2:
+        raise ValueError(f"region_crop_split: size = (h, w) in cells, got {size!r}")
+    hr, wr = int(size[0]), int(size[1])
+    runs = list(runs)
+    if any(not hasattr(pair, "__len__") or len(pair) != 2 for pair in runs):
+        raise ValueError(f"region_crop_split: runs = pairs (start, count) of frames, got {runs!r}")
+    flat = [int(v) for pair in runs for v in pair]
+    F, H, W = (int(v) for v in x.shape[-3:])
+    table, bounds, K = _split_boxes(origins, cuts, "region_crop_split")
+    R = int(math.prod(x.shape[:-3]))
+    Fo = sum(max(c, 0) for c in flat[1::2])
+    out = _region_out(out, (K,) + tuple(x.shape[:-3]) + (Fo, max(hr, 0), max(wr, 0)), x, "region_crop_split.out")
+    _lib.check(_lib.load().wan_region_crop_split(_p(out), _p(x), x.element_size(), R, F, H, W, (ctypes.c_int * max(len(flat), 1))(*flat),
+                                                 len(flat) // 2, table, bounds, K, int(axis), int(bool(clip)), hr, wr, _stream()),
+               "wan_region_crop_split")
+    return out
+
+
+@_on_tensor_device
+def region_restore_split(source: torch.Tensor, state: torch.Tensor, origins, cuts, axis: int, frames,
+                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``region_restore_frames`` for the K boxes of a split: ``source`` [B, C, cc, H, W] and ``state`` [K B, C, n + G + n, hr, wr],
+    box-major -> [B, C, cc + G + cc, H, W] in ONE launch (``wan_region_restore_split``).  A grounding or target cell takes box k's
+    value where it lies inside box k AND inside what band k owns (the target only in the frames ``frames`` = (t0, n)); everywhere
+    else it is the source, bit for bit."""
+    if not source.is_cuda or not state.is_cuda:
+        raise RuntimeError(f"region_restore_split: tensors are on {source.device} and {state.device}; the HIP path has no CPU fallback")
+    if source.element_size() not in (1, 2, 4):
+        raise ValueError(f"region_restore_split: dtype {source.dtype} not supported (elements of 1, 2 or 4 bytes)")
+    if source.dim() != 5 or state.dim() != 5 or source.shape[1] != state.shape[1] or source.dtype != state.dtype \
+            or source.device != state.device:
+        raise ValueError(f"region_restore_split: source {source.dtype} {tuple(source.shape)} on {source.device} and state {state.dtype} "
+                         f"{tuple(state.shape)} on {state.device}: expected [B, C, cc, H, W] and [K B, C, n + G + n, hr, wr] of one dtype")
+    source, state = source.contiguous(), state.contiguous()
+    B, C, cc, H, W = (int(v) for v in source.shape)
+    Fr, hr, wr = (int(v) for v in state.shape[2:])
+    if len(frames) != 2:
+        raise ValueError(f"region_restore_split: frames = (t0, n) in latent frames, got {frames!r}")
+    t0, n = int(frames[0]), int(frames[1])
+    G = Fr - 2 * n
+    table, bounds, K = _split_boxes(origins, cuts, "region_restore_split")
+    if int(state.shape[0]) != K * B:
+        raise ValueError(f"region_restore_split: {int(state.shape[0])} state samples for {K} boxes of {B} samples (box-major)")
+    out = _region_out(out, (B, C, max(2 * cc + G, 0), H, W), source, "region_restore_split.out")
+    _lib.check(_lib.load().wan_region_restore_split(_p(out), _p(source), _p(state), source.element_size(), B, C, cc, G, H, W, t0, n,
+                                                    table, bounds, K, int(axis), hr, wr, _stream()), "wan_region_restore_split")
+    return out
+
+
 def _avail(t: torch.Tensor) -> int:
     """Elements from t's first element to the end of its storage."""
     return t.untyped_storage().nbytes() // t.element_size() - t.storage_offset()

@@ -47,6 +47,7 @@ class WanPipelineOutput:
     edit_region: Optional[tuple] = None             # extension: (y, x, h, w) in pixels, what the loop ran on (edit_region=True); None when off
     edit_region_time: Optional[tuple] = None        # extension: (first pixel frame, pixel frame count) of it (edit_region_time_margin); None when off
     edit_region_vae: Optional[tuple] = None         # extension: (y, x, h, w) in pixels, the box the VAE ran on (edit_region_vae_halo); None when off
+    edit_regions: Optional[tuple] = None            # extension: ((y, x, h, w), ...) in pixels, one per box the loop ran on (edit_region_split; edit_region then encloses them all); None when off or where the mask was not split
     edit_region_track: Optional[tuple] = None       # extension: ((h, w), ((y_f, x_f), ...)) in pixels, the box of every latent frame of the source segment (edit_region_follow; edit_region then encloses them all); None when off
 
 
@@ -413,7 +414,17 @@ class WanPipeline:
             # to the source stays exact; the model sees a stabilised crop whose background slides.  Not with `edit_region_vae_halo`.
             # None: one rectangle for the clip.  There is no default: any value is a guess.  Opt-in and lossy; no quality claim.
             edit_region_follow=switches.pop("edit_region_follow", None),
-            region_follow=None)                          # set below: the span in latent frames, checked (None: the box does not move)
+            region_follow=None,                          # set below: the span in latent frames, checked (None: the box does not move)
+            # `edit_region_split=None` (an int from 2 to 8): with `edit_region=True`, a mask of SEPARATE objects is split into at most this
+            # many bands along ONE axis, columns or rows, every band gets a box of ONE common size (edit_region.region_split_plan, from the
+            # spans wan_mask_spans brings to the host instead of the bounds), and the K' boxes run as K' x B samples of the ordinary loop
+            # (wan_region_crop_split), so two small objects in opposite corners cost two small boxes, not their union.  In box A the cells
+            # of object B are pinned to the source; every box is put back over the part of the frame its band owns
+            # (wan_region_restore_split).  A box sees only itself.  A mask of one object, or one whose split does not pay, is
+            # `edit_region=True` alone, bit for bit.  Not with `edit_region_follow` or `edit_region_vae_halo`.  None: one rectangle.
+            # There is no default: any value is a guess.  Opt-in and lossy; no quality claim.
+            edit_region_split=switches.pop("edit_region_split", None),
+            region_split=None)                           # set below: the most boxes, checked (None: one rectangle)
         if switches:
             raise TypeError(f"__call__() got an unexpected keyword argument {next(iter(switches))!r}")
         if o.edit_mask is not None:
@@ -453,6 +464,18 @@ class WanPipeline:
                 raise ValueError("edit_region_follow with edit_region_vae_halo: a pixel box that moves from frame to frame inside a "
                                  "causal VAE (whose every frame leans on the features of the frames before it, at the same pixels) is "
                                  "a different problem; the VAE box is one rectangle for the clip")
+        if o.edit_region_split is not None:
+            from .edit_region import region_split_count
+            o.region_split = region_split_count(o.edit_region_split)
+            if not o.edit_region:
+                raise ValueError("edit_region_split extends edit_region=True (the rectangle becomes one box per object), and this call "
+                                 "does not set it")
+            if o.edit_region_follow is not None:
+                raise ValueError("edit_region_split with edit_region_follow: the bands are cut from the union of the mask over all "
+                                 "frames and a band's box has one corner for the clip; boxes that move would need a cut per frame")
+            if o.edit_region_vae_halo is not None:
+                raise ValueError("edit_region_split with edit_region_vae_halo: the VAE box is ONE rectangle around the region, and "
+                                 "around boxes in opposite corners that is the whole frame again")
         from .edit_region import region_stitch_feather
         o.stitch_feather = region_stitch_feather(o.edit_region_stitch_feather)
         if o.edit_region_vae_halo is not None:
@@ -537,14 +560,22 @@ class WanPipeline:
     def _plan_region(self, o, weights, hl, wl, tile_cells, cc, G):
         """The bounds of the non-zero weights (wan_mask_bounds), their copy to the host -- the ONE synchronisation of edit_region -- and
         the rules on it: (RegionPlan -- or, with `edit_region_follow`, the TrackPlan from the same host copy --, TimeRegion or None
-        without `edit_region_time_margin`)."""
+        without `edit_region_time_margin`).  With `edit_region_split` the spans (wan_mask_spans) come to the host in place of the
+        bounds, still ONE synchronisation, and the plan is a SplitPlan where splitting the mask pays, the RegionPlan where not."""
         from . import ops
         from .edit_region import region_plan, region_time_plan, region_track_plan
         if G > cc:
             raise ValueError(f"edit_region: {G} grounding frames for {cc} source frames; outside the region grounding frame g is "
                              "source frame g, so at most as many")
-        bounds = ops.mask_bounds(weights).cpu()
         rule = (hl, wl), o.region_margin, None if tile_cells is None else tile_cells[0], int(self.transformer.config.patch_size[1])
+        if o.region_split is not None:
+            # `edit_region_split`: the spans come to the host in place of the bounds (a frame's bounds are the min and max of its spans)
+            from .edit_region import region_split_plan, spans_bounds
+            spans = ops.mask_spans(weights).cpu()
+            bounds = spans_bounds(spans, (hl, wl))
+            plan = region_split_plan(spans, *rule, max_regions=o.region_split)
+            return plan, None if o.region_time_margin is None else region_time_plan(bounds, cc, o.region_time_margin, G)
+        bounds = ops.mask_bounds(weights).cpu()
         plan = region_plan(bounds, *rule) if o.region_follow is None else region_track_plan(bounds, *rule, span=o.region_follow)
         return plan, None if o.region_time_margin is None else region_time_plan(bounds, cc, o.region_time_margin, G)
 
@@ -556,6 +587,8 @@ class WanPipeline:
         state and weights are cropped in frames and cells at once (wan_region_crop_frames, still one launch each).
         With `edit_region_follow` the plan is a TrackPlan and both are cropped by ONE table of corners (wan_region_crop_track): the
         weights by the source frames' table, the state by the same table laid out as [source | grounding | target].
+        With `edit_region_split` and a SplitPlan both are cropped into K' boxes at once (wan_region_crop_split), box-major: the state
+        becomes [K' B, ...] and the weights, clipped to what each band owns, [K' B, ...] too.
         Returns (latents, weights, region, the source frames of the loop's clip): `region` is None with the option off -- nothing is
         launched then -- or (RegionPlan, the whole source block to restore into; None where nothing was cropped, the TimeRegion; None
         without a time crop)."""
@@ -564,6 +597,17 @@ class WanPipeline:
         from . import ops
         hl, wl = int(latents.shape[3]), int(latents.shape[4])
         plan, span = self._plan_region(o, weights, hl, wl, tile_cells, cc, G)
+        if hasattr(plan, "cuts"):
+            # `edit_region_split`, and the mask was split: K' boxes of one size, box-major [K' B, ...] (one launch each); the weights
+            # are clipped to what each band owns and given one row per sample of the state
+            t0, n = (0, cc) if span is None else span
+            runs = [(0, 2 * cc + G)] if span is None else [(t0, n)] + ([(cc, G)] if G else []) + [(cc + G + t0, n)]
+            boxes = plan.origins, plan.cuts, plan.axis, (plan.h, plan.w)
+            state = ops.region_crop_split(latents.contiguous(), runs, *boxes).flatten(0, 1)
+            cropped = ops.region_crop_split(weights, [(t0, n)], *boxes, clip=True)
+            if cropped.shape[1] != latents.shape[0]:
+                cropped = cropped.expand(-1, latents.shape[0], -1, -1, -1)
+            return state, cropped.reshape((-1,) + tuple(cropped.shape[2:])), (plan, latents[:, :, :cc], span), n
         if o.region_follow is not None:
             t0, n = (0, cc) if span is None else span
             if (plan.h, plan.w, n) == (hl, wl, cc):
@@ -586,12 +630,16 @@ class WanPipeline:
     @staticmethod
     def _restore_region(latents, region, box=None):
         """Edit region, the second stage: the loop's final state on the region put back into the source latents (wan_region_restore, or
-        wan_region_restore_frames after a time crop, wan_region_restore_track where the box follows the mask) -- outside the region the grounding and target frames are the source's bits.
+        wan_region_restore_frames after a time crop, wan_region_restore_track where the box follows the mask, wan_region_restore_split
+        where the mask was split into boxes) -- outside the region the grounding and target frames are the source's bits.
         `box` (`edit_region_vae_halo`): the source latents are the VAE box's, and the region's corner counts from the box's."""
         plan, source, span = region
         if source is None:
             return latents
         from . import ops
+        if hasattr(plan, "cuts"):                        # `edit_region_split`: a SplitPlan (never with a VAE box)
+            return ops.region_restore_split(source.to(latents.dtype), latents, plan.origins, plan.cuts, plan.axis,
+                                            (0, source.shape[2]) if span is None else span)
         if hasattr(plan, "origins"):                     # `edit_region_follow`: a TrackPlan (never with a VAE box)
             return ops.region_restore_track(source.to(latents.dtype), latents, plan.origins,
                                             (0, source.shape[2]) if span is None else span)
@@ -739,11 +787,12 @@ class WanPipeline:
             return noise_pred
         return guided
 
-    def _whole_clip_form(self, guided, cc, G, zero_source):
+    def _whole_clip_form(self, guided, cc, G, zero_source, boxes=False):
         """The loop's `predict` for a clip that is one model input (:700-736): `cat([latents] * 2)` or the latents themselves, one
-        forward, guidance, the CoF mask.  Returns (predict, the target's first frame in the loop state, the state -> latents cut)."""
+        forward, guidance, the CoF mask.  `boxes` (`edit_region_split`): the samples are boxes of a clip, not a clip each -- windows, as
+        far as the model's cfg_skip rule goes.  Returns (predict, the target's first frame in the loop state, the state -> latents cut)."""
         def predict(latents, neg, pos, i, t):
-            noise_pred = guided(lambda rep: torch.cat([latents] * 2) if rep == 2 else latents, latents.shape[0], neg, pos, t, False)
+            noise_pred = guided(lambda rep: torch.cat([latents] * 2) if rep == 2 else latents, latents.shape[0], neg, pos, t, boxes)
             if zero_source:
                 noise_pred[:, :, :cc] = 0                                                       # :736
             # else: already zero -- written by wan_unpatchify(zero_frames); CFG keeps it (0 + s * (0 - 0))
@@ -977,6 +1026,11 @@ class WanPipeline:
             # `loop_cc`: the source frames of the clip the loop runs on -- condition_count, or the frame range's after a time crop
             latents, mask_weights, region, loop_cc = self._crop_to_region(opt, latents, mask_weights, window_sizes[1], condition_count,
                                                                           ground_latent_count)
+        # `edit_region_split`: the K' boxes are K' x B samples, box-major, and every box takes its sample's prompts (the order in
+        # which _windowed_form repeats them for its windows)
+        boxes = len(region[0].origins) if region is not None and hasattr(region[0], "cuts") else 1
+        if boxes > 1:
+            in_prompt_embeds = (negative_prompt_embeds * boxes + prompt_embeds * boxes) if do_cfg else prompt_embeds * boxes
         plan, tiles = self._plan_windows(opt, window_sizes, latents.shape, loop_cc, ground_latent_count, capture_graph)
         windowed = plan is not None or tiles is not None
         win_n = loop_cc if not windowed else tiles.t.window if tiles is not None else plan.window
@@ -1009,7 +1063,7 @@ class WanPipeline:
                 latents, predict, target_frame0, cut = self._windowed_form(guided, latents, plan, tiles, opt.window_batch,
                                                                            loop_cc, ground_latent_count)
             else:
-                predict, target_frame0, cut = self._whole_clip_form(guided, loop_cc, ground_latent_count, zero_source)
+                predict, target_frame0, cut = self._whole_clip_form(guided, loop_cc, ground_latent_count, zero_source, boxes > 1)
             callback = None if callback_on_step_end is None else (callback_on_step_end, callback_on_step_end_tensor_inputs, {
                 "prompt_embeds": prompt_embeds, "negative_prompt_embeds": negative_prompt_embeds})
             loop = lambda lat, embeds: cut(self._denoise(
@@ -1031,7 +1085,9 @@ class WanPipeline:
         self._stage("vae_decode", t_stage)
         tracked = region is not None and opt.region_follow is not None
         return WanPipelineOutput(videos=videos, ground_videos=ground, edit_videos=edit, latents=latents, compare_videos=compared,
-                                 edit_region=None if region is None else (region[0].enclosing() if tracked else region[0]).pixels(
+                                 edit_region=None if region is None else (region[0].enclosing() if tracked or boxes > 1 else region[0]).pixels(
+                                     getattr(getattr(self.vae, "config", None), "spatial_compression_ratio", 8)),
+                                 edit_regions=None if boxes == 1 else region[0].pixels(
                                      getattr(getattr(self.vae, "config", None), "spatial_compression_ratio", 8)),
                                  edit_region_track=None if not tracked else region[0].pixels(
                                      getattr(getattr(self.vae, "config", None), "spatial_compression_ratio", 8)),
