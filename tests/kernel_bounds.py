@@ -9,7 +9,8 @@ A truncating conversion has 2 u; the bounds allow u for the output rounding, so 
 
 Plain module: no fixtures, no pytest hooks.  tests/test_kernel_bounds_host.py, tests/test_vae_bounds_host.py and
 tests/test_fp8_bounds_host.py check it on the CPU (honest emulations inside, mutants outside); tests/test_gpu_kernel_elementwise.py,
-tests/test_gpu_vae_elementwise.py and tests/test_gpu_fp8_elementwise.py use it on the kernels.
+tests/test_gpu_vae_elementwise.py and tests/test_gpu_fp8_elementwise.py use it on the kernels; tests/test_t5_bounds_host.py and
+tests/test_gpu_t5_elementwise.py are the same pair for the umT5 text encoder's kernels.
 """
 import math
 
@@ -660,6 +661,89 @@ def heavy_half_qkv_e4m3(Lq, Lk, seed, q_exp=5, k_exp=2, D=128):
     guard = torch.zeros(D)
     guard[0] = 2.0 ** gk * 2.0 ** k_exp
     return dict(q8=q8, k8=k8, v=v, guard=guard.to(FP8), qd=dq_pow2(q8, q_exp), kd=dq_pow2(k8, k_exp))
+
+
+# ------------------------------------------------------------------------------------------------ umT5 text encoder row kernels
+def rmsnorm_rows_bound(x, w, eps, out_dtype):
+    """wan_rmsnorm_rows (rmsnorm_rows_kernel<NV, OUT_F32>, videocof_amd/csrc/t5_kernels.hip): out = x rstd w, rstd = rsqrtf(ss / dim + eps),
+    x, w fp32, out bf16 (one rounding to nearest even, v_cvt_pk_bf16_f32) or fp32 (none).  Returns (ref, bound), [rows, dim]:
+        u_out |ref| (bf16 only)  +  ((dim + 16) u32 + 2^-127 / (mean x² + eps)) |ref|  +  2^-149
+    ref: fp64 x / sqrt(mean(x²) + eps) w on the fp32 inputs, eps at the fp32 value the kernel is handed.  Counted on the gfx950 code:
+    * ss: dim squares (one rounding each, u32 of a non-negative term) added in fp32 in any order -- per thread over strided float4
+      chunks, a 64-lane shuffle tree, 0 + four wave sums -- relative (dim + 1) u32, HALVED by the root;
+    * ss / (float)dim is the correctly rounded expansion (v_div_scale / v_rcp_f32 / v_div_fmas / v_div_fixup; (float)dim is exact
+      below 2^24), + eps one addition: 2 u32 on the root's argument, halved;
+    * rsqrtf is ONE v_rsq_f32 (1 ulp = 2 u32, CDNA ISA guide); an argument below 2^-126 is multiplied by 2^24 first and the result
+      by 2^12, both exact;  * two multiplies (v_pk_mul_f32), u32 each:   (dim + 1) / 2 + 1 + 2 + 2 = dim / 2 + 5.5,
+      granted as (dim + 16) u32 like rmsnorm_rope_bound's rstd -- the count is smaller at every dim;
+    * squares below the normal range (|x| < 2^-63) are denormal (the kernels run with denormals on; a build that flushed them would
+      lose at most 2^-126 per square, so at most 2^-126 of the MEAN): relative 2^-127 / (mean + eps) on rstd -- 1e-32 at eps = 1e-6;
+    * 2^-149: a result below the normal range lands on the subnormal grid."""
+    x, w = _d(x), _d(w)
+    dim = x.shape[-1]
+    eps32 = float(torch.tensor(float(eps), dtype=torch.float32))
+    arg = (x * x).mean(dim=-1, keepdim=True) + eps32
+    ref = x / torch.sqrt(arg) * w
+    rel = (dim + 16) * U_F32 + 2.0 ** -127 / arg
+    out_u = U_BF16 if out_dtype == torch.bfloat16 else 0.0
+    return ref, out_u * ref.abs() + rel * ref.abs() + 2.0 ** -149
+
+
+def t5_bias(table, lut, L):
+    """bias[h, i, j] = table[lut[j - i + L - 1], h], fp64 [H, L, L]: the relative position bias as wan_t5_softmax_bias defines it
+    (include/wan_hip.h), by plain indexing.  table [num_buckets, H]; lut int [2 L - 1], index = key minus query offset + L - 1."""
+    i = torch.arange(L)
+    idx = lut.long().cpu()[i[None, :] - i[:, None] + L - 1]                 # [L(i), L(j)]
+    return _d(table)[idx].permute(2, 0, 1)
+
+
+def t5_softmax_bias_bound(s, table, lut, H, k_len):
+    """wan_t5_softmax_bias (t5_softmax_bias_kernel): p_j = e_j / sum_j e_j, e_j = __expf(t_j - mx), t_j = fl(s[h, i, j] + bias[h, i, j]),
+    over j < k_len; s fp32 [H, L, L].  Returns (ref, bound), [H, L, k_len]; columns [k_len, npad) of the output must be exactly 0.
+        u16 p_j + p_j u32 (r_j + sum_k p_k r_k + k_len + 4) + 2^-120,    r_j = |t_j| + 3 x_j + 2,   x_j = mx - t_j >= 0
+    softmax_rows_bound with the scale multiply removed and one rounding added, counted on the gfx950 code of the kernel:
+    * t_j = s + bias is ONE fp32 addition: an absolute u32 |t_j| on the exponent, seen through e^x as a relative u32 |t_j| of e_j -- in
+      the numerator, and weighted by p_k in the row sum.  (The softmax is invariant under the shift by mx, so the maximum's own rounding
+      cancels; the maximum of the computed t is found exactly.)
+    * __expf(t - mx) is v_sub_f32, v_mul_f32 by the rounded constant 0x3fb8aa3b (log2 e), v_exp_f32 -- no range scaling: the
+      subtraction, the constant and the multiply are 3 u32 RELATIVE on the argument, through e^x a relative 3 u32 x_j of e_j; v_exp_f32
+      is 1 ulp = 2 u32;
+    * the row sum: k_len fp32 additions of non-negative terms in any order (8 strided terms per thread, a 64-lane tree, four wave
+      sums): k_len u32, + the terms' own errors weighted by their share;
+    * 1.f / sum is the correctly rounded division expansion (u32; 2 u32 granted, so that a bare v_rcp_f32 would pass), the multiply
+      u32, + 1 spare: the 4;  * one rounding to bf16, to nearest even (v_cvt_pk_bf16_f32);
+    * 2^-120: exponentials below the normal range are flushed by v_exp_f32, and a bf16 result there lands on the subnormal grid."""
+    sd = _d(s)
+    L = sd.shape[-1]
+    t = (sd + t5_bias(table, lut, L))[:, :, :k_len]
+    x = t.max(dim=-1, keepdim=True).values - t
+    p = torch.softmax(-x, dim=-1)
+    r = t.abs() + 3.0 * x + 2.0
+    row = (p * r).sum(dim=-1, keepdim=True)
+    return p, U_BF16 * p + p * U_F32 * (r + row + k_len + 4.0) + 2.0 ** -120
+
+
+GUARD_SCORE = 80.0
+
+
+def t5_softmax_inputs(H, L, k_len, seed, lut, guard=False, num_buckets=32):
+    """Scores fp32 [H, L, L] of std 3 and a bias table [num_buckets, H] of std 2 (fp32), checked here on the CPU: at L >= 260 the lut
+    uses every bucket an offset can have (all but num_buckets / 2), so no reachable table row goes unread.  guard: the "guard score" input -- real scores are capped at 9 and every score
+    BEHIND the mask, s[:, :, k_len:], is +80: a key admitted by a wrong mask (|bias| stays below 12: margin > 45) takes all the mass of
+    its row, as heavy_key() does for attention.  On random scores an admitted key among hundreds stays inside every whole-tensor limit."""
+    g = torch.Generator().manual_seed(seed)
+    s = torch.randn(H, L, L, generator=g) * 3.0
+    table = torch.randn(num_buckets, H, generator=g) * 2.0
+    assert lut.numel() == 2 * L - 1 and int(lut.min()) >= 0 and int(lut.max()) < num_buckets
+    if L >= 260:
+        # bucket num_buckets / 2 is "key behind the query at distance 0", which no offset has: 31 of the 32 buckets can be reached
+        reachable = [b for b in range(num_buckets) if b != num_buckets // 2]
+        assert sorted(set(lut.tolist())) == reachable, "the lut must reach every bucket an offset can have"
+    if guard:
+        s.clamp_(max=9.0)
+        s[:, :, k_len:] = GUARD_SCORE
+        assert float(s[:, :, :k_len].max()) < 10.0 and float(table.abs().max()) < 12.0
+    return s, table
 
 
 # ------------------------------------------------------------------------------------------------ comparison

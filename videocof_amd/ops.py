@@ -2077,6 +2077,8 @@ def rmsnorm_rows(x: torch.Tensor, w: torch.Tensor, eps: float, out_dtype: torch.
     if out is None:
         out = torch.empty(x.shape, device=x.device, dtype=out_dtype)
     _need(out, out_dtype, "rmsnorm_rows.out")
+    if out.shape != x.shape or not out.is_contiguous():
+        raise ValueError(f"rmsnorm_rows.out must be contiguous and of x's shape {tuple(x.shape)}, got {tuple(out.shape)} with strides {out.stride()}")
     lib = _lib.load()
     _lib.check(lib.wan_rmsnorm_rows(_p(x), _p(w), _p(out), 0 if out_dtype == torch.float32 else 1, x.shape[0],
                                     x.shape[1], float(eps), _stream()), "wan_rmsnorm_rows")
@@ -2098,6 +2100,11 @@ def t5_softmax_bias(scores: torch.Tensor, table: torch.Tensor, lut: torch.Tensor
     if out is None:
         out = torch.empty(H, Lq, npad, device=scores.device, dtype=torch.bfloat16)
     _need(out, torch.bfloat16, "t5_softmax.out")
+    # the kernel addresses row (h, i) at (h * Lq + i) * ldp: heads must follow each other without a gap
+    if out.dim() != 3 or out.shape[0] != H or out.shape[1] != Lq or out.shape[2] < npad:
+        raise ValueError(f"t5_softmax.out must be [H, Lq, >= npad] = [{H}, {Lq}, >= {int(npad)}], got {tuple(out.shape)}")
+    if out.stride(2) != 1 or out.stride(1) < npad or out.stride(0) != Lq * out.stride(1):
+        raise ValueError(f"t5_softmax.out: strides {out.stride()} must be (Lq * ldp, ldp, 1) with ldp >= npad")
     lib = _lib.load()
     _lib.check(lib.wan_t5_softmax_bias(_p(scores), Lk, _p(table), _p(lut), _p(out), out.stride(1), H, Lq, Lk,
                                        int(k_len), int(npad), _stream()), "wan_t5_softmax_bias")
@@ -2113,6 +2120,8 @@ def mul_bf16(a: torch.Tensor, b: torch.Tensor, out: Optional[torch.Tensor] = Non
     if out is None:
         out = torch.empty_like(a)
     _need(out, torch.bfloat16, "mul.out")
+    if out.shape != a.shape or not out.is_contiguous():
+        raise ValueError(f"mul_bf16.out must be contiguous and of the operands' shape {tuple(a.shape)}, got {tuple(out.shape)} with strides {out.stride()}")
     lib = _lib.load()
     _lib.check(lib.wan_mul_bf16(_p(a), _p(b), _p(out), a.numel(), _stream()), "wan_mul_bf16")
     return out
