@@ -1117,6 +1117,51 @@ int64_t wan_clip_stats_workspace_bytes(int N, int H, int W);
 wan_status_t wan_clip_stats(const void* a_u8, const void* b_u8, const void* alpha_u8, void* stats_i64, int N, int H, int W, int smooth,
                             void* workspace, int64_t workspace_bytes, void* stream);
 
+/* Colour match: bring the edit's colours back to the source's with one gain and offset per frame and channel, estimated where the edit
+ * left the frame alone, in exact integers (videocof_amd/video_io.py: reference_color_stats / reference_color_coefficients /
+ * reference_frames_affine restate this in Python ints and numpy and equal the kernels word for word).
+ * replaces: color_transfer_post_process of save_videos_grid (videox_fun/utils/utils.py:31-57) in PURPOSE only: that one is Reinhard's
+ * transfer in OpenCV's 8-bit LAB; this one is the same mean / deviation transfer per RGB channel.  A hue rotation is not corrected, and
+ * neither is a shift that varies over the frame.
+ *
+ * wan_color_stats: ref uint8 [B, ref_T, H, W, 3], edit uint8 [B, T, H, W, 3] (any base alignment), alpha uint8 [B, ref_T, H, W] or NULL
+ * -> stats int64 [B * T][WAN_COLOR_STATS_WORDS].  ref_T is T, or 1: that one frame (and its alpha) is then paired with every frame of the
+ * sample.  A pixel counts where its alpha == 0 (NULL: every pixel).  Per frame, over the counted pixels:
+ *     [0]                 n   their number
+ *     [1 + 4 c + 0]       A   the sum of ref's channel c          [1 + 4 c + 1]   E   the sum of edit's
+ *     [1 + 4 c + 2]       AA  the sum of ref's squares            [1 + 4 c + 3]   EE  the sum of edit's squares
+ *     [13, 16)            0
+ * Every word is overwritten; integer adds only, so the result does not depend on the order of execution.  A null ref, edit or stats, a
+ * size below 1, ref_T other than 1 or T, or a workspace below wan_color_stats_workspace_bytes(B * T, H, W) bytes -> WAN_ERR_INVALID;
+ * B * T > 65535 or a frame of 2 GiB or more -> WAN_ERR_UNSUPPORTED; both before anything is enqueued.  Enqueues two kernels on `stream`
+ * (both clips are read once); never synchronises.
+ *
+ * wan_color_coef: stats int64 [B * T][16] as above -> coef int32 [B * T][3][2] = (g, b) per frame and channel, ONE = WAN_COLOR_ONE:
+ *     the sums of frame t are first replaced by the sums over frames t - pool_t .. t + pool_t of the SAME sample (0 <= pool_t <=
+ *     WAN_COLOR_MAX_POOL_T; pool_t >= T - 1 gives one transform per sample)
+ *     n < max(1, min_pixels):   g = ONE, b = 0
+ *     else   Vs = n AA - A A,  Ve = n EE - E E   (128-bit)
+ *            g = ONE                                          if gain == 0 or Ve == 0
+ *            k = max(0, bit_length(max(Vs, Ve)) - 38),  vs = Vs >> k,  ve = Ve >> k
+ *            g = 2 ONE if ve == 0, else floor(sqrt((vs << 24) / ve)) (floor division, integer square root), clamped to [ONE / 2, 2 ONE]
+ *            b = floor((ONE A - g E + (n >> 1)) / n)
+ * No floating point anywhere.  The sums have to be sums: Vs, Ve >= 0.  A null pointer, B or T below 1, B * T above 2^24, pool_t out of
+ * range or min_pixels < 0 -> WAN_ERR_INVALID.  Enqueues one kernel on `stream`; never synchronises.
+ *
+ * wan_frames_u8_affine: frames uint8 [N, H, W, 3] (any alignment), coef int32 [N][3][2] -> out uint8 of the frames' shape, per byte x of
+ * channel c (its index mod 3) of frame f:   out = clamp((g x + b + ONE / 2) >> 12, 0, 255)   with an arithmetic shift, computed in 32
+ * bits: -2^21 <= g <= 2^21 and -2^30 <= b <= 2^30 are the caller's to keep (wan_color_coef's are far inside).  out may be frames (in
+ * place): a thread reads its bytes before it writes them, and no thread writes another's.  N <= 65535 and a frame below 2 GiB -> else
+ * WAN_ERR_UNSUPPORTED.  Enqueues one kernel on `stream`; never synchronises. */
+#define WAN_COLOR_STATS_WORDS 16
+#define WAN_COLOR_ONE 4096
+#define WAN_COLOR_MAX_POOL_T 8
+int64_t wan_color_stats_workspace_bytes(int N, int H, int W);
+wan_status_t wan_color_stats(const void* ref_u8, const void* edit_u8, const void* alpha_u8, void* stats_i64, int B, int T, int ref_T,
+                             int H, int W, void* workspace, int64_t workspace_bytes, void* stream);
+wan_status_t wan_color_coef(const void* stats_i64, void* coef_i32, int B, int T, int pool_t, int gain, int min_pixels, void* stream);
+wan_status_t wan_frames_u8_affine(const void* frames_u8, const void* coef_i32, void* out_u8, int N, int H, int W, void* stream);
+
 /* ===========================================================================
  * the umT5 text encoder (videox_fun/models/wan_text_encoder.py:256-304), the step
  * before the denoising path.  Its Linear layers are wan_gemm_bf16; the rest:

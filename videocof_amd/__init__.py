@@ -34,6 +34,8 @@ from .video_io import change_mask, composite_frames, keep_unedited, reference_ch
 from .video_io import (fit_mask, latent_edit_mask, reference_fit_mask, reference_latent_edit_mask,  # noqa: F401
                        reference_masked_prediction)
 from .video_io import ClipStats, clip_stats, reference_clip_stats, vae_roundtrip_frames  # noqa: F401
+from .video_io import (color_match, color_match_coefficients, reference_color_match, reference_color_stats,  # noqa: F401
+                       reference_color_coefficients, reference_frames_affine)
 from .video_io import grid_frames, compare_frames, reference_grid_frames, reference_compare_frames  # noqa: F401
 from .video_io import yuv_matrix, yuv_to_frames, frames_to_yuv, reference_yuv_to_frames, reference_frames_to_yuv  # noqa: F401
 from .video_io import YuvClip, read_y4m, load_y4m_frames, write_y4m  # noqa: F401

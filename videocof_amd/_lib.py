@@ -286,6 +286,10 @@ SIGNATURES = {
                                         c_void_p]),
     "wan_clip_stats_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
     "wan_clip_stats": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p]),
+    "wan_color_stats_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
+    "wan_color_stats": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int64, c_void_p]),
+    "wan_color_coef": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "wan_frames_u8_affine": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
 }
 
 _lib = None

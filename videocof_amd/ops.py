@@ -1447,6 +1447,82 @@ def clip_stats(a: torch.Tensor, b: torch.Tensor, alpha: Optional[torch.Tensor], 
     return out
 
 
+COLOR_STATS_WORDS, COLOR_ONE, COLOR_MAX_POOL_T = 16, 4096, 8             # WAN_COLOR_* of include/wan_hip.h
+
+
+@_on_tensor_device
+def color_stats(ref: torch.Tensor, edit: torch.Tensor, alpha: Optional[torch.Tensor], out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """ref uint8 [B,T,H,W,3] or [B,1,H,W,3], edit uint8 [B,T,H,W,3], alpha uint8 of ref's [B,.,H,W] or None -> int64 [B,T,16] on the
+    device: per frame n, then (A, E, AA, EE) per channel over the pixels whose alpha is 0, three zero words (``wan_color_stats``,
+    include/wan_hip.h: two launches, exact integers).  ``out``: a contiguous int64 tensor of that shape, every word of which is
+    overwritten.  The workgroups' partial sums live in a workspace allocated here."""
+    _need(ref, torch.uint8, "color_stats.ref")
+    _need(edit, torch.uint8, "color_stats.edit")
+    if edit.dim() != 5 or edit.shape[-1] != 3:
+        raise ValueError(f"color_stats.edit: expected [B, T, H, W, 3], got {tuple(edit.shape)}")
+    B, T, H, W, _ = (int(v) for v in edit.shape)
+    if ref.dim() != 5 or tuple(ref.shape) not in ((B, T, H, W, 3), (B, 1, H, W, 3)) or ref.device != edit.device:
+        raise ValueError(f"color_stats.ref: expected [{B}, {T}, {H}, {W}, 3] or [{B}, 1, {H}, {W}, 3] on {edit.device}, got "
+                         f"{tuple(ref.shape)} on {ref.device}")
+    ref_T = int(ref.shape[1])
+    ref, edit = ref.contiguous(), edit.contiguous()
+    if alpha is not None:
+        _need(alpha, torch.uint8, "color_stats.alpha")
+        if tuple(alpha.shape) != (B, ref_T, H, W) or alpha.device != edit.device:
+            raise ValueError(f"color_stats.alpha: expected [{B}, {ref_T}, {H}, {W}] on {edit.device}, got {tuple(alpha.shape)} on "
+                             f"{alpha.device}")
+        alpha = alpha.contiguous()
+    if out is None:
+        out = torch.empty(B, T, COLOR_STATS_WORDS, device=edit.device, dtype=torch.int64)
+    elif out.dtype != torch.int64 or tuple(out.shape) != (B, T, COLOR_STATS_WORDS) or out.device != edit.device or not out.is_contiguous():
+        raise ValueError(f"color_stats.out: expected contiguous int64 [{B}, {T}, {COLOR_STATS_WORDS}] on {edit.device}, got {out.dtype} "
+                         f"{tuple(out.shape)} on {out.device}")
+    lib = _lib.load()
+    nws = int(lib.wan_color_stats_workspace_bytes(B * T, H, W))
+    ws = torch.empty(max(nws, 1), device=edit.device, dtype=torch.uint8)
+    _lib.check(lib.wan_color_stats(_p(ref), _p(edit), _p(alpha), _p(out), B, T, ref_T, H, W, _p(ws), nws, _stream()), "wan_color_stats")
+    return out
+
+
+@_on_tensor_device
+def color_coef(stats: torch.Tensor, pool_t: int, gain: bool, min_pixels: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int64 [B,T,16] sums of ``color_stats`` -> int32 [B,T,3,2] = (g, b) per frame and channel (``wan_color_coef``: the sums pooled
+    over ``pool_t`` frames either side within a sample, 128-bit variances, integer division and square root; one launch)."""
+    _need(stats, torch.int64, "color_coef.stats")
+    if stats.dim() != 3 or stats.shape[-1] != COLOR_STATS_WORDS or not stats.is_contiguous():
+        raise ValueError(f"color_coef.stats: expected contiguous int64 [B, T, {COLOR_STATS_WORDS}], got {tuple(stats.shape)}")
+    B, T = int(stats.shape[0]), int(stats.shape[1])
+    if out is None:
+        out = torch.empty(B, T, 3, 2, device=stats.device, dtype=torch.int32)
+    elif out.dtype != torch.int32 or tuple(out.shape) != (B, T, 3, 2) or out.device != stats.device or not out.is_contiguous():
+        raise ValueError(f"color_coef.out: expected contiguous int32 [{B}, {T}, 3, 2] on {stats.device}, got {out.dtype} "
+                         f"{tuple(out.shape)} on {out.device}")
+    _lib.check(_lib.load().wan_color_coef(_p(stats), _p(out), B, T, int(pool_t), int(bool(gain)), int(min_pixels), _stream()),
+               "wan_color_coef")
+    return out
+
+
+@_on_tensor_device
+def frames_u8_affine(frames: torch.Tensor, coef: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``clamp((g * x + b + 2048) >> 12, 0, 255)`` per byte of uint8 [N,H,W,3] frames with int32 [N,3,2] = (g, b) per frame and
+    channel (``wan_frames_u8_affine``, one launch).  ``out``: a contiguous uint8 tensor of the frames' shape; it may be ``frames``."""
+    _need(frames, torch.uint8, "frames_u8_affine.frames")
+    _need(coef, torch.int32, "frames_u8_affine.coef")
+    if frames.dim() != 4 or frames.shape[-1] != 3 or not frames.is_contiguous():
+        raise ValueError(f"frames_u8_affine.frames: expected contiguous [N, H, W, 3], got {tuple(frames.shape)}")
+    N, H, W, _ = (int(v) for v in frames.shape)
+    if tuple(coef.shape) != (N, 3, 2) or coef.device != frames.device or not coef.is_contiguous():
+        raise ValueError(f"frames_u8_affine.coef: expected contiguous [{N}, 3, 2] on {frames.device}, got {tuple(coef.shape)} on "
+                         f"{coef.device}")
+    if out is None:
+        out = torch.empty_like(frames)
+    elif out.dtype != torch.uint8 or out.shape != frames.shape or out.device != frames.device or not out.is_contiguous():
+        raise ValueError(f"frames_u8_affine.out: expected contiguous uint8 {tuple(frames.shape)} on {frames.device}, got {out.dtype} "
+                         f"{tuple(out.shape)} on {out.device}")
+    _lib.check(_lib.load().wan_frames_u8_affine(_p(frames), _p(coef), _p(out), N, H, W, _stream()), "wan_frames_u8_affine")
+    return out
+
+
 @_on_tensor_device
 def lincomb(terms, out_dtype: torch.dtype) -> torch.Tensor:
     """sum_i c_i * x_i over <= 4 same-shape CUDA tensors in one pass (fp32 accumulate); `terms` is a list

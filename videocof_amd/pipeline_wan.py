@@ -49,6 +49,7 @@ class WanPipelineOutput:
     edit_region_vae: Optional[tuple] = None         # extension: (y, x, h, w) in pixels, the box the VAE ran on (edit_region_vae_halo); None when off
     edit_regions: Optional[tuple] = None            # extension: ((y, x, h, w), ...) in pixels, one per box the loop ran on (edit_region_split; edit_region then encloses them all); None when off or where the mask was not split
     edit_region_track: Optional[tuple] = None       # extension: ((h, w), ((y_f, x_f), ...)) in pixels, the box of every latent frame of the source segment (edit_region_follow; edit_region then encloses them all); None when off
+    color_match: Optional[torch.Tensor] = None      # extension: int32 [B, T, 3, 2] on the device, the (gain, offset) in 1/4096 applied to every frame and channel of the edit segment (color_match=...); None when off
 
 
 def _require_source(has_source: bool, why: str) -> None:
@@ -296,11 +297,14 @@ class WanPipeline:
     def attention_kwargs(self):
         return getattr(self, "_attention_kwargs", None)
 
-    def _decode_frames_u8(self, latents, out, clip=None, dst_frame=0, keep=None, stitch=None) -> np.ndarray:
+    def _decode_frames_u8(self, latents, out, clip=None, dst_frame=0, keep=None, stitch=None, match=None) -> np.ndarray:
         """decode, then wan_video_to_frames_u8 into frames [dst_frame, dst_frame + T) of the device clip `clip` (uint8
         [B, T_clip, H, W, 3]; None = one of exactly T frames), then ONE asynchronous copy per sample of that frame range -- one
         contiguous run of bytes -- into `out`, a page-locked uint8 [B, T, H, W, 3] host tensor (or a frame slice of one).
         `keep`: a list that receives the device frames of the segment (the compare clip is composed from them).
+        `match` (`color_match`): (the uint8 source frames, the edit mask or None, (pool_t, gain, min_pixels), a list) -- the segment's
+        frames are matched to the source's colours in place on the device (video_io.color_match's kernels) before they are kept or
+        copied, and the list receives the coefficient table.
         `stitch` (`edit_region_vae_halo`): (the device source frames, the box, the region's rectangle, the feather) -- the latents are
         the box's, and wan_video_box_stitch_u8 writes the whole frames instead: the source's bytes from frame 0 on, the decoder's inside
         the rectangle."""
@@ -311,6 +315,9 @@ class WanPipeline:
         else:
             clip = ops.video_box_stitch_u8(frames, stitch[0], stitch[1], stitch[2], stitch[3], out=clip, dst_frame=dst_frame)
         seg = clip[:, dst_frame:dst_frame + frames.shape[2]]
+        if match is not None:
+            from . import video_io
+            match[3].append(video_io._color_match_segment(seg, *match[:3]))
         if keep is not None:
             keep.append(seg)
         if out is None:
@@ -356,6 +363,15 @@ class WanPipeline:
         """The keywords of ``__call__`` that travel in `switches` (as `as_uint8` is decode_latents': the named parameters stay the
         reference's plus the extensions tests/test_oracle_vs_reference.py lists), and every check of them that needs no device."""
         o = SimpleNamespace(
+            # `color_match=False`: True, or a dict of `pool_t`, `gain`, `min_pixels` (video_io.color_match's, with its defaults, which are
+            # guesses): the edit segment's uint8 frames are brought back to the colours of the uint8 source frames on the device -- one
+            # gain and offset per frame and RGB channel, estimated where `edit_mask` is 0 (everywhere without a mask), applied to the
+            # whole frame -- before they are copied to the host and before the compare clip is composed; the table is returned in
+            # `color_match` (device int32; with `video` and `edit_mask` on the device no synchronisation is added, from the host they are
+            # uploaded once more first).  Needs uint8 frames as `video` and output_type="uint8".  Not with
+            # `edit_region_vae_halo`.  Opt-in; no quality claim.
+            color_match=switches.pop("color_match", False),
+            color_args=None, color_source=None,          # set below: (pool_t, gain, min_pixels) checked (None: off); the uint8 source frames
             mask_args=None, compare_source=None,         # set below: (grow, grow_t, feather) checked; the uint8 source frames of compare=True
             # compare=True: also return the reference's compare clip (save_side_by_side, fast_infer.py:183-206, as its writer's bytes) in
             # `compare_videos`, composed on the device from the uint8 source frames and the edit segment (video_io.compare_frames)
@@ -427,6 +443,9 @@ class WanPipeline:
             region_split=None)                           # set below: the most boxes, checked (None: one rectangle)
         if switches:
             raise TypeError(f"__call__() got an unexpected keyword argument {next(iter(switches))!r}")
+        if o.color_match is not False and o.color_match is not None and o.edit_region_vae_halo is not None:
+            raise ValueError("color_match with edit_region_vae_halo: the pixels to estimate from there are the ring of the decoded box "
+                             "around the region's rectangle, which the stitch discards; the two do not combine")
         if o.edit_mask is not None:
             from . import video_io
             _require_source(has_source, "edit_mask: outside the mask the clip is kept on its source")
@@ -509,6 +528,23 @@ class WanPipeline:
             if not torch.is_tensor(src) or src.dtype != torch.uint8 or src.dim() not in (4, 5) or src.shape[-1] != 3:
                 raise ValueError("compare=True needs the uint8 source frames as `video` ([T, H, W, 3] or [B, T, H, W, 3]), got "
                                  f"{getattr(src, 'dtype', type(src))} {tuple(getattr(src, 'shape', ()))}")
+        if o.color_match is not False and o.color_match is not None:
+            from . import video_io
+            if o.color_match is not True and not isinstance(o.color_match, dict):
+                raise ValueError(f"color_match={o.color_match!r}: True, or a dict of pool_t, gain, min_pixels")
+            args = {} if o.color_match is True else dict(o.color_match)
+            o.color_args = video_io._color_args("color_match", args.pop("pool_t", 2), args.pop("gain", True), args.pop("min_pixels", 1024))
+            if args:
+                raise ValueError(f"color_match: unknown key {next(iter(args))!r} (pool_t, gain, min_pixels)")
+            if output_type != "uint8":
+                raise ValueError(f"color_match matches uint8 frames on the device: it needs output_type='uint8', not {output_type!r}")
+            src = o.color_source = torch.from_numpy(video) if isinstance(video, np.ndarray) else video
+            if not torch.is_tensor(src) or src.dtype != torch.uint8 or src.dim() not in (4, 5) or src.shape[-1] != 3:
+                raise ValueError("color_match needs the uint8 source frames as `video` ([T, H, W, 3] or [B, T, H, W, 3]), got "
+                                 f"{getattr(src, 'dtype', type(src))} {tuple(getattr(src, 'shape', ()))}")
+            if tuple(src.shape[-4:-1]) != (source_frames, height, width):
+                raise ValueError(f"color_match: `video` {tuple(src.shape)} is not [{source_frames}, {height}, {width}, 3] or [B, "
+                                 f"{source_frames}, {height}, {width}, 3] (source_frames, height, width of this call)")
         return o
 
     def _set_timesteps(self, num_inference_steps, shift, device):
@@ -901,9 +937,9 @@ class WanPipeline:
             return loop(lat, emb)
         return self._graphed_loop(key, latents, embeds, loop_fn, keep=(timesteps, self.scheduler.sigmas))
 
-    def _decode_outputs(self, latents, output_type, cot, cc, G, compare_source, return_dict, stitch=None):
+    def _decode_outputs(self, latents, output_type, cot, cc, G, compare_source, return_dict, stitch=None, match=None):
         """:757-790 -- decode only the grounding and edit segments: (videos, ground_videos, edit_videos, compare_videos).  `stitch`: see
-        _decode_frames_u8 -- the frames have the source's size then, not the latents'."""
+        _decode_frames_u8 -- the frames have the source's size then, not the latents'.  `match`: see there; the edit segment only."""
         ground_video = edit_video = video_out = compare_out = None
         if output_type == "latent":
             return video_out, ground_video, edit_video, compare_out
@@ -931,21 +967,21 @@ class WanPipeline:
                 clip = torch.empty(shape, dtype=dtype, pin_memory=True)
                 dev_clip = torch.empty(clip.shape, dtype=torch.uint8, device=latents.device) if u8 else None
 
-            def segment(lat, a, b, keep=None):      # latent frames `lat` decoded into frames [a, b) of the clip
+            def segment(lat, a, b, keep=None, match=None):      # latent frames `lat` decoded into frames [a, b) of the clip
                 if u8:
-                    return self._decode_frames_u8(lat, clip[:, a:b], dev_clip, a, keep, stitch)
+                    return self._decode_frames_u8(lat, clip[:, a:b], dev_clip, a, keep, stitch, match)
                 return self.decode_latents(lat, None if clip is None else clip[:, :, a:b])
             if ng:
                 ground_video = segment(latents[:, :, g0:g1], 0, ng)
             if ne:
-                edit_video = segment(latents[:, :, g1:], ng, ng + ne, edit_dev)
+                edit_video = segment(latents[:, :, g1:], ng, ng + ne, edit_dev, match)
             if clip is not None:
                 video_out = clip.numpy()
             elif not u8:
                 video_out = np.concatenate([v for v in (ground_video, edit_video) if v is not None], axis=2)
         elif cc < Ftot:
-            video_out = edit_video = (self._decode_frames_u8(latents[:, :, cc:], None, keep=edit_dev, stitch=stitch)
-                                      if edit_dev is not None or stitch is not None else self.decode_latents(latents[:, :, cc:], as_uint8=u8))
+            video_out = edit_video = (self._decode_frames_u8(latents[:, :, cc:], None, keep=edit_dev, stitch=stitch, match=match)
+                                      if edit_dev is not None or stitch is not None or match is not None else self.decode_latents(latents[:, :, cc:], as_uint8=u8))
         if edit_dev:
             from . import video_io
             src = (compare_source if compare_source.dim() == 5 else compare_source.unsqueeze(0)).to(edit_dev[0].device)
@@ -1080,11 +1116,19 @@ class WanPipeline:
         self._stage("denoise_loop", t_stage)
         # -- decode (:757-790)
         t_stage = self._stage("vae_decode")
+        match = None
+        if opt.color_args is not None:
+            # one upload of the source frames and the mask where they came from the host (compare=True then takes the same device frames)
+            src = opt.color_source.to(latents.device)
+            if opt.compare_source is not None and not opt.compare_source.is_cuda:
+                opt.compare_source = src
+            match = (src, None if opt.edit_mask is None else opt.edit_mask.to(latents.device), opt.color_args, [])
         videos, ground, edit, compared = self._decode_outputs(latents, output_type, cot, condition_count, ground_latent_count,
-                                                              opt.compare_source, return_dict, stitch)
+                                                              opt.compare_source, return_dict, stitch, match)
         self._stage("vae_decode", t_stage)
         tracked = region is not None and opt.region_follow is not None
         return WanPipelineOutput(videos=videos, ground_videos=ground, edit_videos=edit, latents=latents, compare_videos=compared,
+                                 color_match=match[3][0] if match is not None and match[3] else None,
                                  edit_region=None if region is None else (region[0].enclosing() if tracked or boxes > 1 else region[0]).pixels(
                                      getattr(getattr(self.vae, "config", None), "spatial_compression_ratio", 8)),
                                  edit_regions=None if boxes == 1 else region[0].pixels(

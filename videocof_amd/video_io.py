@@ -39,6 +39,11 @@ x264's 8-bit SSIM; ``ClipStats`` turns those into PSNR, MAE, quantiles, SSIM and
 ``vae_roundtrip_frames`` gives the clip a checkpoint's VAE alone makes of a clip, the floor under every such number.
 ``reference_clip_stats`` states the definition in numpy and is what the kernels equal word for word.
 
+Bring the edit's colours back to the source's: ``color_match`` estimates one gain and offset per frame and RGB channel from the pixels
+the edit left alone (``wan_color_stats``, ``wan_color_coef``) and applies it to the whole frame (``wan_frames_u8_affine``), in exact
+integers; ``reference_color_match`` and its three steps state the definition in Python ints.  It stands where
+the reference's writer has ``color_transfer_post_process``, and is not that function: no LAB, no OpenCV tables.
+
 What the writer makes of more than one sample, and the compare clip: ``grid_frames`` is ``save_videos_grid`` up to the encoder
 (videox_fun/utils/utils.py:59-68: the ``make_grid(nrow=6)`` mosaic with its 2-pixel zero border, ``rescale``, the byte conversion)
 and ``compare_frames`` is ``save_side_by_side`` (fast_infer.py:183-206: ``_normalize_to_01`` of source and edit, the crop to the
@@ -66,6 +71,8 @@ __all__ = ["frames_to_video", "video_to_frames", "load_video_frames", "reference
            "change_mask", "composite_frames", "keep_unedited", "reference_change_mask", "reference_composite_frames",
            "latent_edit_mask", "fit_mask", "reference_latent_edit_mask", "reference_masked_prediction", "reference_fit_mask",
            "ClipStats", "clip_stats", "reference_clip_stats", "vae_roundtrip_frames",
+           "color_match", "color_match_coefficients", "reference_color_match", "reference_color_stats", "reference_color_coefficients",
+           "reference_frames_affine",
            "grid_layout", "grid_frames", "compare_frames", "reference_grid_frames", "reference_compare_frames",
            "select_frame_indices", "yuv_matrix", "chroma_shape", "yuv_to_frames", "frames_to_yuv", "reference_yuv_to_frames",
            "reference_frames_to_yuv", "YuvClip", "read_y4m", "load_y4m_frames", "write_y4m"]
@@ -828,6 +835,191 @@ def vae_roundtrip_frames(vae, frames_u8) -> torch.Tensor:
     latents = torch.cat([vae.encode(video[i:i + 1])[0].mode() for i in range(video.shape[0])])
     frames = ops.video_to_frames_u8(vae.decode(latents.to(vae.dtype)).sample)
     return frames if x.dim() == 5 else frames[0]
+
+
+# ---------------------------------------------------------------------------------------------- colour match
+COLOR_ONE, COLOR_MAX_POOL_T = ops.COLOR_ONE, ops.COLOR_MAX_POOL_T
+
+
+def _color_args(what: str, pool_t, gain, min_pixels) -> Tuple[int, bool, int]:
+    if isinstance(pool_t, bool) or not isinstance(pool_t, (int, np.integer)) or not 0 <= int(pool_t) <= COLOR_MAX_POOL_T:
+        raise ValueError(f"{what}: pool_t={pool_t!r} (an int, 0..{COLOR_MAX_POOL_T})")
+    if isinstance(min_pixels, bool) or not isinstance(min_pixels, (int, np.integer)) or not 0 <= int(min_pixels) < 2 ** 31:
+        raise ValueError(f"{what}: min_pixels={min_pixels!r} (an int, 0..2^31 - 1)")
+    if not isinstance(gain, (bool, np.bool_)):
+        raise ValueError(f"{what}: gain={gain!r} (True or False)")
+    return int(pool_t), bool(gain), int(min_pixels)
+
+
+def _color_clips(what: str, edit, ref, alpha):
+    """The three as tensors ``[B, T, H, W, 3]``, ``[B, T or 1, H, W, 3]`` and ``[B, T or 1, H, W]`` / None (views, wherever they
+    live), and the edit's leading sizes."""
+    e, r = (torch.from_numpy(v) if isinstance(v, np.ndarray) else v for v in (edit, ref))
+    if not torch.is_tensor(e) or e.dtype != torch.uint8 or e.dim() not in (4, 5) or e.shape[-1] != 3:
+        raise ValueError(f"{what}: edit_u8: expected uint8 [T, H, W, 3] or [B, T, H, W, 3] frames, got "
+                         f"{getattr(e, 'dtype', type(e))} {tuple(getattr(e, 'shape', ()))}")
+    lead = tuple(e.shape[:-3])
+    e5 = e if e.dim() == 5 else e.unsqueeze(0)
+    B, T, H, W, _ = (int(v) for v in e5.shape)
+    if not torch.is_tensor(r) or r.dtype != torch.uint8:
+        raise ValueError(f"{what}: ref_u8: expected a uint8 tensor, got {getattr(r, 'dtype', type(r))}")
+    one_frame = r.dim() == 3 and e.dim() == 4                                   # [H, W, 3] for the clip, its alpha [H, W]
+    if one_frame:
+        r = r[None]
+    if tuple(r.shape) not in (tuple(e.shape), lead[:-1] + (1, H, W, 3)):
+        raise ValueError(f"{what}: ref_u8 {tuple(r.shape)} for an edit {tuple(e.shape)}: expected the edit's shape, or one frame per "
+                         f"sample ({'[H, W, 3] or [1, H, W, 3]' if e.dim() == 4 else '[B, 1, H, W, 3]'})")
+    r5 = r if r.dim() == 5 else r.unsqueeze(0)
+    a4 = None
+    if alpha is not None:
+        a = torch.from_numpy(alpha) if isinstance(alpha, np.ndarray) else alpha
+        if torch.is_tensor(a) and a.dim() == 2 and one_frame:
+            a = a[None]
+        if not torch.is_tensor(a) or a.dtype != torch.uint8 or tuple(a.shape) != tuple(r.shape[:-1]):
+            raise ValueError(f"{what}: alpha {getattr(a, 'dtype', type(a))} {tuple(getattr(a, 'shape', ()))} for a ref_u8 "
+                             f"{tuple(r.shape)}: expected uint8 {tuple(r.shape[:-1])}")
+        a4 = a if a.dim() == 4 else a.unsqueeze(0)
+    return e5, r5, a4, lead
+
+
+def reference_color_stats(ref_u8, edit_u8, alpha=None) -> np.ndarray:
+    """The sums ``color_match`` estimates from, in numpy int64 on the host: int64 ``[.., T, 16]`` = per frame
+    ``n``, then ``A, E, AA, EE`` per channel -- the sums of ``ref``, of ``edit`` and of their squares over the pixels whose ``alpha``
+    is 0 -- and three zero words.  What ``wan_color_stats`` equals word for word; never called by the product path."""
+    e, r, a, lead = _color_clips("reference_color_stats", *(None if v is None else torch.as_tensor(v).cpu() for v in (edit_u8, ref_u8, alpha)))
+    e, r = e.numpy().astype(np.int64), r.numpy().astype(np.int64)
+    B, T, H, W, _ = e.shape
+    r = np.broadcast_to(r, e.shape)
+    on = np.ones((B, T, H, W, 1), np.int64) if a is None else np.broadcast_to((a.numpy() == 0).astype(np.int64)[..., None], (B, T, H, W, 1))
+    words = np.zeros((B, T, ops.COLOR_STATS_WORDS), np.int64)
+    words[..., 0] = on.sum((2, 3, 4))
+    for k, x in enumerate((r, e, r * r, e * e)):
+        words[..., 1 + k:13:4] = (x * on).sum((2, 3))
+    return words.reshape(*lead, ops.COLOR_STATS_WORDS)
+
+
+def reference_color_coefficients(stats, *, pool_t: int = 2, gain: bool = True, min_pixels: int = 1024) -> np.ndarray:
+    """``(g, b)`` per frame and channel from the sums of ``reference_color_stats``, in Python ints: int64 ``[.., T, 16]`` -> int32
+    ``[.., T, 3, 2]``.  The sums of frame ``t`` are pooled over frames ``t - pool_t .. t + pool_t`` of its sample; then, with
+    ``ONE = 4096``: below ``max(1, min_pixels)`` counted pixels ``(ONE, 0)``; else ``g = isqrt(((Vs >> k) << 24) // (Ve >> k))``
+    clamped to ``[ONE / 2, 2 * ONE]`` with ``Vs = n * AA - A * A``, ``Ve = n * EE - E * E`` and ``k`` what brings the larger to 38
+    bits (``ONE`` where ``gain`` is off or ``Ve == 0``, ``2 * ONE`` where the shift leaves nothing of ``Ve``), and
+    ``b = (ONE * A - g * E + n // 2) // n``.  What ``wan_color_coef`` equals word for word."""
+    pool_t, gain, min_pixels = _color_args("reference_color_coefficients", pool_t, gain, min_pixels)
+    s = np.asarray(stats.cpu() if torch.is_tensor(stats) else stats)
+    if s.dtype != np.int64 or s.ndim not in (2, 3) or s.shape[-1] != ops.COLOR_STATS_WORDS:
+        raise ValueError(f"reference_color_coefficients: stats: expected int64 [T, 16] or [B, T, 16], got {s.dtype} {s.shape}")
+    lead = s.shape[:-1]
+    s3 = s.reshape(-1, lead[-1], ops.COLOR_STATS_WORDS)
+    T, ONE = s3.shape[1], COLOR_ONE
+    coef = np.zeros((s3.shape[0], T, 3, 2), np.int32)
+    for bi in range(s3.shape[0]):
+        for t in range(T):
+            pooled = [sum(int(s3[bi, u, w]) for u in range(max(t - pool_t, 0), min(t + pool_t, T - 1) + 1)) for w in range(13)]
+            n = pooled[0]
+            for c in range(3):
+                A, E, AA, EE = pooled[1 + 4 * c:5 + 4 * c]
+                g, b = ONE, 0
+                if n >= max(1, min_pixels):
+                    Vs, Ve = n * AA - A * A, n * EE - E * E
+                    if gain and Ve != 0:
+                        k = max(0, max(Vs, Ve).bit_length() - 38)
+                        vs, ve = Vs >> k, Ve >> k
+                        g = 2 * ONE if ve == 0 else math.isqrt((vs << 24) // ve)
+                        g = min(max(g, ONE // 2), 2 * ONE)
+                    b = (ONE * A - g * E + (n >> 1)) // n
+                coef[bi, t, c] = (g, b)
+    return coef.reshape(*lead, 3, 2)
+
+
+def reference_frames_affine(frames_u8, coef) -> torch.Tensor:
+    """``clamp((g * x + b + 2048) >> 12, 0, 255)`` per byte in numpy int64: uint8 ``[.., H, W, 3]`` frames and int ``[.., 3, 2]``
+    coefficients with the same leading sizes.  What ``wan_frames_u8_affine`` equals byte for byte."""
+    x = torch.as_tensor(frames_u8).cpu()
+    k = np.asarray(coef.cpu() if torch.is_tensor(coef) else coef).astype(np.int64)
+    if x.dtype != torch.uint8 or x.dim() < 3 or x.shape[-1] != 3 or k.shape != tuple(x.shape[:-3]) + (3, 2):
+        raise ValueError(f"reference_frames_affine: uint8 [.., H, W, 3] frames and [.., 3, 2] coefficients, got {x.dtype} "
+                         f"{tuple(x.shape)} and {k.shape}")
+    g, b = k[..., None, None, :, 0], k[..., None, None, :, 1]
+    y = (g * x.numpy().astype(np.int64) + b + COLOR_ONE // 2) >> 12
+    return torch.from_numpy(np.ascontiguousarray(np.clip(y, 0, 255).astype(np.uint8)))
+
+
+def reference_color_match(edit_u8, ref_u8, alpha=None, *, pool_t: int = 2, gain: bool = True, min_pixels: int = 1024) -> torch.Tensor:
+    """The definition of ``color_match`` on the host: ``reference_color_stats``, ``reference_color_coefficients``,
+    ``reference_frames_affine``.  Never called by the product path."""
+    coef = reference_color_coefficients(reference_color_stats(ref_u8, edit_u8, alpha), pool_t=pool_t, gain=gain, min_pixels=min_pixels)
+    return reference_frames_affine(edit_u8, coef)
+
+
+def _color_coefficients(what: str, edit_u8, ref_u8, alpha, pool_t, gain, min_pixels):
+    pool_t, gain, min_pixels = _color_args(what, pool_t, gain, min_pixels)
+    e, r, a, lead = _color_clips(what, edit_u8, ref_u8, alpha)
+    if not e.is_cuda:
+        e = e.to(torch.device("cuda", torch.cuda.current_device()))          # bytes over the host link, as they are
+    r, a = r.to(e.device), None if a is None else a.to(e.device)
+    return e, ops.color_coef(ops.color_stats(r, e, a), pool_t, gain, min_pixels), lead
+
+
+def _color_match_segment(seg: torch.Tensor, source_u8: torch.Tensor, mask: Optional[torch.Tensor], args):
+    """``WanPipeline(color_match=...)``: the edit segment's device frames ``[B, T, H, W, 3]`` matched IN PLACE to the source frames
+    where ``mask`` (``edit_mask``: ``[T, H, W]`` / ``[B, T, H, W]``) is 0 -> the coefficients ``[B, T, 3, 2]``.  ``seg`` may be a frame
+    range of a longer clip: a sample's frames are contiguous then, the batch is not, and the samples go one by one (pooling never
+    crosses a sample, so that is the same result); one source or mask for several samples is paired with each the same way, without
+    a copy.  With ``source_u8`` and ``mask`` on the device this is launches only; tensors on the host are uploaded here first, which
+    waits for the stream as every such copy does."""
+    B, T, H, W, _ = (int(v) for v in seg.shape)
+    src = (source_u8 if source_u8.dim() == 5 else source_u8.unsqueeze(0)).to(seg.device)
+    if tuple(src.shape[1:]) != (T, H, W, 3) or src.shape[0] not in (1, B):
+        raise ValueError(f"color_match: the edit segment is {tuple(seg.shape)} and the source frames are {tuple(src.shape)}: one "
+                         "transform per frame needs a source frame for every edit frame")
+    if mask is not None:
+        mask = (mask if mask.dim() == 4 else mask.unsqueeze(0)).to(seg.device)
+    whole = seg.is_contiguous() and src.shape[0] == B and (mask is None or mask.shape[0] == B)
+    coef = torch.empty(B, T, 3, 2, device=seg.device, dtype=torch.int32)
+    for b in (slice(0, B),) if whole else (slice(k, k + 1) for k in range(B)):
+        one = (lambda t: t[b] if t.shape[0] == B else t)                                # a sample's own source / mask, or the shared one
+        n = b.stop - b.start
+        ops.color_coef(ops.color_stats(one(src), seg[b], None if mask is None else one(mask)), *args, out=coef[b])
+        flat = seg[b].view(n * T, H, W, 3)
+        ops.frames_u8_affine(flat, coef[b].view(n * T, 3, 2), out=flat)
+    return coef
+
+
+def color_match_coefficients(edit_u8, ref_u8, alpha=None, *, pool_t: int = 2, gain: bool = True, min_pixels: int = 1024) -> torch.Tensor:
+    """The table ``color_match`` applies: int32 ``[T, 3, 2]`` / ``[B, T, 3, 2]`` = ``(g, b)`` per frame and channel on the device, in
+    units of 1/4096 (``out = (g * x + b + 2048) >> 12``), for callers who want to look at it or apply it elsewhere
+    (``ops.frames_u8_affine``).  The arguments are ``color_match``'s."""
+    _, coef, lead = _color_coefficients("color_match_coefficients", edit_u8, ref_u8, alpha, pool_t, gain, min_pixels)
+    return coef.view(*lead, 3, 2)
+
+
+def color_match(edit_u8, ref_u8, alpha=None, *, pool_t: int = 2, gain: bool = True, min_pixels: int = 1024,
+                out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Bring the edit's colours back to the reference clip's: per frame and RGB channel one gain and offset, estimated from the pixels
+    the edit left alone and applied to the WHOLE frame, on the device in exact integers (``wan_color_stats``, ``wan_color_coef``,
+    ``wan_frames_u8_affine``: four launches; the definition is ``reference_color_match``).  The gain is the
+    ratio of the standard deviations and the offset what then makes the means equal -- Reinhard's transfer, per RGB channel.
+
+    ``edit_u8``: uint8 ``[T, H, W, 3]`` or ``[B, T, H, W, 3]``, host or device.  ``ref_u8``: the clip to match, of the same shape --
+    or ONE frame, ``[H, W, 3]`` / ``[1, H, W, 3]`` / ``[B, 1, H, W, 3]``, which every frame of the sample is then matched to
+    (``ref_u8 = edit_u8[:1]`` is the rule of the reference's ``color_transfer_post_process``: every frame towards frame 0).
+    ``alpha``: uint8 of ``ref_u8``'s ``[.., H, W]`` as ``change_mask`` returns it, or None: only pixels with ``alpha == 0`` are
+    estimated from; None counts all.  ``pool_t``: the sums of a frame are pooled with those of ``pool_t`` frames either side (within
+    a sample), ``0 <= pool_t <= 8``; a value of ``T - 1`` or more gives one transform for the clip.  ``gain=False``: offsets only.
+    A frame (pooled) with fewer than ``min_pixels`` counted pixels is left as it is.  Else ``ValueError``.  ``out``: a page-locked
+    uint8 host tensor of the edit's shape, filled by one copy and returned, as in ``composite_frames``; without it the device
+    frames are returned (a new tensor; ``edit_u8`` is not written).
+
+    The defaults ``pool_t=2`` and ``min_pixels=1024`` are guesses: no real checkpoint has been run, so how much the round trip's
+    shift wobbles from frame to frame, and how few pixels still give a stable estimate, has not been measured.  Limits: this is RGB
+    per channel, so a hue rotation is not corrected; it is one transform per frame, so a shift that varies over the frame is not;
+    it is NOT OpenCV's 8-bit LAB transfer, which the reference's writer uses.  No quality is claimed:
+    ``clip_stats(source, matched, alpha=mask)`` is the tool to judge the result with."""
+    e, coef, lead = _color_coefficients("color_match", edit_u8, ref_u8, alpha, pool_t, gain, min_pixels)
+    B, T, H, W, _ = e.shape
+    res = ops.frames_u8_affine(e.contiguous().view(B * T, H, W, 3), coef.view(B * T, 3, 2)).view(*lead, H, W, 3)
+    return _to_host(res, out, "color_match")
 
 
 # ---------------------------------------------------------------------------------------------- the writer's grid, the compare clip
